@@ -42,8 +42,6 @@ import argparse
 import contextlib
 import json
 import os
-
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")  # before the HIP runtime initialises: see columbiaimagesearch_amd/_lib.py
 import sys
 import threading
 import time
@@ -275,9 +273,10 @@ def scan_binding(cfg_name, scan_name, cand, cand_items, M, scan_s, launches):
     return out
 
 
-def search_leg(ctx, cfg_name, n_vectors, S, steps, warmup, scaling, oracle_rows):
+def search_leg(ctx, cfg_name, n_vectors, S, steps, warmup, scaling, oracle_rows, one_window=False):
     """Build the index of one configuration (encode on the GPUs, device-side insert, R x S layout with S cell shards) and time
-    `steps` query batches.  Returns (result dict (rank 0's view), state for the follow-up legs)."""
+    `steps` query batches (one_window: exactly `steps` steps are timed, in one repetition -- the headline, whose --steps is the number
+    of timed steps).  Returns (result dict (rank 0's view), state for the follow-up legs; `last_out` = the last timed step's result)."""
     import torch.distributed as dist
     from columbiaimagesearch_amd.distributed import GridSearcher, greedy_cell_owner
     from columbiaimagesearch_amd.lopq import LOPQSearcherHIP
@@ -439,17 +438,18 @@ def search_leg(ctx, cfg_name, n_vectors, S, steps, warmup, scaling, oracle_rows)
     from columbiaimagesearch_amd import _lib as _cl
 
     def run_steps(first):
-        """Exactly `steps` steps (batches first ... first + steps - 1); returns (candidates, work items) of this rank."""
+        """Exactly `steps` steps (batches first ... first + steps - 1); returns (candidates, work items, the last step's result) of
+        this rank."""
         cand = cand_items = 0
         if sharded is None:
             for b in range(steps):
                 sv, stream = lanes[b % P]
                 with torch.cuda.stream(stream):
-                    sv.search_batch_dev(qb(first + b), quota=QUOTA, limit=LIMIT)
+                    out = sv.search_batch_dev(qb(first + b), quota=QUOTA, limit=LIMIT)
                 ls = sv.last_stats()
                 cand += ls["candidates"]
                 cand_items += ls["items"]
-            return cand, cand_items
+            return cand, cand_items, out
         # steps are independent batches: the exchange + merge of batch b (side stream, RCCL) overlap the partial search
         # of batch b+1 (compute stream)
         def stats_of(hh):
@@ -468,14 +468,16 @@ def search_leg(ctx, cfg_name, n_vectors, S, steps, warmup, scaling, oracle_rows)
             cand_items += i_
             st.exchange_flags.append(sharded.search_end(h, check=False).get("overflow"))
             h = h2
-        st.exchange_flags.append(sharded.search_end(h, check=False).get("overflow"))
-        return cand, cand_items
+        out = sharded.search_end(h, check=False)
+        st.exchange_flags.append(out.get("overflow"))
+        return cand, cand_items, out
 
     # Timed region: REPETITIONS of exactly `steps` steps, each bracketed by barrier + synchronize on both sides (the contract's
     # bracket) and timed twice -- host wall clock (what `value` is made of: the max over ranks, then the MEDIAN over repetitions) and a
     # pair of HIP events around the same steps (start on the launch stream, end after every lane's stream joined it).  One
     # repetition of 20 steps is 8 ms: a single host hiccup used to decide the figure; repetitions continue until >= 0.5 s are
-    # timed (at least 5, at most 400).  wall >> events, or a workspace allocation inside the region, marks the leg `suspect`.
+    # timed (at least 5, at most 400).  one_window (the headline): one repetition, the caller sizes --steps from ms_per_step.  wall >>
+    # events, or a workspace allocation inside the region, marks the leg `suspect`.
     st.exchange_flags = []
     main_stream = torch.cuda.current_stream(device)
     lane_streams = [s_ for _, s_ in lanes if s_ is not None and s_ != main_stream] if sharded is None else \
@@ -492,7 +494,7 @@ def search_leg(ctx, cfg_name, n_vectors, S, steps, warmup, scaling, oracle_rows)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             t0 = time.perf_counter()
             e0.record(main_stream)
-            c_, i_ = run_steps(warmup + reps * steps)
+            c_, i_, st.last_out = run_steps(warmup + reps * steps)
             for s_ in lane_streams:
                 main_stream.wait_stream(s_)
             if sharded is not None and getattr(sharded.row, "_side", None) is not None:
@@ -513,7 +515,7 @@ def search_leg(ctx, cfg_name, n_vectors, S, steps, warmup, scaling, oracle_rows)
             cand += c_
             cand_items += i_
             reps += 1
-            if reps >= 400 or (reps >= min_reps and sum(walls) >= min_timed_s):
+            if one_window or reps >= 400 or (reps >= min_reps and sum(walls) >= min_timed_s):
                 break
         scan_name = searcher.last_stats()["scan_kernel"]
     alloc1 = _cl.alloc_stats()
@@ -1396,12 +1398,13 @@ def collectives_leg(ctx, L=None, row_bytes=1024):
     return out
 
 
-def routed_leg(ctx, st, steps, warmup, strong=False):
+def routed_leg(ctx, st, steps, warmup, strong=False, one_window=False):
     """N > 1, cells only (S = N): the ROUTED protocol (columbiaimagesearch_amd/distributed.py: RoutedSearcher) on the index of the headline
     leg.  A step = one batch of world x NQ queries over the job: every rank is the HOME of NQ of them (its own batch), finds the owners
     of the cells they visit, sends each query to those owners only (one all-to-all), answers what it receives and merges its home
     queries' lists.  Per-GPU work is fixed as N grows (NQ home queries, ~NQ received): weak scaling of the QUERY load over ONE 10M
-    index sharded by coarse cell.  Before the timed region the protocol is compared with the all-gather protocol on one batch."""
+    index sharded by coarse cell.  Before the timed region the protocol is compared with the all-gather protocol on one batch.
+    one_window: exactly `steps` steps are timed, in one repetition (the headline)."""
     import torch.distributed as dist
     from columbiaimagesearch_amd.distributed import RoutedSearcher, home_slice
     device, rank, world, wd = ctx.device, ctx.rank, ctx.world, ctx.wd
@@ -1459,7 +1462,7 @@ def routed_leg(ctx, st, steps, warmup, strong=False):
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             walls.append(float(tt.item()))
             reps += 1
-            if reps >= 400 or (reps >= min_reps and sum(walls) >= min_timed_s):
+            if one_window or reps >= 400 or (reps >= min_reps and sum(walls) >= min_timed_s):
                 break
     med = sorted(walls)[len(walls) // 2]
     return {"metric": "queries/sec @ recall@10 on 10M LOPQ index",
@@ -1581,6 +1584,17 @@ def compact_line(line):
     return out
 
 
+def dump_outputs(out_dir, out):
+    """--dump-outputs: the result of the headline leg's last timed step as its caller receives it (search_batch_dev: ranked ids,
+    distances, hits per query, codes visited per query; at N > 1 rank 0's merged answer of the all-gather protocol), one float64 .npy
+    per array -- ids and counts are exact in float64.  8192 queries x limit 100: 13 MB."""
+    arrays = {k: out[k].cpu().numpy().astype(np.float64) for k in ("ids", "dists", "n_found", "visited")}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def emit_lines(line, compact, detail_file=None):
     # the JSON lines are the last thing on stdout: flush what native libraries (the RCCL banner) still hold in C stdio first
     try:
@@ -1629,7 +1643,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-cnn", action="store_true")
     ap.add_argument("--no-pcie", action="store_true", help="skip the host-pointer leg (profiling runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the headline's last timed step returned to DIR/<name>.npy (float64): "
+                                                          "the output of two builds on the same arguments can be compared array for array")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     explicit_config = args.config is not None
     only_c4x = args.config == "c4x"
     cfg_name = "c4" if (args.config is None or only_c4x) else args.config
@@ -1704,12 +1722,14 @@ def main():
         emit_lines(line, compact_line(line), args.detail_file)
         return
     # ---- headline: BASELINE C4's layout -- ONE copy of the index sharded by coarse cell over all N GPUs ---------------------------
-    head, st = search_leg(ctx, cfg_name, args.n, world, args.steps, args.warmup, args.scaling, 4096 if want_oracle else 0)
+    head, st = search_leg(ctx, cfg_name, args.n, world, args.steps, args.warmup, args.scaling, 4096 if want_oracle else 0, one_window=True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, st.last_out)
 
     routed = routed_strong = None
     if world > 1 and st.sharded is not None and st.sharded.row is not None and not args.no_routed:
         try:
-            routed = routed_leg(ctx, st, args.steps, args.warmup)
+            routed = routed_leg(ctx, st, args.steps, args.warmup, one_window=True)
         except Exception as e:  # the all-gather headline stands on its own
             routed = {"error": repr(e)}
             sys.stderr.write("[bench rank %d] routed leg failed: %r\n" % (rank, e))

@@ -381,12 +381,12 @@ def test_query_groups_times_cell_shards_with_four_ranks_on_one_gpu():
         assert "world 4 grid %s: build and search equal the single index" % shape in text, text[-3000:]
 
 
-@pytest.mark.parametrize("gpus,shards,grid_groups", [(2, 0, 2), (4, 0, 2), (4, 1, 4), (8, 0, 4)])
+@pytest.mark.parametrize("gpus,shards,grid_groups", [(2, 0, 2), (4, 0, 2), (4, 1, 4)])
 def test_bench_multi_rank_protocol_on_one_gpu(gpus, shards, grid_groups):
     """`bench.py --gpus N`: the headline is BASELINE C4's layout (ONE copy of the index sharded by cell over all N ranks) answered by the
-    routed protocol; the all-gather protocol (`allgather`) and the R x S grid (`grid`, whose value counts every group's queries) ride along.  N = 8 is the size the
-    driver's scaling run uses: cells only (1 x 8) as the headline, the default 4 x 2 grid beside it.  stdout ends with the `#detail`
-    line (every field) and ONE compact JSON line (what the driver parses)."""
+    routed protocol; the all-gather protocol (`allgather`) and the R x S grid (`grid`, whose value counts every group's queries) ride along.
+    N stays at 4 or below: the ranks and this process all hold the one GPU, which a shared machine allows to at most 6 processes at once.
+    stdout ends with the `#detail` line (every field) and ONE compact JSON line (what the driver parses)."""
     import json, os, subprocess, sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, CIS_BENCH_BACKEND="gloo", CIS_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0", CIS_BENCH_N="400000",
@@ -417,7 +417,7 @@ def test_bench_multi_rank_protocol_on_one_gpu(gpus, shards, grid_groups):
     assert line["config"]["query_groups"] == 1 and line["config"]["cell_shards"] == gpus and line["config"]["queries_per_step"] == gpus * 8192
     assert abs(line["value"] - line["config"]["queries_per_step"] * 3 / (line["ms_per_step"] * 3e-3)) <= 1e-6 * line["value"]
     assert line["config"]["index_vectors"] == 400000
-    assert line["timing"]["repetitions"] >= 2 and line["timing"]["steps_per_repetition"] == 3
+    assert line["timing"]["repetitions"] == 1 and line["timing"]["steps_per_repetition"] == 3   # the headline times exactly --steps steps
     # ... and the all-gather protocol at 8192 queries per step over the whole job (strong) beside it
     a = line["allgather"]
     assert a["scaling"] == "strong" and a["config"]["cell_shards"] == gpus and a["config"]["queries_per_step"] == 8192 and a["recall_at_10"] >= 0.9
