@@ -5755,7 +5755,7 @@ __global__ void k_route_rows(const uint32_t* __restrict__ q, int nq, int W /* 32
 extern "C" int cis_route_queries_dev(const void* d_q, int nq, int row_bytes, const uint64_t* d_mask, int world, int cap, void* d_out_q,
                                      int32_t* d_slot, int32_t* d_cnt, int32_t* d_overflow, void* stream) {
     CIS_REQUIRE(nq >= 0 && row_bytes > 0 && row_bytes % 4 == 0 && world >= 1 && world <= 64 && cap >= 1, "route: sizes out of range");
-    CIS_REQUIRE(d_slot && d_cnt && d_overflow && (nq == 0 || (d_q && d_mask && d_out_q)), "NULL buffer");
+    CIS_REQUIRE(d_cnt && d_overflow && (nq == 0 || (d_q && d_mask && d_out_q && d_slot)), "NULL buffer");  // (nq = 0: [world][0] slots)
     hipStream_t st = (hipStream_t)stream;
     const int W = row_bytes / 4;
     CIS_CHECK_HIP(hipMemsetAsync(d_overflow, 0, sizeof(int32_t), st));
@@ -6100,7 +6100,7 @@ __global__ __launch_bounds__(1024) void k_exchange_offsets(const int32_t* __rest
 extern "C" int cis_exchange_offsets_dev(const int32_t* d_cnt_all, int world, int nq, int64_t stride, int64_t* d_off, int64_t* d_totals,
                                         int32_t* d_overflow, void* stream) {
     CIS_REQUIRE(world >= 1 && nq >= 0 && stride >= 0, "bad exchange arguments");
-    CIS_REQUIRE(d_cnt_all && d_off && d_totals && d_overflow, "NULL buffer");
+    CIS_REQUIRE(d_totals && d_overflow && (nq == 0 || (d_cnt_all && d_off)), "NULL buffer");  // (nq = 0: empty [world][0] arrays)
     CIS_TRY(cis_lazy_init());
     hipStream_t st = (hipStream_t)stream;
     CIS_CHECK_HIP(hipMemsetAsync(d_overflow, 0, sizeof(int32_t), st));
