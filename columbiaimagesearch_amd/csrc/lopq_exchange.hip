@@ -1,0 +1,489 @@
+// Cell-sharded search, the exchange between the ranks (columbiaimagesearch_amd/distributed.py): routing of the queries to the ranks
+// that own the cells they visit, packing of a rank's partial hit lists, offsets of the packed exchange, the merges of the shards'
+// lists, and the exact re-ranking with resident features.  The batch search itself is lopq_search.hip.
+#include "lopq_index.h"
+#include "scan_common.h"
+
+// Routing tables of a home rank: slot[d][i] = the row of query i in the buffer that goes to rank d (-1: not sent), in query order;
+// cnt[d] = rows used (at most cap; *overflow = 1 when a destination would need more).  One workgroup per destination.
+__global__ __launch_bounds__(1024) void k_route_slots(const unsigned long long* __restrict__ mask, int nq, int cap, int32_t* __restrict__ slot,
+                                                      int32_t* __restrict__ cnt, int32_t* __restrict__ overflow) {
+    __shared__ int s_w[16];
+    __shared__ int s_base;
+    const int d = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (tid == 0) s_base = 0;
+    __syncthreads();
+    for (int i0 = 0; i0 < nq; i0 += 1024) {
+        const int i = i0 + tid;
+        const bool f = i < nq && ((mask[i] >> d) & 1ull);
+        const unsigned long long b = __builtin_amdgcn_ballot_w64(f);
+        const int before = __builtin_popcountll(b & ((1ull << lane) - 1ull));
+        if (lane == 0) s_w[wv] = __builtin_popcountll(b);
+        __syncthreads();
+        int wbase = s_base;
+        for (int w = 0; w < wv; ++w) wbase += s_w[w];
+        if (i < nq) {
+            const int pos = wbase + before;
+            slot[(int64_t)d * nq + i] = (f && pos < cap) ? pos : -1;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            int tot = s_base;
+            for (int w = 0; w < 16; ++w) tot += s_w[w];
+            s_base = tot;
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        cnt[d] = s_base < cap ? s_base : cap;
+        if (s_base > cap) atomicExch(overflow, 1);
+    }
+}
+
+__global__ void k_route_rows(const uint32_t* __restrict__ q, int nq, int W /* 32-bit words per row */, const int32_t* __restrict__ slot, int cap,
+                             uint32_t* __restrict__ out) {
+    const int i = blockIdx.x, d = blockIdx.y;
+    const int sl = slot[(int64_t)d * nq + i];
+    if (sl < 0) return;
+    const uint32_t* src = q + (int64_t)i * W;
+    uint32_t* dst = out + ((int64_t)d * cap + sl) * W;
+    for (int k = threadIdx.x; k < W; k += blockDim.x) dst[k] = src[k];
+}
+
+extern "C" int cis_route_queries_dev(const void* d_q, int nq, int row_bytes, const uint64_t* d_mask, int world, int cap, void* d_out_q,
+                                     int32_t* d_slot, int32_t* d_cnt, int32_t* d_overflow, void* stream) {
+    CIS_REQUIRE(nq >= 0 && row_bytes > 0 && row_bytes % 4 == 0 && world >= 1 && world <= 64 && cap >= 1, "route: sizes out of range");
+    CIS_REQUIRE(d_cnt && d_overflow && (nq == 0 || (d_q && d_mask && d_out_q && d_slot)), "NULL buffer");  // (nq = 0: [world][0] slots)
+    hipStream_t st = (hipStream_t)stream;
+    const int W = row_bytes / 4;
+    CIS_CHECK_HIP(hipMemsetAsync(d_overflow, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(k_route_slots, dim3(world), dim3(1024), 0, st, (const unsigned long long*)d_mask, nq, cap, d_slot, d_cnt, d_overflow);
+    if (nq > 0) hipLaunchKernelGGL(k_route_rows, dim3(nq, world), dim3(W >= 256 ? 256 : 64), 0, st, (const uint32_t*)d_q, nq, W, d_slot, cap, (uint32_t*)d_out_q);
+    CIS_CHECK_HIP(hipGetLastError());
+    return CIS_OK;
+}
+
+// Merge tables of the routed search's return trip: the list of home query i from rank d is row base[d] + slot[d][i] of the returned
+// buffer (L records per row, ranked, valid hits first).  off = the row's first record, cnt = its valid hits (0: rank d was not asked).
+struct RouteBase { int64_t v[64]; };
+__global__ void k_routed_tables(const int32_t* __restrict__ slot, int world, int nq, RouteBase base, const cis_hit* __restrict__ hits, int L,
+                                int64_t* __restrict__ off, int32_t* __restrict__ cnt) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (int64_t)world * nq) return;
+    const int d = (int)(t / nq);
+    const int sl = slot[t];
+    if (sl < 0) { off[t] = 0; cnt[t] = 0; return; }
+    const int64_t row = base.v[d] + sl;
+    const cis_hit* h = hits + row * L;
+    int lo = 0, hi = L;  // first empty slot (id < 0): the valid hits are a prefix
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (h[mid].id >= 0) lo = mid + 1; else hi = mid;
+    }
+    off[t] = row * L;
+    cnt[t] = lo;
+}
+
+extern "C" int cis_routed_merge_tables_dev(const int32_t* d_slot, int world, int nq, const int64_t* h_base, const cis_hit* d_hits, int L,
+                                           int64_t* d_off, int32_t* d_cnt, void* stream) {
+    CIS_REQUIRE(world >= 1 && world <= 64 && nq >= 0 && L >= 0, "routed merge tables: sizes out of range");
+    CIS_REQUIRE(nq == 0 || (d_slot && h_base && d_off && d_cnt && (L == 0 || d_hits)), "NULL buffer");
+    if (nq == 0) return CIS_OK;
+    RouteBase b;
+    for (int d = 0; d < 64; ++d) b.v[d] = d < world ? h_base[d] : 0;
+    const int64_t n = (int64_t)world * nq;
+    hipLaunchKernelGGL(k_routed_tables, dim3((unsigned)ceil_div(n, (int64_t)256)), dim3(256), 0, (hipStream_t)stream, d_slot, world, nq, b, d_hits, L, d_off, d_cnt);
+    CIS_CHECK_HIP(hipGetLastError());
+    return CIS_OK;
+}
+
+// exclusive scan of the per-query hit counts (single block) and the packing of the valid row prefixes
+__global__ __launch_bounds__(1024) void k_pack_scan(const int32_t* __restrict__ cnt, int nq, int64_t* __restrict__ off,
+                                                    int64_t* __restrict__ total) {
+    __shared__ int64_t s_w[16];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    int64_t run = 0;  // all queries before this block-sized chunk
+    for (int base = 0; base < nq; base += 1024) {
+        const int q = base + tid;
+        const int64_t c = q < nq ? cnt[q] : 0;
+        int64_t x = c;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int64_t y = __shfl_up(x, d);
+            if (lane >= d) x += y;
+        }
+        if (lane == 63) s_w[wv] = x;
+        __syncthreads();
+        int64_t wp = 0, all = 0;
+        for (int k = 0; k < 16; ++k) { const int64_t y = s_w[k]; if (k < wv) wp += y; all += y; }
+        if (q < nq) off[q] = run + wp + x - c;
+        run += all;
+        __syncthreads();
+    }
+    if (tid == 0) *total = run;
+}
+
+__global__ void k_pack_hits(const cis_hit* __restrict__ dense /* [nq][L] */, const int32_t* __restrict__ cnt,
+                            const int64_t* __restrict__ off, int nq, int L, cis_hit* __restrict__ packed) {
+    const int q = blockIdx.x;
+    const int c = cnt[q];
+    const int64_t o = off[q];
+    for (int x = threadIdx.x; x < c; x += blockDim.x) packed[o + x] = dense[(int64_t)q * L + x];
+}
+
+extern "C" int cis_index_search_partial_packed_dev(cis_index* ix, const void* dQ, int q_dtype, int nq, int64_t quota, int limit,
+                                                   cis_hit* d_packed, int32_t* d_cnt, int64_t* d_off, int64_t* d_total,
+                                                   int32_t* d_visited, void* stream) {
+    int L;
+    CIS_TRY(effective_limit(quota, limit, &L));
+    CIS_REQUIRE(ix != nullptr && d_cnt && d_off && d_total && (L == 0 || d_packed), "NULL buffer");
+    hipStream_t st = (hipStream_t)stream;
+    if (nq == 0 || L == 0) {
+        CIS_CHECK_HIP(hipMemsetAsync(d_total, 0, sizeof(int64_t), st));
+        if (nq > 0) {
+            CIS_CHECK_HIP(hipMemsetAsync(d_cnt, 0, (size_t)nq * sizeof(int32_t), st));
+            CIS_CHECK_HIP(hipMemsetAsync(d_off, 0, (size_t)nq * sizeof(int64_t), st));
+        }
+        if (nq == 0) return CIS_OK;
+    }
+    CIS_CHECK_HIP(hipSetDevice(ix->m->device));
+    CIS_TRY(ix->w_part.reserve((size_t)nq * (L > 0 ? L : 1) * sizeof(cis_hit)));
+    CIS_TRY(cis_search_partial(ix, dQ, q_dtype, nq, quota, L, ix->w_part.as<cis_hit>(), d_cnt, d_visited, st));
+    if (L == 0) return CIS_OK;
+    hipLaunchKernelGGL(k_pack_scan, dim3(1), dim3(1024), 0, st, d_cnt, nq, d_off, d_total);
+    hipLaunchKernelGGL(k_pack_hits, dim3(nq), dim3(64), 0, st, ix->w_part.as<cis_hit>(), d_cnt, d_off, nq, L, d_packed);
+    CIS_CHECK_HIP(hipGetLastError());
+    return CIS_OK;
+}
+
+template <int CAPM>
+__global__ __launch_bounds__(256) void k_merge_parts(const cis_hit* __restrict__ parts /* [world][nq][limit] */, int world,
+                                                     int nq, int limit, int64_t* __restrict__ out_ids,
+                                                     double* __restrict__ out_dists, int* __restrict__ out_n,
+                                                     int32_t* __restrict__ out_cells, uint32_t* __restrict__ out_pos) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    uint64_t* ka = reinterpret_cast<uint64_t*>(smem);
+    uint64_t* kb = ka + CAPM;
+    int64_t* pay = reinterpret_cast<int64_t*>(kb + CAPM);
+    int* s_n = reinterpret_cast<int*>(pay + CAPM);
+    const int q = blockIdx.x;
+    // list w of query q starts at parts + (w*nq + q)*limit: first_list = q, distance between lists = nq*limit
+    merge_lists<CAPM>(parts + (int64_t)q * limit, nullptr, 0, world, (int64_t)nq * limit, limit, limit, ka, kb, pay,
+                      s_n, nullptr, out_ids + (int64_t)q * limit, out_dists + (int64_t)q * limit, out_n + q,
+                      out_cells ? out_cells + (int64_t)q * limit : nullptr, out_pos ? out_pos + (int64_t)q * limit : nullptr);
+}
+
+static int merge_parts(const cis_hit* d_parts, int world, int nq, int L, int64_t* d_ids, double* d_dists,
+                       int32_t* d_nf, int32_t* d_cells, uint32_t* d_pos, hipStream_t st) {
+    if (nq == 0 || L == 0) return CIS_OK;
+    if (L <= 512)
+        hipLaunchKernelGGL(k_merge_parts<1024>, dim3(nq), dim3(256), (size_t)1024 * 24 + 16, st, d_parts, world, nq, L, d_ids, d_dists, d_nf, d_cells, d_pos);
+    else if (L <= 1024)
+        hipLaunchKernelGGL(k_merge_parts<2048>, dim3(nq), dim3(256), (size_t)2048 * 24 + 16, st, d_parts, world, nq, L, d_ids, d_dists, d_nf, d_cells, d_pos);
+    else
+        hipLaunchKernelGGL(k_merge_parts<4096>, dim3(nq), dim3(256), (size_t)4096 * 24 + 16, st, d_parts, world, nq, L, d_ids, d_dists, d_nf, d_cells, d_pos);
+    CIS_CHECK_HIP(hipGetLastError());
+    return CIS_OK;
+}
+
+// Records of shard w for query q that really ARRIVED: with the fixed-size exchange a shard that held more than `stride` records was
+// cut there (the overflow flag tells the caller to repeat the exchange); the merge must not read past the cut.
+static __device__ __forceinline__ int arrived(const int32_t* __restrict__ cnt, const int64_t* __restrict__ off, int64_t stride, int w, int nq, int q) {
+    const int64_t o = off[(int64_t)w * nq + q];
+    const int64_t room = stride - o;
+    const int c = cnt[(int64_t)w * nq + q];
+    if (stride == 0) return c;  // one flat buffer, absolute offsets, nothing was cut (the routed search's return trip)
+    return room <= 0 ? 0 : (c < room ? c : (int)room);
+}
+
+// Merge of PACKED per-shard hit lists: shard w contributed parts[w*stride + off[w*nq+q] .. + cnt[w*nq+q]) for query q
+// (its valid hits only, in query order).  One wave per query; same ranking key as everywhere: (dist, visit_rank, pos).
+template <int CAPM, int WPB /* waves (= queries) per workgroup */>
+__global__ __launch_bounds__(WPB * 64) void k_merge_packed(const cis_hit* __restrict__ parts, int world, int64_t stride,
+                                                      const int64_t* __restrict__ off, const int32_t* __restrict__ cnt, int nq,
+                                                      int limit, int64_t* __restrict__ out_ids, double* __restrict__ out_dists,
+                                                      int* __restrict__ out_n, int32_t* __restrict__ out_cells,
+                                                      uint32_t* __restrict__ out_pos) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x & 63, wq = threadIdx.x >> 6;
+    const int q = blockIdx.x * WPB + wq;
+    if (q >= nq) return;
+    uint64_t* ka = reinterpret_cast<uint64_t*>(smem) + (size_t)wq * 3 * CAPM;
+    uint64_t* kb = ka + CAPM;
+    uint64_t* pay = kb + CAPM;  // index of the hit in parts
+    // A query whose hits all come from ONE shard (the rule with few coarse clusters: a V = 16 query visits one or two cells, and a
+    // cell lives on one shard): that list arrives ranked, so it is copied -- no LDS, no sort.  The merge then costs what the number
+    // of non-empty lists costs, not what the number of shards does.
+    {
+        int nonempty = 0, lone = 0, lone_n = 0;
+        for (int w = 0; w < world; ++w) {
+            const int v = arrived(cnt, off, stride, w, nq, q);
+            if (v > 0) { ++nonempty; lone = w; lone_n = v; }
+        }
+        if (nonempty <= 1) {
+            const int nv1 = lone_n < limit ? lone_n : limit;
+            const int64_t base = nonempty ? (int64_t)lone * stride + off[(int64_t)lone * nq + q] : 0;
+            const int64_t o1 = (int64_t)q * limit;
+            for (int x = lane; x < limit; x += 64) {
+                int64_t id = -1;
+                double dist = __longlong_as_double(0x7ff8000000000000LL);
+                int32_t cell = -1;
+                uint32_t pos = 0xffffffffu;
+                if (x < nv1) {
+                    const cis_hit hh = parts[base + x];
+                    id = hh.id; dist = hh.dist; cell = hh.cell; pos = hh.pos;
+                }
+                out_ids[o1 + x] = id;
+                out_dists[o1 + x] = dist;
+                if (out_cells) out_cells[o1 + x] = cell;
+                if (out_pos) out_pos[o1 + x] = pos;
+            }
+            if (lane == 0 && out_n) out_n[q] = nv1;
+            return;
+        }
+    }
+    int have = 0, l = 0, e = 0, total = 0;
+    while (true) {
+        int n = have;
+        int room = CAPM - have;
+        while (l < world && room > 0) {
+            const int valid = arrived(cnt, off, stride, l, nq, q);
+            const int take = (valid - e < room) ? (valid - e) : room;
+            const int64_t base = (int64_t)l * stride + off[(int64_t)l * nq + q] + e;
+            for (int x = lane; x < take; x += 64) {
+                const cis_hit hh = parts[base + x];
+                ka[n + x] = (uint64_t)__double_as_longlong(hh.dist);
+                kb[n + x] = ((uint64_t)hh.visit_rank << 32) | hh.pos;
+                pay[n + x] = (uint64_t)(base + x);
+            }
+            n += take; total += take; room -= take; e += take;
+            if (e >= valid) { ++l; e = 0; }
+        }
+        int ns = 64;
+        while (ns < n) ns <<= 1;
+        for (int x = n + lane; x < ns; x += 64) { ka[x] = ~0ull; kb[x] = ~0ull; pay[x] = ~0ull; }
+        wave_lds_sync();
+        // bitonic sort with payload
+        for (int k = 2; k <= ns; k <<= 1) {
+            for (int j = k >> 1; j > 0; j >>= 1) {
+                for (int t = lane; t < (ns >> 1); t += 64) {
+                    const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+                    const int p = i + j;
+                    const bool asc = ((i & k) == 0);
+                    const uint64_t a0 = ka[i], b0 = kb[i], a1 = ka[p], b1 = kb[p];
+                    const bool gt = (a0 > a1) || (a0 == a1 && b0 > b1);
+                    if (gt == asc) {
+                        ka[i] = a1; kb[i] = b1; ka[p] = a0; kb[p] = b0;
+                        const uint64_t y = pay[i]; pay[i] = pay[p]; pay[p] = y;
+                    }
+                }
+                wave_lds_sync();
+            }
+        }
+        have = n < limit ? n : limit;
+        if (l >= world) break;
+    }
+    const int nv = total < limit ? total : limit;
+    const int64_t o = (int64_t)q * limit;
+    for (int x = lane; x < limit; x += 64) {
+        int64_t id = -1;
+        double dist = __longlong_as_double(0x7ff8000000000000LL);
+        int32_t cell = -1;
+        uint32_t pos = 0xffffffffu;
+        if (x < nv) {
+            const cis_hit hh = parts[pay[x]];
+            id = hh.id; dist = hh.dist; cell = hh.cell; pos = hh.pos;
+        }
+        out_ids[o + x] = id;
+        out_dists[o + x] = dist;
+        if (out_cells) out_cells[o + x] = cell;
+        if (out_pos) out_pos[o + x] = pos;
+    }
+    if (lane == 0 && out_n) out_n[q] = nv;
+}
+
+// Any limit (above the 3072 records a wave ranks in LDS): every shard's list arrives ranked by (dist, visit_rank, pos), and the
+// keys of different shards never tie (a cell lives on one shard), so a record's place in the merged ranking is its index in its
+// own list plus, for every other list, the number of records with a smaller key -- binary searches, no sort.  One workgroup per
+// query; records past `limit` are dropped, unused slots padded like every other route (-1 / NaN).
+__global__ __launch_bounds__(256) void k_merge_packed_ranked(const cis_hit* __restrict__ parts, int world, int64_t stride,
+                                                             const int64_t* __restrict__ off, const int32_t* __restrict__ cnt, int nq, int limit,
+                                                             int64_t* __restrict__ out_ids, double* __restrict__ out_dists, int32_t* __restrict__ out_n,
+                                                             int32_t* __restrict__ out_cells, uint32_t* __restrict__ out_pos) {
+    const int q = blockIdx.x;
+    __shared__ int s_tot;
+    if (threadIdx.x == 0) {
+        int t = 0;
+        for (int w = 0; w < world; ++w) t += arrived(cnt, off, stride, w, nq, q);
+        s_tot = t;
+    }
+    __syncthreads();
+    const int total = s_tot;
+    const int64_t o = (int64_t)q * limit;
+    auto less = [](const cis_hit& a, const cis_hit& b) -> bool {
+        const uint64_t da = (uint64_t)__double_as_longlong(a.dist), db = (uint64_t)__double_as_longlong(b.dist);
+        if (da != db) return da < db;  // non-negative doubles order like their bit patterns
+        if (a.visit_rank != b.visit_rank) return a.visit_rank < b.visit_rank;
+        return a.pos < b.pos;
+    };
+    for (int w = 0; w < world; ++w) {
+        const cis_hit* lst = parts + (int64_t)w * stride + off[(int64_t)w * nq + q];
+        const int n = arrived(cnt, off, stride, w, nq, q);
+        for (int a = threadIdx.x; a < n; a += blockDim.x) {
+            const cis_hit e = lst[a];
+            int64_t rank = a;
+            for (int w2 = 0; w2 < world && rank < limit; ++w2) {
+                if (w2 == w) continue;
+                const cis_hit* l2 = parts + (int64_t)w2 * stride + off[(int64_t)w2 * nq + q];
+                int lo = 0, hi = arrived(cnt, off, stride, w2, nq, q);
+                while (lo < hi) {  // records of list w2 with a smaller key
+                    const int mid = (lo + hi) >> 1;
+                    if (less(l2[mid], e)) lo = mid + 1;
+                    else hi = mid;
+                }
+                rank += lo;
+            }
+            if (rank < limit) {
+                out_ids[o + rank] = e.id;
+                out_dists[o + rank] = e.dist;
+                if (out_cells) out_cells[o + rank] = e.cell;
+                if (out_pos) out_pos[o + rank] = e.pos;
+            }
+        }
+    }
+    const int nv = total < limit ? total : limit;
+    for (int x = nv + threadIdx.x; x < limit; x += blockDim.x) {
+        out_ids[o + x] = -1;
+        out_dists[o + x] = __longlong_as_double(0x7ff8000000000000LL);
+        if (out_cells) out_cells[o + x] = -1;
+        if (out_pos) out_pos[o + x] = 0xffffffffu;
+    }
+    if (threadIdx.x == 0 && out_n) out_n[q] = nv;
+}
+
+// Offsets of the packed exchange on the device: cnt_all [world][nq] (what the counts all-gather delivered) -> off [world][nq] =
+// exclusive scan of a shard's counts over the queries, totals[w], and *overflow = 1 when a shard holds more records than the fixed
+// stride of the payload all-gather (the caller then repeats the exchange with the exact stride).  Replaces a torch.cumsum + a host
+// read per batch (round 3).  One workgroup per shard.
+__global__ __launch_bounds__(1024) void k_exchange_offsets(const int32_t* __restrict__ cnt_all, int nq, int64_t stride, int64_t* __restrict__ off,
+                                                           int64_t* __restrict__ totals, int32_t* __restrict__ overflow) {
+    __shared__ int64_t s_w[16];
+    __shared__ int64_t s_run;
+    const int w = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int32_t* c = cnt_all + (int64_t)w * nq;
+    int64_t* o = off + (int64_t)w * nq;
+    if (tid == 0) s_run = 0;
+    __syncthreads();
+    for (int q0 = 0; q0 < nq; q0 += 1024) {
+        const int q = q0 + tid;
+        const int64_t v = q < nq ? (int64_t)c[q] : 0;
+        int64_t x = v;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int64_t y = __shfl_up(x, d);
+            if (lane >= d) x += y;
+        }
+        if (lane == 63) s_w[wv] = x;
+        __syncthreads();
+        int64_t base = s_run;
+        for (int k = 0; k < wv; ++k) base += s_w[k];
+        if (q < nq) o[q] = base + x - v;
+        __syncthreads();
+        if (tid == 1023) s_run = base + x;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        totals[w] = s_run;
+        if (s_run > stride) atomicExch(overflow, 1);
+    }
+}
+
+extern "C" int cis_exchange_offsets_dev(const int32_t* d_cnt_all, int world, int nq, int64_t stride, int64_t* d_off, int64_t* d_totals,
+                                        int32_t* d_overflow, void* stream) {
+    CIS_REQUIRE(world >= 1 && nq >= 0 && stride >= 0, "bad exchange arguments");
+    CIS_REQUIRE(d_totals && d_overflow && (nq == 0 || (d_cnt_all && d_off)), "NULL buffer");  // (nq = 0: empty [world][0] arrays)
+    CIS_TRY(cis_lazy_init());
+    hipStream_t st = (hipStream_t)stream;
+    CIS_CHECK_HIP(hipMemsetAsync(d_overflow, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(k_exchange_offsets, dim3((unsigned)world), dim3(1024), 0, st, d_cnt_all, nq, stride, d_off, d_totals, d_overflow);
+    CIS_CHECK_HIP(hipGetLastError());
+    return CIS_OK;
+}
+
+extern "C" int cis_merge_packed_dev(const cis_hit* d_parts, int world, int64_t stride, const int64_t* d_off,
+                                    const int32_t* d_cnt, int nq, int limit, int64_t* d_ids, double* d_dists,
+                                    int32_t* d_n_found, int32_t* d_cells, uint32_t* d_pos, void* stream) {
+    CIS_REQUIRE(world >= 1 && nq >= 0 && limit >= 0 && limit <= MAX_LIMIT && stride >= 0, "bad merge arguments");
+    CIS_REQUIRE(nq == 0 || limit == 0 || (d_parts && d_off && d_cnt && d_ids && d_dists), "NULL buffer");
+    CIS_TRY(cis_lazy_init());
+    if (nq == 0 || limit == 0) return CIS_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 g((unsigned)ceil_div(nq, 4));
+    if (limit <= 128)
+        hipLaunchKernelGGL((k_merge_packed<256, 4>), g, dim3(256), (size_t)4 * 3 * 256 * 8, st, d_parts, world, stride, d_off, d_cnt, nq, limit,
+                           d_ids, d_dists, d_n_found, d_cells, d_pos);
+    else if (limit <= 512)
+        hipLaunchKernelGGL((k_merge_packed<1024, 4>), g, dim3(256), (size_t)4 * 3 * 1024 * 8, st, d_parts, world, stride, d_off, d_cnt, nq,
+                           limit, d_ids, d_dists, d_n_found, d_cells, d_pos);
+    else if (limit <= 3072)  // one wave per workgroup with 96 KB of LDS: 4096 keys per round, `limit` of them carried over
+        hipLaunchKernelGGL((k_merge_packed<4096, 1>), dim3((unsigned)nq), dim3(64), (size_t)3 * 4096 * 8, st, d_parts, world, stride, d_off,
+                           d_cnt, nq, limit, d_ids, d_dists, d_n_found, d_cells, d_pos);
+    else  // any limit: places by binary search in the other shards' ranked lists
+        hipLaunchKernelGGL(k_merge_packed_ranked, dim3((unsigned)nq), dim3(256), 0, st, d_parts, world, stride, d_off, d_cnt, nq, limit,
+                           d_ids, d_dists, d_n_found, d_cells, d_pos);
+    CIS_CHECK_HIP(hipGetLastError());
+    return CIS_OK;
+}
+
+// ---- exact re-ranking with resident features (searcher_lopqhbase.py:864-912): true L2 distance of a query to the
+// original features of its first `L` results.  One wave per (query, result); arithmetic in the feature dtype like
+// np.linalg.norm(normed_feat - res_fts[pos]) (float32 features -> float32 distance), returned as float64.
+template <typename T>
+__global__ __launch_bounds__(256) void k_rerank(const T* __restrict__ feats, int64_t n_feats, int D, const T* __restrict__ Q,
+                                                const int64_t* __restrict__ rows, int64_t n_pairs, int L,
+                                                double* __restrict__ dists) {
+    const int lane = threadIdx.x & 63;
+    const int64_t pair = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (pair >= n_pairs) return;
+    const int64_t r = rows[pair];
+    if (r < 0 || r >= n_feats) {  // feature not resident: the caller keeps the ADC distance (reference :889-893)
+        if (lane == 0) dists[pair] = __longlong_as_double(0x7ff8000000000000LL);
+        return;
+    }
+    const T* x = feats + r * D;
+    const T* q = Q + (pair / L) * D;
+    T acc = (T)0;
+    for (int i = lane; i < D; i += 64) {
+        const T df = q[i] - x[i];
+        acc = fma(df, df, acc);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc = acc + __shfl_xor(acc, o);
+    if (lane == 0) dists[pair] = (double)(T)sqrt(acc);
+}
+
+extern "C" int cis_rerank_dev(const void* d_feats, int f_dtype, int64_t n_feats, int D, const void* d_q, int nq,
+                              const int64_t* d_rows, int L, double* d_dists, void* stream) {
+    CIS_REQUIRE(f_dtype == CIS_F32 || f_dtype == CIS_F64, "f_dtype must be 4 or 8");
+    CIS_REQUIRE(n_feats >= 0 && D > 0 && nq >= 0 && L >= 0, "bad re-ranking arguments");
+    if (nq == 0 || L == 0) return CIS_OK;
+    CIS_REQUIRE(d_feats && d_q && d_rows && d_dists, "NULL buffer");
+    CIS_TRY(cis_lazy_init());
+    const int64_t n_pairs = (int64_t)nq * L;
+    const dim3 g((unsigned)ceil_div(n_pairs, 4));
+    hipStream_t st = (hipStream_t)stream;
+    if (f_dtype == CIS_F32)
+        hipLaunchKernelGGL(k_rerank<float>, g, dim3(256), 0, st, (const float*)d_feats, n_feats, D, (const float*)d_q, d_rows, n_pairs, L, d_dists);
+    else
+        hipLaunchKernelGGL(k_rerank<double>, g, dim3(256), 0, st, (const double*)d_feats, n_feats, D, (const double*)d_q, d_rows, n_pairs, L, d_dists);
+    CIS_CHECK_HIP(hipGetLastError());
+    return CIS_OK;
+}
+
+extern "C" int cis_merge_hits_dev(const cis_hit* d_parts, int world, int nq, int limit, int64_t* d_ids,
+                                  double* d_dists, int32_t* d_n_found, int32_t* d_cells, uint32_t* d_pos,
+                                  void* stream) {
+    CIS_REQUIRE(world >= 1 && nq >= 0 && limit >= 0 && limit <= MAX_LDS_LIMIT, "bad merge arguments (limit <= 3072)");
+    CIS_TRY(cis_lazy_init());
+    return merge_parts(d_parts, world, nq, limit, d_ids, d_dists, d_n_found, d_cells, d_pos, (hipStream_t)stream);
+}

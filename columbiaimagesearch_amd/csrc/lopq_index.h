@@ -1,5 +1,5 @@
-// Internal view of the LOPQ index handle, shared by lopq_index.hip (storage: device-side insert) and lopq_search.hip
-// (search pipeline).
+// Internal view of the LOPQ index handle, shared by lopq_index.hip (storage: device-side insert), lopq_search.hip
+// (search pipeline), lopq_exchange.hip (cell-sharded exchange) and lopq_host.hip (host-pointer entry points).
 //
 // The index lives in HBM and only there.  Inserts -- from host arrays (cis_index_add) or from device arrays
 // (cis_index_add_dev) -- are merged into the cell-contiguous arrays by kernels (lopq_index.hip); the host keeps no copy
@@ -89,7 +89,7 @@ struct cis_index {
     hipStream_t h_stream = nullptr; // the host-pointer entry points' own stream (cis_index_search[_async])
     hipEvent_t h_ev_in = nullptr, h_ev_out = nullptr, h_ev_done = nullptr;  // copy-in landed / search done / copy-out landed
     bool h_pending = false;         // a batch of cis_index_search_async is in flight on it
-    bool h_out_enqueued = false;    // ... and its copy-out is on the copy stream already (cis_host_pump_locked: lopq_search.hip)
+    bool h_out_enqueued = false;    // ... and its copy-out is on the copy stream already (host_pump_locked: lopq_host.hip)
     struct HostOut { int64_t* ids; double* dists; int32_t* n_found; int32_t* visited; int32_t* cells; uint32_t* pos; int nq, L; };
     HostOut h_out = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};  // where its results go (copied out by cis_index_search_wait)
     bool force_scan5 = false;       // scan mode 7 (tests): k_adc_scan5 (one threshold per query, eight queries per slot) whatever the batch size
@@ -119,5 +119,24 @@ struct cis_index {
 // Makes the device arrays exist (empty index: offsets all zero) -- called at the head of every search.
 int cis_index_ready(cis_index* ix);
 
-// lopq_search.hip: a handle that is being destroyed leaves the list of handles whose copy-out is still to be enqueued
+// lopq_host.hip: a handle that is being destroyed leaves the list of handles whose copy-out is still to be enqueued
 void cis_host_forget(cis_index* ix);
+
+static const int MAX_LDS_LIMIT = 3072;  // ranked results per query the LDS top-k kernels hold
+static const int MAX_LIMIT = 1 << 24;  // with the sorted path: bounded by the workspace only
+
+static inline int effective_limit(int64_t quota, int limit, int* L) {
+    int64_t l = limit < 0 ? quota : limit;  // search.py:213-214
+    if (l < 0) l = 0;
+    if (l > MAX_LIMIT) {
+        cis_set_error("limit=%lld exceeds the %d ranked results per query supported by this build", (long long)l, MAX_LIMIT);
+        return CIS_EUNSUPPORTED;
+    }
+    *L = (int)l;
+    return CIS_OK;
+}
+
+// lopq_search.hip: the batch search for the entry point that packs its hits (lopq_exchange.hip) -- ranked partial hits [nq][L] of
+// this shard, their counts [nq] and visited [nq] (either may be null); L from effective_limit
+int cis_search_partial(cis_index* ix, const void* dQ, int q_dtype, int nq, int64_t quota, int L, cis_hit* d_hits, int32_t* d_n_found,
+                       int32_t* d_visited, hipStream_t st);

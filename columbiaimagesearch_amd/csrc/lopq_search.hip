@@ -17,8 +17,6 @@
 //   top-k -> per-query merge -> ids/dists.
 #include <atomic>
 #include <chrono>
-#include <mutex>
-#include <algorithm>
 
 #include "lopq_index.h"
 #include "scan_common.h"
@@ -1559,28 +1557,6 @@ __device__ __forceinline__ void block_bitonic(uint64_t* ka, uint64_t* kb, int64_
     }
 }
 
-// same network with the size chosen at run time (N a power of two): the merge sorts only as many
-// slots as it actually filled
-template <int NT, bool PAY>
-__device__ __forceinline__ void block_bitonic_rt(uint64_t* ka, uint64_t* kb, int64_t* pay, int N) {
-    for (int k = 2; k <= N; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = threadIdx.x; t < N / 2; t += NT) {
-                const int i = ((t / j) * 2 * j) + (t % j);
-                const int p = i + j;
-                const bool asc = ((i & k) == 0);
-                const uint64_t a0 = ka[i], b0 = kb[i], a1 = ka[p], b1 = kb[p];
-                const bool gt = (a0 > a1) || (a0 == a1 && b0 > b1);
-                if (gt == asc) {
-                    ka[i] = a1; kb[i] = b1; ka[p] = a0; kb[p] = b0;
-                    if (PAY) { const int64_t x = pay[i]; pay[i] = pay[p]; pay[p] = x; }
-                }
-            }
-            __syncthreads();
-        }
-    }
-}
-
 // k_rank for wide coarse vocabularies (production configs go up to V = 4096): the rank by counting above is O(V^2)
 // per (query, split); here the (distance bits, centroid index) pairs are sorted in LDS -- the index as second key
 // reproduces "first minimum wins" among equal distances.
@@ -2739,77 +2715,6 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NR == 1
     }
 }
 
-// ================================================================================================
-// kernel: per-query merge of ranked lists -> top `limit` by (dist, visit_rank, pos)
-// ================================================================================================
-// Lists of query q: entries src[lo .. hi) in groups: list l has `stride` slots of which cnt[l]
-// are valid (cnt == nullptr: a slot is valid when id >= 0).  Used twice: (a) merging the work
-// items of a query, (b) merging the per-shard partial results after the all-gather.
-template <int CAPM>
-__device__ void merge_lists(const cis_hit* __restrict__ src, const int* __restrict__ cnt, int64_t first_list,
-                            int n_lists, int64_t list_stride /* distance between lists, in hits */,
-                            int slots, int limit, uint64_t* ka, uint64_t* kb, int64_t* pay, int* s_n,
-                            cis_hit* __restrict__ out_hits /* [limit] or null */, int64_t* __restrict__ out_ids,
-                            double* __restrict__ out_dists, int* __restrict__ out_n, int32_t* __restrict__ out_cells,
-                            uint32_t* __restrict__ out_pos) {
-    const int tid = threadIdx.x;
-    int have = 0;      // sorted survivors currently in [0, have)
-    int l = 0, e = 0;  // cursor: list l, entry e (uniform over the block)
-    // rounds: append up to CAPM - have entries, sort, keep `limit`.  pay = index of the hit in src.
-    while (true) {
-        int n = have;
-        int room = CAPM - have;
-        while (l < n_lists && room > 0) {
-            const int64_t lbase = (first_list + l) * list_stride;
-            const int valid = cnt ? cnt[first_list + l] : slots;
-            const int take = (valid - e < room) ? (valid - e) : room;
-            for (int x = tid; x < take; x += blockDim.x) {
-                const cis_hit hh = src[lbase + e + x];
-                const bool ok = hh.id >= 0;
-                ka[n + x] = ok ? (uint64_t)__double_as_longlong(hh.dist) : ~0ull;
-                kb[n + x] = ok ? (((uint64_t)hh.visit_rank << 32) | hh.pos) : ~0ull;
-                pay[n + x] = ok ? (lbase + e + x) : -1;
-            }
-            n += take;
-            room -= take;
-            e += take;
-            if (e >= valid) { ++l; e = 0; }
-        }
-        int ns = 64;  // sort only the next power of two above what was filled
-        while (ns < n) ns <<= 1;
-        for (int x = n + tid; x < ns; x += blockDim.x) { ka[x] = ~0ull; kb[x] = ~0ull; pay[x] = -1; }
-        __syncthreads();
-        block_bitonic_rt<256, true>(ka, kb, pay, ns);
-        have = n < limit ? n : limit;
-        if (l >= n_lists) break;
-    }
-    // empty slots (id < 0) carry all-ones keys and therefore sit behind every real hit
-    if (tid == 0) *s_n = 0;
-    __syncthreads();
-    int local = 0;
-    for (int x = tid; x < have; x += blockDim.x) local += (pay[x] >= 0) ? 1 : 0;
-    if (local) atomicAdd(s_n, local);
-    __syncthreads();
-    const int nv = *s_n;
-    for (int x = tid; x < limit; x += blockDim.x) {
-        cis_hit hh;
-        if (x < nv) {
-            hh = src[pay[x]];
-        } else {
-            hh.dist = __longlong_as_double(0x7ff0000000000000LL);
-            hh.visit_rank = 0xffffffffu; hh.pos = 0xffffffffu; hh.id = -1; hh.cell = -1; hh.reserved = 0;
-        }
-        if (out_hits) out_hits[x] = hh;
-        if (out_ids) {
-            out_ids[x] = hh.id;
-            out_dists[x] = (x < nv) ? hh.dist : __longlong_as_double(0x7ff8000000000000LL);
-        }
-        if (out_cells) out_cells[x] = hh.cell;
-        if (out_pos) out_pos[x] = hh.pos;
-    }
-    if (tid == 0 && out_n) *out_n = nv;
-}
-
 template <int CAPM>
 __global__ __launch_bounds__(256) void k_merge_items(const cis_hit* __restrict__ item_hits, const int* __restrict__ item_n,
                                                      const int64_t* __restrict__ item_off, int limit, int S,
@@ -2835,11 +2740,6 @@ __global__ __launch_bounds__(256) void k_merge_items(const cis_hit* __restrict__
 // workgroup barrier: a query is a chain of dependent global loads, so what counts is how many queries a CU has in
 // flight) re-scores them exactly -- the code from the index, float64 table entries summed left to right as
 // search.py:173, one candidate per lane -- and ranks them by (dist, visit_rank, pos) with a bitonic sort in LDS.
-static __device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // ascending bitonic sort of N (power of two >= 64) 128-bit keys (ka, kb) by one wave
 static __device__ __forceinline__ void wave_bitonic_lds(uint64_t* ka, uint64_t* kb, int N) {
@@ -3107,23 +3007,6 @@ void k_merge_survivors(const uint64_t* __restrict__ surv /* [n_items][S] */,
         if (out_pos) out_pos[o + x] = hh.pos;
     }
     if (lane == 0 && out_n) out_n[q] = nv;
-}
-
-template <int CAPM>
-__global__ __launch_bounds__(256) void k_merge_parts(const cis_hit* __restrict__ parts /* [world][nq][limit] */, int world,
-                                                     int nq, int limit, int64_t* __restrict__ out_ids,
-                                                     double* __restrict__ out_dists, int* __restrict__ out_n,
-                                                     int32_t* __restrict__ out_cells, uint32_t* __restrict__ out_pos) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    uint64_t* ka = reinterpret_cast<uint64_t*>(smem);
-    uint64_t* kb = ka + CAPM;
-    int64_t* pay = reinterpret_cast<int64_t*>(kb + CAPM);
-    int* s_n = reinterpret_cast<int*>(pay + CAPM);
-    const int q = blockIdx.x;
-    // list w of query q starts at parts + (w*nq + q)*limit: first_list = q, distance between lists = nq*limit
-    merge_lists<CAPM>(parts + (int64_t)q * limit, nullptr, 0, world, (int64_t)nq * limit, limit, limit, ka, kb, pay,
-                      s_n, nullptr, out_ids + (int64_t)q * limit, out_dists + (int64_t)q * limit, out_n + q,
-                      out_cells ? out_cells + (int64_t)q * limit : nullptr, out_pos ? out_pos + (int64_t)q * limit : nullptr);
 }
 
 __global__ void k_copy_visited(const PlanOut* __restrict__ plan, int nq, int32_t* __restrict__ visited) {
@@ -4126,8 +4009,6 @@ __global__ __launch_bounds__(NT) void k_select_topl(const uint64_t* __restrict__
     }
 }
 
-static const int MAX_LDS_LIMIT = 3072;  // ranked results per query the LDS top-k kernels hold
-static const int MAX_LIMIT = 1 << 24;  // with the sorted path: bounded by the workspace only
 
 // how the all-candidates path ranks: select (k_select_topl) when it shrinks the sort, LDS-ranked for limit <= 3072
 struct SelectPlan { bool select, sort_lds; int64_t stride; int p2; size_t lds; };
@@ -4762,56 +4643,137 @@ struct SearchOut {  // any of these may be null; all are [nq][L] except n_found 
     }
 };
 
-static int search_batch(cis_index* ix, const void* dQ, int q_dtype, int nq, int64_t quota, int L, const SearchOut& out,
-                        hipStream_t st) {
+// ---- front end: LOPQ-space queries, coarse type, the rank workspaces (the batch search and the owner walk of the routed search) ----
+struct Front {
+    const void* xc;  // the queries as the coarse quantizers read them
+    int ct;          // their type: CIS_F32 or CIS_F64
+    int* grp_cnt;    // [2V][GRP_SUB] tables per (split, cluster, query % GRP_SUB); the rank kernels leave the counters zeroed
+};
+
+static int front_prepare(cis_index* ix, const void* dQ, int q_dtype, int nq, hipStream_t st, Front* f) {
     cis_model* m = ix->m;
-    const int V = m->V, D = m->D, K = m->K, M = m->M, h = m->h, nf = m->nf;
-    const auto t_entry = std::chrono::steady_clock::now();
-    ix->last_scan_kernel = 0;
-    cis_index::ProfRec pr;
-    pr.has_scan = false;
-    for (int i = 0; i < 6; ++i) pr.ev[i] = nullptr;
-    auto mark = [&](int i) -> int {
-        if (!ix->profiling) return CIS_OK;
-        if (ix->profiling == 1 && i != 5 && i != 3) return CIS_OK;  // level 1: only the pair around the scan kernel
-        CIS_CHECK_HIP(hipEventCreate(&pr.ev[i]));
-        CIS_CHECK_HIP(hipEventRecord(pr.ev[i], st));
-        return CIS_OK;
-    };
-    CIS_TRY(mark(0));
+    const int V = m->V;
     // 1. LOPQ-space queries
     const void* xp = dQ;
     int xp_dtype = q_dtype;
     if (m->has_pca) {
-        CIS_TRY(ix->w_xp.reserve((size_t)nq * D * sizeof(float)));
+        CIS_TRY(ix->w_xp.reserve((size_t)nq * m->D * sizeof(float)));
         CIS_TRY(cis_dev_apply_pca(m, dQ, q_dtype, nq, ix->w_xp.as<float>(), st, &ix->w_y64));
         xp = ix->w_xp.p;
         xp_dtype = CIS_F32;
     }
-    const void* xc;
-    int ct;
-    CIS_TRY(cis_dev_coarse_type(m, xp, xp_dtype, nq, &xc, &ct, st, &ix->w_x64));
-    const size_t csz = (ct == CIS_F32) ? 4 : 8;
+    CIS_TRY(cis_dev_coarse_type(m, xp, xp_dtype, nq, &f->xc, &f->ct, st, &ix->w_x64));
+    const size_t csz = (f->ct == CIS_F32) ? 4 : 8;
     // 2. coarse distances, rank
     CIS_TRY(ix->w_cd.reserve((size_t)2 * nq * V * csz));
     CIS_TRY(ix->w_sorted.reserve((size_t)2 * nq * V * csz));
     CIS_TRY(ix->w_order.reserve((size_t)2 * nq * V * sizeof(uint16_t)));
-    CIS_TRY(ix->w_plan.reserve((size_t)nq * sizeof(PlanOut)));
-    CIS_TRY(ix->w_off.reserve((size_t)(2 * (nq + 1) + 4 + nq) * sizeof(int64_t)));
-    int64_t* item_off = ix->w_off.as<int64_t>();
-    int64_t* tab_off = item_off + (nq + 1);
-    int64_t* totals = tab_off + (nq + 1);
-    unsigned long long* qbound = reinterpret_cast<unsigned long long*>(totals + 4);  // per query: cross-cell bound of the scan
-    PlanOut* plan = ix->w_plan.as<PlanOut>();
-    {
-        const void* grp_before = ix->w_grp.p;
-        CIS_TRY(ix->w_grp.reserve((size_t)(GRP_WORDS(V) + 2 * GRP_TILES(V)) * sizeof(int)));
-        if (ix->w_grp.p != grp_before)  // fresh memory: the counters start clean (afterwards every k_plan_scan leaves them clean)
-            CIS_CHECK_HIP(hipMemsetAsync(ix->w_grp.p, 0, ix->w_grp.cap, st));
+    const void* grp_before = ix->w_grp.p;
+    CIS_TRY(ix->w_grp.reserve((size_t)(GRP_WORDS(V) + 2 * GRP_TILES(V)) * sizeof(int)));
+    if (ix->w_grp.p != grp_before)  // fresh memory: the counters start clean (afterwards every k_plan_scan leaves them clean)
+        CIS_CHECK_HIP(hipMemsetAsync(ix->w_grp.p, 0, ix->w_grp.cap, st));
+    f->grp_cnt = ix->w_grp.as<int>();
+    return CIS_OK;
+}
+
+static const float* coarse_centroids(const cis_model* m, float) { return m->d_Cs32; }
+static const double* coarse_centroids(const cis_model* m, double) { return m->d_Cs64; }
+
+// Rank of the coarse distances in w_cd -> w_order / w_sorted.  reg_sorts: the caller takes the register sorts (float32 distances
+// only: k_rank_sort_reg has no float64 form) where the vocabulary fits one; the owner walk keeps to k_rank_sort / k_rank.
+template <typename CT>
+static void launch_rank(cis_index* ix, int nq, bool reg_sorts, int* grp_cnt, hipStream_t st) {
+    const int V = ix->m->V;
+    int Vp2 = 64;
+    while (Vp2 < V) Vp2 <<= 1;
+    const CT* cd = ix->w_cd.as<CT>();
+    uint16_t* order = ix->w_order.as<uint16_t>();
+    CT* sorted = ix->w_sorted.as<CT>();
+    if constexpr (sizeof(CT) == 4) {
+        const bool sort_lds = getenv("CIS_RANK_SORT_LDS") != nullptr;  // the LDS form of the sort (A/B runs)
+        if (reg_sorts && V > 256 && !sort_lds && (Vp2 == 1024 || Vp2 == 2048 || Vp2 == 4096)) {
+            if (Vp2 == 1024) hipLaunchKernelGGL(k_rank_sort_reg<4>, dim3(nq, 2), dim3(256), 0, st, cd, nq, V, order, sorted, grp_cnt);
+            else if (Vp2 == 2048) hipLaunchKernelGGL(k_rank_sort_reg<8>, dim3(nq, 2), dim3(256), 0, st, cd, nq, V, order, sorted, grp_cnt);
+            else hipLaunchKernelGGL(k_rank_sort_reg<16>, dim3(nq, 2), dim3(256), 0, st, cd, nq, V, order, sorted, grp_cnt);
+            return;
+        }
     }
-    int* grp_cnt = ix->w_grp.as<int>();         // [2V][GRP_SUB] tables per (split, cluster, query % GRP_SUB)
-    int* grp_cur = grp_cnt + 2 * V * GRP_SUB;    // cursors
-    int* grp_base = grp_cnt + 4 * V * GRP_SUB;   // exclusive scan
+    if (V > 256 && Vp2 <= 4096)
+        hipLaunchKernelGGL(k_rank_sort<CT>, dim3(nq, 2), dim3(256), (size_t)Vp2 * 16, st, cd, nq, V, Vp2, order, sorted, grp_cnt);
+    else
+        hipLaunchKernelGGL(k_rank<CT>, dim3(nq, 2), dim3(V <= 64 ? 64 : 256), (size_t)V * 8, st, cd, nq, V, order, sorted, grp_cnt);
+}
+
+// ---- what a batch runs: every predicate once -----------------------------------------------------------------------------------
+struct Route {
+    // route_hints: before the plan (the chunk size is part of the plan)
+    bool w_pow2;        // sub-quantizers of 4, 8, 16 or 32 components
+    bool split_tables;  // ... and K <= 256: tables from the projected residuals (k_tables_from_px), exact keys from them (k_adc_direct)
+    bool big;           // ranked over all candidates' exact distances (use_all_path)
+    bool fast;          // the float32 / fixed-point prefilter scans serve this shape
+    bool tiny_cells;
+    bool use3;          // lopq_scan3.hip instead of k_adc_scan2
+    bool stream_hint;   // the HBM-streaming route, if the plan confirms it
+    bool par_plan, fused_front;
+    int seg_max;
+    int64_t stream_min;
+    Scan2Geom geom;
+    // route_decide: with the plan totals, or their bounds
+    bool direct;        // tiny cells on the all-candidates path: entries computed per candidate from px (k_adc_direct), no tables
+    bool stream;
+    bool use5;          // k_adc_scan5 where the sampled form k_adc_scan4 would run
+    bool drop_t32;
+    Scan3Geom geom3;
+    int S;              // hit slots per work item (fast kernels: a full region per wave)
+};
+
+// values the phases of one batch share
+struct Batch {
+    cis_index* ix;
+    const void* dQ;
+    int q_dtype, nq;
+    int64_t quota;
+    int L;
+    SearchOut out;
+    hipStream_t st;
+    Front f;
+    PlanOut* plan;
+    int64_t *item_off, *tab_off, *totals;
+    unsigned long long* qbound;  // per query: cross-cell bound of the scan
+    int *grp_cur, *grp_base;     // cursors and exclusive scan of the table groups
+    int* plan_fb;                // k_plan_par: per-query fall-back flags
+    uint64_t* vis_list;
+    int vis_cap;
+    unsigned long long* plan_hint;
+    int hint_slot;
+    const int64_t* d_tot;        // the batch did not wait for the totals: n_items, n_tabs, n_cand_all are bounds, the kernels read these
+    int64_t n_items, n_tabs, n_cand_all;
+    WorkItem* items;
+    TabDesc* tabs;
+    int* tab_order;              // table indices grouped by (split, cluster)
+    double *T, *px_buf;
+    float* T32;
+    cis_index::ProfRec pr;
+    std::chrono::steady_clock::time_point t_entry;
+};
+
+static int mark(Batch& b, int i) {
+    if (!b.ix->profiling) return CIS_OK;
+    if (b.ix->profiling == 1 && i != 5 && i != 3) return CIS_OK;  // level 1: only the pair around the scan kernel
+    CIS_CHECK_HIP(hipEventCreate(&b.pr.ev[i]));
+    CIS_CHECK_HIP(hipEventRecord(b.pr.ev[i], b.st));
+    return CIS_OK;
+}
+
+static void route_hints(cis_index* ix, int nq, int64_t quota, int L, Route* r) {
+    cis_model* m = ix->m;
+    const int V = m->V, K = m->K, M = m->M;
+    r->w_pow2 = m->w == 4 || m->w == 8 || m->w == 16 || m->w == 32;
+    r->split_tables = r->w_pow2 && K <= 256;
+    r->big = use_all_path(ix, M, K, L, nq);
+    r->fast = scan2_supported(M, K, L) && !ix->force_exact_scan;
+    r->tiny_cells = index_has_tiny_cells(ix);
+    r->geom = scan2_geom(M, K, L, nq);
     // scan v3 (16-bit fixed-point tables, four queries per workgroup) for large batches; its region entries hold 16-bit
     // positions, so a chunk is at most 65536 candidates.  scan_mode 3 forces it for any batch size (tests).
     static const int env_scan = getenv("CIS_FORCE_SCAN") ? atoi(getenv("CIS_FORCE_SCAN")) : 0;  // A/B runs: 2 or 3
@@ -4833,27 +4795,28 @@ static int search_batch(cis_index* ix, const void* dQ, int q_dtype, int nq, int6
         else if (n_s > 0 && (int64_t)n_f * 8 > n_s) { ix->m16_holdoff = 64; ++ix->m16_backoffs; ix->h_totals[4] = 0; }
     }
     const bool long_cells = env_long != 0 && !short_cells && (M <= 8 || (env_m16 && ix->m16_holdoff == 0)) && L <= 128 && ix->ncells <= 65536;
-    const bool use3 = !ix->force_exact_scan && scan3_supported(M, K, L) && !use_all_path(ix, M, K, L, nq) &&
-                      (ix->force_scan3 || (nq >= 256 && !ix->force_scan2 && (env_scan == 3 || (env_scan == 0 && (short_cells || long_cells)))));
+    r->use3 = !ix->force_exact_scan && scan3_supported(M, K, L) && !r->big &&
+              (ix->force_scan3 || (nq >= 256 && !ix->force_scan2 && (env_scan == 3 || (env_scan == 0 && (short_cells || long_cells)))));
     // (Splitting a shard's cells into chunks so that a cell-sharded index at world = 8 fills the chip again was measured
     // and lost: 0.516 against 0.306 ms per partial search -- more survivors, colder bounds: profiles/r02d_shard_emulation.txt.)
-    int seg_max = use3 ? (nq >= 64 ? 65536 : 4096) : (nq >= 1024 ? (1 << 20) : (nq >= 64 ? 16384 : 4096));
+    int seg_max = r->use3 ? (nq >= 64 ? 65536 : 4096) : (nq >= 1024 ? (1 << 20) : (nq >= 64 ? 16384 : 4096));
     // (Round 3 cut the long cells of a shard of four or more into chunks of 20480 candidates so that its few work items spread over
     // the chip: partial search 0.343 -> 0.307 ms alone on the device.  With three batches in flight the whole-cell chunks win -- emulated
     // rank 0 of world 8: 0.227 -> 0.163 ms per step, and 0.552 -> 0.479 ms for the routed protocol's full batches
     // (profiles/archive/r05b/r05_shards.txt) -- so the rule is gone; CIS_SEG_MAX=20480 brings it back for A/B runs.)
     // The HBM-streaming route (lopq_stream.hip): few queries, very many candidates each -- an exhaustive quota, or any quota on cells
     // of hundreds of thousands of codes.  Decided here from the bound of the candidates per query (the chunk size is part of the
-    // plan); the exact count confirms it below.  Chunks of 65536 candidates, longer when the largest cell would need more than the
-    // slot builder's 16 chunk keys (the items of a slot must be the SAME chunk of a cell).
+    // plan); the exact count confirms it in route_decide.  Chunks of 65536 candidates, longer when the largest cell would need more
+    // than the slot builder's 16 chunk keys (the items of a slot must be the SAME chunk of a cell).
     static const int64_t stream_min = getenv("CIS_STREAM_MIN") ? atoll(getenv("CIS_STREAM_MIN")) : 262144;  // candidates per query from which it pays
     static const int stream_nq = getenv("CIS_STREAM_NQ") ? atoi(getenv("CIS_STREAM_NQ")) : 16;               // 0: never
+    r->stream_min = stream_min;
     const bool stream_auto = !ix->stream_off && !ix->force_exact_scan && !ix->force_prefilter_scan && !ix->force_scan2 && !ix->force_scan3 &&
                              nq <= stream_nq && L <= 440 && ix->world == 1 &&
                              ((quota < ix->n_total ? (quota < 0 ? 0 : quota) : ix->n_total) + ix->max_cell) >= stream_min;
-    const bool stream_hint = (ix->force_stream || stream_auto) && !ix->stream_off && stream_supported(M, K, L) && (K % 4 == 0) &&
-                             ix->ncells <= 65536 && !index_has_tiny_cells(ix);
-    if (stream_hint) {
+    r->stream_hint = (ix->force_stream || stream_auto) && !ix->stream_off && stream_supported(M, K, L) && (K % 4 == 0) &&
+                     ix->ncells <= 65536 && !r->tiny_cells;
+    if (r->stream_hint) {
         // One chunk per cell (round 6): the stream kernel cuts the ROWS of all slots into equal ranges itself, so short chunks buy
         // nothing and cost plan, slot builder and candidate layout their work items (2398 -> 256 for the exhaustive query over 200 M
         // codes).  A chunk stays below 2^31 code bytes (32-bit buffer offsets).
@@ -4867,106 +4830,115 @@ static int search_batch(cis_index* ix, const void* dQ, int q_dtype, int nq, int6
         if (ix->force_stream && getenv("CIS_STREAM_SEG")) seg_max = atoi(getenv("CIS_STREAM_SEG")) > 0 ? atoi(getenv("CIS_STREAM_SEG")) : seg_max;  // tests: short chunks on small fixtures
     }
     if (const char* e = getenv("CIS_SEG_MAX")) seg_max = atoi(e) > 0 ? atoi(e) : seg_max;  // A/B runs (tools/emulate_shard.py)
+    r->seg_max = seg_max;
     // thousands of coarse clusters (the release configurations' V = 2048 / 4096): the plan is a per-query selection + sort
     // (k_plan_par) instead of one frontier step per visited cell; queries it cannot resolve fall back to the frontier walk
     const bool no_par_plan = getenv("CIS_NO_PAR_PLAN") != nullptr;
     // ... and few queries that visit MANY cells of a small vocabulary (the streaming route's exhaustive quota: all 256 cells of V = 16):
     // the frontier walk costs ~1.3 us per visited cell and runs twice (count, emit) -- 0.67 of the 1.25 ms of a single exhaustive
     // query over 200 M codes; the sort-based plan does the same cells in one band
-    const bool stream_par = stream_hint && V >= 8 && ix->n_total > 0 &&
+    const bool stream_par = r->stream_hint && V >= 8 && ix->n_total > 0 &&
                             (double)(quota < 0 ? 0 : quota) * (double)ix->nonempty_cells >= 32.0 * (double)ix->n_total;
-    const bool par_plan = ((V >= 128 || stream_par) && V <= PLAN_PAR_STAGE) && !no_par_plan;
-    unsigned long long* plan_hint = (par_plan && !getenv("CIS_NO_PLAN_HINT")) ? ix->plan_hint_ptr() : nullptr;
-    const int hint_slot = (int)((ix->plan_seq + 1) & 1);  // this batch's launches add into this parity and read the other
-    int* plan_fb = nullptr;
-    uint64_t* vis_list = nullptr;
-    // cells WITH candidates per query the fast plan lists (16 bytes each; the empty cells it walks -- most of them at thousands of coarse
-    // clusters, tens of thousands for an outlier query -- are not listed): 2 GB of lists per batch at most; past the cap the query goes
-    // to the serial frontier walk, ~3 us per cell
-    int64_t vis_cap64 = ((int64_t)1 << 31) / ((int64_t)(nq > 0 ? nq : 1) * 16);
-    if (vis_cap64 < 4096) vis_cap64 = 4096;
-    if (vis_cap64 > (1 << 20)) vis_cap64 = 1 << 20;
-    if (vis_cap64 > (int64_t)V * V) vis_cap64 = (int64_t)V * V;
-    const int vis_cap = (int)vis_cap64;
-    if (par_plan) {
-        CIS_TRY(ix->w_planfb.reserve((size_t)2 * nq * sizeof(int)));
-        CIS_TRY(ix->w_vis.reserve((size_t)nq * vis_cap * 2 * sizeof(uint64_t)));
-        plan_fb = ix->w_planfb.as<int>();
-        vis_list = ix->w_vis.as<uint64_t>();
-    }
-    const size_t plan_lds = (size_t)V * sizeof(int);
-    int Vp2 = 64;
-    while (Vp2 < V) Vp2 <<= 1;
+    r->par_plan = ((V >= 128 || stream_par) && V <= PLAN_PAR_STAGE) && !no_par_plan;
     static const bool no_fused_front = getenv("CIS_NO_FUSED_FRONT") != nullptr;
-    const bool fused_front = V <= 64 && !par_plan && !no_fused_front;
-    if (fused_front) {
+    r->fused_front = V <= 64 && !r->par_plan && !no_fused_front;
+}
+
+#ifdef CIS_PLAN_DBG
+static void dump_plan_dbg(int nq) {
+    unsigned long long h[12];
+    (void)hipDeviceSynchronize();
+    (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_plan_dbg), sizeof(h));
+    fprintf(stderr, "[cis] k_plan_par: %d queries, probes %.1f / query, bands %.2f / query, bisection %.1f us / query, after rows %.1f, after cells %.1f, after sort %.1f, after cut %.1f us / query (cumulative), cells per band %.0f (100 MHz clock)\n",
+            nq, (double)h[0] / nq, (double)h[1] / nq, (double)h[2] / nq / 100.0, (double)h[5] / nq / 100.0, (double)h[6] / nq / 100.0, (double)h[7] / nq / 100.0, (double)h[3] / nq / 100.0, h[1] ? (double)h[4] / (double)h[1] : 0.0);
+    fprintf(stderr, "[cis] k_plan_par since kernel start: staged %.1f, bands done %.1f, visited pass %.1f, end %.1f us / query\n", (double)h[8] / nq / 100.0, (double)h[9] / nq / 100.0, (double)h[10] / nq / 100.0, (double)h[11] / nq / 100.0);
+    memset(h, 0, sizeof(h));
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_plan_dbg), h, sizeof(h));
+}
+#endif
+
+// CIS_DEBUG_PLAN: how many queries of the batch the sort-based plan handed to the frontier walk
+static int dump_plan_fallbacks(const Batch& b) {
+    std::vector<int> fbh(b.nq);
+    CIS_CHECK_HIP(hipMemcpyAsync(fbh.data(), b.plan_fb, (size_t)b.nq * sizeof(int), hipMemcpyDeviceToHost, b.st));
+    CIS_CHECK_HIP(hipStreamSynchronize(b.st));
+    int nfb = 0;
+    for (int i = 0; i < b.nq; ++i) nfb += fbh[i] != 0;
+    fprintf(stderr, "[cis] k_plan_par: %d of %d queries fall back to the frontier walk (quota %lld)\n", nfb, b.nq, (long long)b.quota);
+    return CIS_OK;
+}
+
+// CIS_HOST_TIMING=1: where the host spends a batch (stderr, every 400 batches): entry -> plan totals requested, the wait for them
+static void host_timing(const Batch& b, std::chrono::steady_clock::time_point t0) {
+    static const bool ht = getenv("CIS_HOST_TIMING") != nullptr;
+    if (!ht) return;
+    static std::atomic<long long> n_{0}, wait_ns{0}, front_ns{0};
+    const auto t1 = std::chrono::steady_clock::now();
+    wait_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(t1 - t0).count();
+    front_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(t0 - b.t_entry).count();
+    if (++n_ % 400 == 0)
+        fprintf(stderr, "[cis] host timing over %lld batches: front-end enqueue %.1f us, wait for the plan totals %.1f us per batch\n", (long long)n_,
+                front_ns / 1e3 / n_, wait_ns / 1e3 / n_);
+}
+
+// coarse distances, rank and the counting pass of the multisequence walk
+template <typename CT>
+static int front_count(Batch& b, const Route& r) {
+    cis_index* ix = b.ix;
+    cis_model* m = ix->m;
+    hipStream_t st = b.st;
+    const int V = m->V, nq = b.nq;
+    uint16_t* order = ix->w_order.as<uint16_t>();
+    CT* sorted = ix->w_sorted.as<CT>();
+    if (r.fused_front) {
         // coarse distances + rank + counting pass of the multisequence walk in one launch (k_front_small)
         const size_t flds = (size_t)V * (32 + 4 + 4);
-        if (ct == CIS_F32)
-            hipLaunchKernelGGL(k_front_small<float>, dim3(nq), dim3(64), flds, st, (const float*)xc, D, h, m->d_Cs32, m->prog_h, ix->gcount_ptr(),
-                               ix->loff_ptr(), nq, V, quota, seg_max, ix->w_order.as<uint16_t>(), ix->w_sorted.as<float>(), plan, grp_cnt);
-        else
-            hipLaunchKernelGGL(k_front_small<double>, dim3(nq), dim3(64), flds, st, (const double*)xc, D, h, m->d_Cs64, m->prog_h, ix->gcount_ptr(),
-                               ix->loff_ptr(), nq, V, quota, seg_max, ix->w_order.as<uint16_t>(), ix->w_sorted.as<double>(), plan, grp_cnt);
-    } else {
-    CIS_TRY(cis_launch_sqdist_both(m, xc, ct, nq, ix->w_cd.p, st));
-    if (ct == CIS_F32) {
-        const bool sort_lds = getenv("CIS_RANK_SORT_LDS") != nullptr;  // the LDS form of the sort (A/B runs)
-        if (V > 256 && Vp2 == 1024 && !sort_lds)
-            hipLaunchKernelGGL(k_rank_sort_reg<4>, dim3(nq, 2), dim3(256), 0, st, ix->w_cd.as<float>(), nq, V, ix->w_order.as<uint16_t>(), ix->w_sorted.as<float>(), grp_cnt);
-        else if (V > 256 && Vp2 == 2048 && !sort_lds)
-            hipLaunchKernelGGL(k_rank_sort_reg<8>, dim3(nq, 2), dim3(256), 0, st, ix->w_cd.as<float>(), nq, V, ix->w_order.as<uint16_t>(), ix->w_sorted.as<float>(), grp_cnt);
-        else if (V > 256 && Vp2 == 4096 && !sort_lds)
-            hipLaunchKernelGGL(k_rank_sort_reg<16>, dim3(nq, 2), dim3(256), 0, st, ix->w_cd.as<float>(), nq, V, ix->w_order.as<uint16_t>(), ix->w_sorted.as<float>(), grp_cnt);
-        else if (V > 256 && Vp2 <= 4096)
-            hipLaunchKernelGGL(k_rank_sort<float>, dim3(nq, 2), dim3(256), (size_t)Vp2 * 16, st, ix->w_cd.as<float>(), nq, V, Vp2,
-                               ix->w_order.as<uint16_t>(), ix->w_sorted.as<float>(), grp_cnt);
-        else
-            hipLaunchKernelGGL(k_rank<float>, dim3(nq, 2), dim3(V <= 64 ? 64 : 256), (size_t)V * 8, st, ix->w_cd.as<float>(), nq, V,
-                               ix->w_order.as<uint16_t>(), ix->w_sorted.as<float>(), grp_cnt);
-        if (par_plan)
-            hipLaunchKernelGGL((k_plan_par<float, false>), dim3(nq), dim3(256), (size_t)2 * (V < PLAN_SP ? V : PLAN_SP) * sizeof(float), st, ix->w_sorted.as<float>(), ix->w_order.as<uint16_t>(),
-                               ix->gcount_ptr(), ix->loff_ptr(), nq, V, quota, seg_max, plan, nullptr, nullptr, nullptr,
-                               nullptr, grp_cnt, nullptr, nullptr, nullptr, vis_list, plan_fb, vis_cap, plan_hint, hint_slot);
+        hipLaunchKernelGGL(k_front_small<CT>, dim3(nq), dim3(64), flds, st, (const CT*)b.f.xc, m->D, m->h, coarse_centroids(m, CT()), m->prog_h,
+                           ix->gcount_ptr(), ix->loff_ptr(), nq, V, b.quota, r.seg_max, order, sorted, b.plan, b.f.grp_cnt);
+        return CIS_OK;
+    }
+    CIS_TRY(cis_launch_sqdist_both(m, b.f.xc, b.f.ct, nq, ix->w_cd.p, st));
+    launch_rank<CT>(ix, nq, true, b.f.grp_cnt, st);
+    if (r.par_plan)
+        hipLaunchKernelGGL((k_plan_par<CT, false>), dim3(nq), dim3(256), (size_t)2 * (V < PLAN_SP ? V : PLAN_SP) * sizeof(CT), st, sorted, order,
+                           ix->gcount_ptr(), ix->loff_ptr(), nq, V, b.quota, r.seg_max, b.plan, nullptr, nullptr, nullptr,
+                           nullptr, b.f.grp_cnt, nullptr, nullptr, nullptr, b.vis_list, b.plan_fb, b.vis_cap, b.plan_hint, b.hint_slot);
 #ifdef CIS_PLAN_DBG
-        if (par_plan) {
-            unsigned long long h[12];
-            (void)hipDeviceSynchronize();
-            (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_plan_dbg), sizeof(h));
-            fprintf(stderr, "[cis] k_plan_par: %d queries, probes %.1f / query, bands %.2f / query, bisection %.1f us / query, after rows %.1f, after cells %.1f, after sort %.1f, after cut %.1f us / query (cumulative), cells per band %.0f (100 MHz clock)\n",
-                    nq, (double)h[0] / nq, (double)h[1] / nq, (double)h[2] / nq / 100.0, (double)h[5] / nq / 100.0, (double)h[6] / nq / 100.0, (double)h[7] / nq / 100.0, (double)h[3] / nq / 100.0, h[1] ? (double)h[4] / (double)h[1] : 0.0);
-            fprintf(stderr, "[cis] k_plan_par since kernel start: staged %.1f, bands done %.1f, visited pass %.1f, end %.1f us / query\n", (double)h[8] / nq / 100.0, (double)h[9] / nq / 100.0, (double)h[10] / nq / 100.0, (double)h[11] / nq / 100.0);
-            memset(h, 0, sizeof(h));
-            (void)hipMemcpyToSymbol(HIP_SYMBOL(g_plan_dbg), h, sizeof(h));
-        }
+    if constexpr (sizeof(CT) == 4)  // (the counters are read back for float32 batches only)
+        if (r.par_plan) dump_plan_dbg(nq);
 #endif
-        hipLaunchKernelGGL((k_plan<float, false>), dim3(nq), dim3(64), plan_lds, st, ix->w_sorted.as<float>(),
-                           ix->w_order.as<uint16_t>(), ix->gcount_ptr(), ix->loff_ptr(), nq, V, quota,
-                           seg_max, plan, nullptr, nullptr, nullptr, nullptr, grp_cnt, nullptr, nullptr, nullptr, plan_fb);
-    } else {
-        if (V > 256 && Vp2 <= 4096)
-            hipLaunchKernelGGL(k_rank_sort<double>, dim3(nq, 2), dim3(256), (size_t)Vp2 * 16, st, ix->w_cd.as<double>(), nq, V, Vp2,
-                               ix->w_order.as<uint16_t>(), ix->w_sorted.as<double>(), grp_cnt);
-        else
-            hipLaunchKernelGGL(k_rank<double>, dim3(nq, 2), dim3(V <= 64 ? 64 : 256), (size_t)V * 8, st, ix->w_cd.as<double>(), nq,
-                               V, ix->w_order.as<uint16_t>(), ix->w_sorted.as<double>(), grp_cnt);
-        if (par_plan)
-            hipLaunchKernelGGL((k_plan_par<double, false>), dim3(nq), dim3(256), (size_t)2 * (V < PLAN_SP ? V : PLAN_SP) * sizeof(double), st, ix->w_sorted.as<double>(), ix->w_order.as<uint16_t>(),
-                               ix->gcount_ptr(), ix->loff_ptr(), nq, V, quota, seg_max, plan, nullptr, nullptr, nullptr,
-                               nullptr, grp_cnt, nullptr, nullptr, nullptr, vis_list, plan_fb, vis_cap, plan_hint, hint_slot);
-        hipLaunchKernelGGL((k_plan<double, false>), dim3(nq), dim3(64), plan_lds, st, ix->w_sorted.as<double>(),
-                           ix->w_order.as<uint16_t>(), ix->gcount_ptr(), ix->loff_ptr(), nq, V, quota,
-                           seg_max, plan, nullptr, nullptr, nullptr, nullptr, grp_cnt, nullptr, nullptr, nullptr, plan_fb);
-    }
-    }
-    if (par_plan && getenv("CIS_DEBUG_PLAN")) {
-        std::vector<int> fbh(nq);
-        CIS_CHECK_HIP(hipMemcpyAsync(fbh.data(), plan_fb, (size_t)nq * sizeof(int), hipMemcpyDeviceToHost, st));
-        CIS_CHECK_HIP(hipStreamSynchronize(st));
-        int nfb = 0;
-        for (int i = 0; i < nq; ++i) nfb += fbh[i] != 0;
-        fprintf(stderr, "[cis] k_plan_par: %d of %d queries fall back to the frontier walk (quota %lld)\n", nfb, nq, (long long)quota);
-    }
+    hipLaunchKernelGGL((k_plan<CT, false>), dim3(nq), dim3(64), (size_t)V * sizeof(int), st, sorted, order, ix->gcount_ptr(), ix->loff_ptr(), nq, V,
+                       b.quota, r.seg_max, b.plan, nullptr, nullptr, nullptr, nullptr, b.f.grp_cnt, nullptr, nullptr, nullptr, b.plan_fb);
+    return CIS_OK;
+}
+
+// the emitting pass of the walk (work items + table list) and the tables' first stage
+template <typename CT>
+static void emit_and_tables(Batch& b, const Route& r) {
+    cis_index* ix = b.ix;
+    cis_model* m = ix->m;
+    hipStream_t st = b.st;
+    const int V = m->V, nq = b.nq, h = m->h;
+    const uint16_t* order = ix->w_order.as<uint16_t>();
+    const CT* sorted = ix->w_sorted.as<CT>();
+    const size_t tab_lds = (size_t)(2 * h + (h < 256 ? 256 : 0)) * sizeof(double);
+    if (r.par_plan)
+        hipLaunchKernelGGL((k_plan_par<CT, true>), dim3(nq), dim3(256), 0, st, sorted, order, ix->gcount_ptr(), ix->loff_ptr(), nq, V, b.quota,
+                           r.seg_max, b.plan, b.item_off, b.tab_off, b.items, b.tabs, nullptr, b.grp_base, b.grp_cur, b.tab_order, b.vis_list,
+                           b.plan_fb, b.vis_cap, nullptr, 0);
+    hipLaunchKernelGGL((k_plan<CT, true>), dim3(nq), dim3(64), (size_t)V * sizeof(int), st, sorted, order, ix->gcount_ptr(), ix->loff_ptr(), nq, V,
+                       b.quota, r.seg_max, b.plan, b.item_off, b.tab_off, b.items, b.tabs, nullptr, b.grp_base, b.grp_cur, b.tab_order, b.plan_fb);
+    if (b.n_tabs > 0)
+        launch_tables<CT>(b.n_tabs, tab_lds, st, (const CT*)b.f.xc, coarse_centroids(m, CT()), m->d_Rt, m->d_mus, m->d_subs, b.tabs, b.tab_order, V, h,
+                          m->w, m->nf, m->K, m->D, b.T, m->prog_w, b.px_buf, b.d_tot, r.direct ? b.T32 : nullptr);
+}
+
+// exclusive scan of the plan; then the totals that size the rest of the batch -- their bounds where those do, else the read-back
+static int plan_totals(Batch& b, const Route& r) {
+    cis_index* ix = b.ix;
+    cis_model* m = ix->m;
+    hipStream_t st = b.st;
+    const int V = m->V, nq = b.nq, L = b.L;
     if (!ix->h_totals) {
         CIS_CHECK_HIP(hipHostMalloc((void**)&ix->h_totals, 12 * sizeof(int64_t), hipHostMallocMapped | hipHostMallocCoherent));
         CIS_CHECK_HIP(hipHostGetDevicePointer((void**)&ix->d_h_totals, ix->h_totals, 0));
@@ -4977,47 +4949,43 @@ static int search_batch(cis_index* ix, const void* dQ, int q_dtype, int nq, int6
     const int64_t seq = ++ix->plan_seq;
     const int n_groups = 2 * V * GRP_SUB;
     const bool groups_apart = n_groups > 8192;  // wide vocabularies: the group bases by their own launch (all 16 waves)
+    int* grp_cnt = b.f.grp_cnt;
     if (groups_apart)
-        hipLaunchKernelGGL(k_group_bases, dim3((n_groups + GROUP_TILE - 1) / GROUP_TILE), dim3(256), 0, st, grp_cnt, grp_base, n_groups,
+        hipLaunchKernelGGL(k_group_bases, dim3((n_groups + GROUP_TILE - 1) / GROUP_TILE), dim3(256), 0, st, grp_cnt, b.grp_base, n_groups,
                            reinterpret_cast<unsigned long long*>(grp_cnt + GRP_WORDS(V)), (uint32_t)(seq & 0x7fffffff) | 0x80000000u);
-    hipLaunchKernelGGL(k_plan_scan, dim3(1), dim3(1024), 0, st, plan, nq, item_off, tab_off, totals, qbound, ix->d_h_totals, seq, grp_cnt, grp_base, groups_apart ? 0 : n_groups,
-                       plan_hint ? plan_hint + (hint_slot ^ 1) * 2 : nullptr);
+    hipLaunchKernelGGL(k_plan_scan, dim3(1), dim3(1024), 0, st, b.plan, nq, b.item_off, b.tab_off, b.totals, b.qbound, ix->d_h_totals, seq, grp_cnt, b.grp_base,
+                       groups_apart ? 0 : n_groups, b.plan_hint ? b.plan_hint + (b.hint_slot ^ 1) * 2 : nullptr);
     volatile int64_t* h_tot = ix->h_totals;
     // A small batch on the all-candidates path does not wait for the plan totals: the workspace is sized by upper bounds
     // (every query stops within quota + largest cell candidates, in at most `nonempty cells` cells) and the kernels
     // below read the real totals from device memory -- no host round trip in the middle of the batch.
-    const int64_t* d_tot = nullptr;
-    int64_t n_items = 0, n_tabs = 0, n_cand_all = 0;
+    b.d_tot = nullptr;
+    b.n_items = b.n_tabs = b.n_cand_all = 0;
     {
         static const bool no_bounds = getenv("CIS_NO_BOUNDS") != nullptr;
         // quota <= 0 still visits one cell (search.py:131-132: the test follows the first append)
-        const int64_t q_eff = quota < 0 ? 0 : quota;
+        const int64_t q_eff = b.quota < 0 ? 0 : b.quota;
         const int64_t per_q = (q_eff < ix->n_total ? q_eff : ix->n_total) + ix->max_cell;
-        const int64_t items_q = ix->nonempty_cells + per_q / seg_max + 2;
-        const bool split_ok = (m->w == 4 || m->w == 8 || m->w == 16 || m->w == 32) && K <= 256;
-        if (!no_bounds && !stream_hint && nq <= 64 && L <= MAX_LDS_LIMIT && split_ok && use_all_path(ix, M, K, L, nq) && items_q <= 4096 &&
-            (double)nq * (double)per_q < 64.0e6) {
-            d_tot = totals;
-            n_items = (int64_t)nq * items_q;
-            n_tabs = (int64_t)nq * 2 * V;
-            n_cand_all = (int64_t)nq * per_q;
-            ix->stats_pending_seq = seq;
-        }
+        const int64_t items_q = ix->nonempty_cells + per_q / r.seg_max + 2;
+        const bool small_all = !no_bounds && !r.stream_hint && nq <= 64 && L <= MAX_LDS_LIMIT && r.split_tables && r.big && items_q <= 4096 &&
+                               (double)nq * (double)per_q < 64.0e6;
         // The streaming route when it is CERTAIN before the plan is known -- every query collects at least min(quota, n_total)
         // candidates (search.py:128-133 stops at the quota or at the end of the index), and that alone is past the route's threshold
         // (an exhaustive quota): the same bounds size the workspaces, the kernels read the real totals from device memory, and the
         // host does not stop in the middle of the batch (round 6: the read-back was a 35 us hole in a 0.5 ms exhaustive query).
         static const bool no_stream_bounds = getenv("CIS_STREAM_WAIT") != nullptr;   // A/B runs: the read-back as before
-        if (!no_bounds && !no_stream_bounds && stream_hint && split_ok && items_q <= 65536 && (double)nq * (double)items_q < 4.0e6 &&
-            (ix->force_stream || (q_eff < ix->n_total ? q_eff : ix->n_total) >= stream_min) && ix->n_total > 0 && nq <= 64) {
-            d_tot = totals;
-            n_items = (int64_t)nq * items_q;
-            n_tabs = (int64_t)nq * 2 * V;
-            n_cand_all = (int64_t)nq * per_q;
+        const bool sure_stream = !no_bounds && !no_stream_bounds && r.stream_hint && r.split_tables && items_q <= 65536 &&
+                                 (double)nq * (double)items_q < 4.0e6 &&
+                                 (ix->force_stream || (q_eff < ix->n_total ? q_eff : ix->n_total) >= r.stream_min) && ix->n_total > 0 && nq <= 64;
+        if (small_all || sure_stream) {
+            b.d_tot = b.totals;
+            b.n_items = (int64_t)nq * items_q;
+            b.n_tabs = (int64_t)nq * 2 * V;
+            b.n_cand_all = (int64_t)nq * per_q;
             ix->stats_pending_seq = seq;
         }
     }
-    if (!d_tot) {
+    if (!b.d_tot) {
         // the plan totals size the rest of the batch: poll the pinned sequence word (a blocking stream synchronisation
         // wakes up tens of microseconds late); past 2 ms -- a stream busy with the caller's earlier work, or an error --
         // fall back to the blocking wait
@@ -5032,38 +5000,32 @@ static int search_batch(cis_index* ix, const void* dQ, int q_dtype, int nq, int6
             CIS_CHECK_HIP(hipStreamSynchronize(st));
             CIS_REQUIRE(__atomic_load_n(&ix->h_totals[3], __ATOMIC_ACQUIRE) == seq, "plan totals did not arrive");
         }
-        {   // CIS_HOST_TIMING=1: where the host spends a batch (stderr, every 400 batches): entry -> plan totals requested, the wait for them
-            static const bool ht = getenv("CIS_HOST_TIMING") != nullptr;
-            if (ht) {
-                static std::atomic<long long> n_{0}, wait_ns{0}, front_ns{0};
-                const auto t1 = std::chrono::steady_clock::now();
-                wait_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(t1 - t0).count();
-                front_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(t0 - t_entry).count();
-                if (++n_ % 400 == 0)
-                    fprintf(stderr, "[cis] host timing over %lld batches: front-end enqueue %.1f us, wait for the plan totals %.1f us per batch\n", (long long)n_,
-                            front_ns / 1e3 / n_, wait_ns / 1e3 / n_);
-            }
-        }
-        n_items = h_tot[0]; n_tabs = h_tot[1]; n_cand_all = h_tot[2];
+        host_timing(b, t0);
+        b.n_items = h_tot[0]; b.n_tabs = h_tot[1]; b.n_cand_all = h_tot[2];
         ix->stats_pending_seq = 0;
     }
-    CIS_REQUIRE(n_items < ((int64_t)1 << 31) && n_tabs < ((int64_t)1 << 31), "query batch too large");
-    // tiny cells on the all-candidates path: entries computed per candidate from px (k_adc_direct), no tables
-    const bool direct_elig = !d_tot && use_all_path(ix, M, K, L, nq) && index_has_tiny_cells(ix) && h <= 256 && direct_jp(M, K, m->w) > 0 &&
-                             !getenv("CIS_TABLES_UNGROUPED") && !getenv("CIS_NO_DIRECT");
-    const bool stream = stream_hint && n_items > 0 && ((m->w == 4 || m->w == 8 || m->w == 16 || m->w == 32) || (scan2_supported(M, K, L) && !ix->force_exact_scan)) &&
-                        (ix->force_stream || d_tot != nullptr || n_cand_all / (nq > 0 ? nq : 1) >= stream_min);   // (d_tot: certain, see above)
-    if (!stream)
-    {
+    CIS_REQUIRE(b.n_items < ((int64_t)1 << 31) && b.n_tabs < ((int64_t)1 << 31), "query batch too large");
+    return CIS_OK;
+}
+
+// the route, now that the totals are known; CIS_RETRY_SMALLER when the batch does not fit the workspace budget
+static int route_decide(Batch& b, Route* r) {
+    cis_index* ix = b.ix;
+    cis_model* m = ix->m;
+    const int K = m->K, M = m->M, h = m->h, nf = m->nf, nq = b.nq, L = b.L;
+    r->direct = !b.d_tot && r->big && r->tiny_cells && h <= 256 && direct_jp(M, K, m->w) > 0 &&
+                !getenv("CIS_TABLES_UNGROUPED") && !getenv("CIS_NO_DIRECT");
+    r->stream = r->stream_hint && b.n_items > 0 && (r->w_pow2 || r->fast) &&
+                (ix->force_stream || b.d_tot != nullptr || b.n_cand_all / (nq > 0 ? nq : 1) >= r->stream_min);   // (d_tot: certain, see plan_totals)
+    if (!r->stream) {
         // workspace budget: per-item hit lists and the float64 tables.  A batch that would need more (e.g. an
         // exhaustive quota: every query visits every cell) is split by the caller and planned again.
-        const bool fast_ = scan2_supported(M, K, L) && !ix->force_exact_scan;
-        const int64_t S_ = fast_ ? scan2_geom(M, K, L, nq).S : L;
-        double need = (double)n_items * S_ * (fast_ ? sizeof(uint64_t) : sizeof(cis_hit)) + (double)n_tabs * nf * K * sizeof(double);
-        if (use_all_path(ix, M, K, L, nq)) {  // every candidate's key, plus the selected pairs or the full sort's buffers
-            const SelectPlan sp_ = select_plan(L, nq, n_cand_all);
-            need = (sp_.select ? 8.0 * (double)n_cand_all + (sp_.sort_lds ? 16.0 : 32.0) * (double)nq * (double)sp_.stride : 32.0 * (double)n_cand_all) +
-                   (direct_elig ? (double)n_tabs * h * sizeof(double) : (double)n_tabs * nf * K * sizeof(double));
+        const int64_t S_ = r->fast ? r->geom.S : L;
+        double need = (double)b.n_items * S_ * (r->fast ? sizeof(uint64_t) : sizeof(cis_hit)) + (double)b.n_tabs * nf * K * sizeof(double);
+        if (r->big) {  // every candidate's key, plus the selected pairs or the full sort's buffers
+            const SelectPlan sp_ = select_plan(L, nq, b.n_cand_all);
+            need = (sp_.select ? 8.0 * (double)b.n_cand_all + (sp_.sort_lds ? 16.0 : 32.0) * (double)nq * (double)sp_.stride : 32.0 * (double)b.n_cand_all) +
+                   (r->direct ? (double)b.n_tabs * h * sizeof(double) : (double)b.n_tabs * nf * K * sizeof(double));
         }
         // default 24 GB of the 288 GB: thousands of coarse clusters need ~1.6 MB of tables per query (V = 2048, quota 10000)
         const double budget = (getenv("CIS_WORKSPACE_GB") ? atof(getenv("CIS_WORKSPACE_GB")) : 24.0) * 1.0e9;
@@ -5072,71 +5034,71 @@ static int search_batch(cis_index* ix, const void* dQ, int q_dtype, int nq, int6
             return CIS_RETRY_SMALLER;
         }
     }
-    if (!d_tot) {
-        ix->stats[0] += n_cand_all;
-        ix->stats[1] += n_items;
-        ix->stats[2] += n_tabs;
+    if (!b.d_tot) {
+        ix->stats[0] += b.n_cand_all;
+        ix->stats[1] += b.n_items;
+        ix->stats[2] += b.n_tabs;
     }
-    // 3. emit items + table list
-    CIS_TRY(mark(1));  // the plan read-back above is part of the front end
-    CIS_TRY(ix->w_items.reserve((size_t)(n_items + 1) * sizeof(WorkItem)));
-    CIS_TRY(ix->w_tabs.reserve((size_t)(n_tabs + 1) * sizeof(TabDesc)));
-    CIS_TRY(ix->w_T.reserve(direct_elig ? 256 : (size_t)(n_tabs + 1) * nf * K * sizeof(double)));
-    const bool big = use_all_path(ix, M, K, L, nq);  // ranked over all candidates' exact distances (below)
-    const bool tiny_cells = index_has_tiny_cells(ix);
-    const bool fast = scan2_supported(M, K, L) && !ix->force_exact_scan;
-    const Scan2Geom geom = scan2_geom(M, K, L, nq);
-    const Scan3Geom geom3 = scan3_geom(M, K, L, n_items > 0 ? n_cand_all / n_items : 0, ix->force_two_pass);
-    const int S = fast ? (use3 ? geom3.S : geom.S) : L;  // hit slots per work item (fast kernels: a full region per wave)
-    if (!big && !stream) CIS_TRY(ix->w_hits.reserve((size_t)(n_items + 1) * S * (fast ? sizeof(uint64_t) : sizeof(cis_hit))));
-    CIS_TRY(ix->w_hitn.reserve((size_t)(n_items + 1) * 2 * sizeof(int)));
-    if (use3) CIS_TRY(ix->w_slack.reserve((size_t)(n_items + 1) * 2 * sizeof(float)));
-    WorkItem* items = ix->w_items.as<WorkItem>();
-    TabDesc* tabs = ix->w_tabs.as<TabDesc>();
-    CIS_TRY(ix->w_tord.reserve((size_t)(n_tabs + 1) * sizeof(int)));
-    int* tab_order = ix->w_tord.as<int>();  // table indices grouped by (split, cluster)
-    double* T = ix->w_T.as<double>();
-    // tiny cells: the float32 copy of px for k_tiny_select lives here (no tables on that path)
+    r->geom3 = scan3_geom(M, K, L, b.n_items > 0 ? b.n_cand_all / b.n_items : 0, ix->force_two_pass);
+    r->S = r->fast ? (r->use3 ? r->geom3.S : r->geom.S) : L;
+    r->use5 = false;
+    if (!r->stream && !r->big && r->fast && b.n_items > 0) {  // (the scan route's fast kernels: the only readers)
+        // k_adc_scan5 (round 5): where the sampled form k_adc_scan4 would run -- one threshold per query for the whole batch
+        // instead of one per slot, eight queries per slot.  MEASURED AND LEFT OFF (profiles/r05g_*, r05h_*: C4 sample 64 + thresholds 17 +
+        // main pass 200 + check 12 us against 231 us for the whole of k_adc_scan4, and a merge of 134 instead of 76 us for the longer
+        // lists; both pipes ~40 % busy at three workgroups per CU: the loop is bound by latency, not by instructions).  CIS_SCAN5=1
+        // routes large batches to it, scan mode 7 forces it (tests: every search test passes on it).
+        static const int env_s5 = getenv("CIS_SCAN5") ? atoi(getenv("CIS_SCAN5")) : 0;
+        r->use5 = r->use3 && r->geom3.two_pass == 2 && scan5_supported(M, K, L) && (ix->force_scan5 || (env_s5 != 0 && !ix->force_scan3 && L <= 128));
+    }
     // The float32 copy of the tables is a third of what the tables kernel writes (8 + 4 bytes per entry: 402 MB per C2 batch, and that
     // kernel is bound by its writes); CIS_NO_T32=1 drops it -- the scans then convert the float64 entries while they stage them
     // (tab_f4: the same bits).  The tiny-cell path keeps its float32 px copy in this buffer.
     static const bool no_t32 = getenv("CIS_NO_T32") != nullptr && atoi(getenv("CIS_NO_T32")) != 0;
-    const bool drop_t32 = no_t32 && !direct_elig && (m->w == 4 || m->w == 8 || m->w == 16 || m->w == 32) && K <= 256;
-    if (!drop_t32) CIS_TRY(ix->w_T32.reserve(direct_elig ? (size_t)(n_tabs + 1) * h * sizeof(float) : (size_t)(n_tabs + 1) * nf * K * sizeof(float)));
-    float* T32 = drop_t32 ? nullptr : ix->w_T32.as<float>();
-    const size_t tab_lds = (size_t)(2 * h + (h < 256 ? 256 : 0)) * sizeof(double);
-    const bool split_tables = (m->w == 4 || m->w == 8 || m->w == 16 || m->w == 32) && K <= 256;
-    double* px_buf = nullptr;
-    if (split_tables) {
+    r->drop_t32 = no_t32 && !r->direct && r->split_tables;
+    return CIS_OK;
+}
+
+// workspaces of the emit pass, the tables and the scans' hit lists
+static int reserve_batch(Batch& b, const Route& r) {
+    cis_index* ix = b.ix;
+    cis_model* m = ix->m;
+    const int K = m->K, h = m->h, nf = m->nf;
+    const int64_t n_items = b.n_items, n_tabs = b.n_tabs;
+    CIS_TRY(ix->w_items.reserve((size_t)(n_items + 1) * sizeof(WorkItem)));
+    CIS_TRY(ix->w_tabs.reserve((size_t)(n_tabs + 1) * sizeof(TabDesc)));
+    CIS_TRY(ix->w_T.reserve(r.direct ? 256 : (size_t)(n_tabs + 1) * nf * K * sizeof(double)));
+    if (!r.big && !r.stream) CIS_TRY(ix->w_hits.reserve((size_t)(n_items + 1) * r.S * (r.fast ? sizeof(uint64_t) : sizeof(cis_hit))));
+    CIS_TRY(ix->w_hitn.reserve((size_t)(n_items + 1) * 2 * sizeof(int)));
+    if (r.use3) CIS_TRY(ix->w_slack.reserve((size_t)(n_items + 1) * 2 * sizeof(float)));
+    b.items = ix->w_items.as<WorkItem>();
+    b.tabs = ix->w_tabs.as<TabDesc>();
+    CIS_TRY(ix->w_tord.reserve((size_t)(n_tabs + 1) * sizeof(int)));
+    b.tab_order = ix->w_tord.as<int>();
+    b.T = ix->w_T.as<double>();
+    // tiny cells: the float32 copy of px for k_tiny_select lives in w_T32 (no tables on that path)
+    if (!r.drop_t32) CIS_TRY(ix->w_T32.reserve(r.direct ? (size_t)(n_tabs + 1) * h * sizeof(float) : (size_t)(n_tabs + 1) * nf * K * sizeof(float)));
+    b.T32 = r.drop_t32 ? nullptr : ix->w_T32.as<float>();
+    b.px_buf = nullptr;
+    if (r.split_tables) {
         CIS_TRY(ix->w_px.reserve((size_t)(n_tabs + 1) * h * sizeof(double)));
-        px_buf = ix->w_px.as<double>();
+        b.px_buf = ix->w_px.as<double>();
     }
-    if (ct == CIS_F32) {
-        if (par_plan)
-            hipLaunchKernelGGL((k_plan_par<float, true>), dim3(nq), dim3(256), 0, st, ix->w_sorted.as<float>(), ix->w_order.as<uint16_t>(),
-                               ix->gcount_ptr(), ix->loff_ptr(), nq, V, quota, seg_max, plan, item_off, tab_off, items,
-                               tabs, nullptr, grp_base, grp_cur, tab_order, vis_list, plan_fb, vis_cap, nullptr, 0);
-        hipLaunchKernelGGL((k_plan<float, true>), dim3(nq), dim3(64), plan_lds, st, ix->w_sorted.as<float>(),
-                           ix->w_order.as<uint16_t>(), ix->gcount_ptr(), ix->loff_ptr(), nq, V, quota,
-                           seg_max, plan, item_off, tab_off, items, tabs, nullptr, grp_base, grp_cur, tab_order, plan_fb);
-        if (n_tabs > 0)
-            launch_tables<float>(n_tabs, tab_lds, st, (const float*)xc, m->d_Cs32, m->d_Rt, m->d_mus, m->d_subs, tabs, tab_order, V, h,
-                                 m->w, nf, K, D, T, m->prog_w, px_buf, d_tot, direct_elig ? T32 : nullptr);
-    } else {
-        if (par_plan)
-            hipLaunchKernelGGL((k_plan_par<double, true>), dim3(nq), dim3(256), 0, st, ix->w_sorted.as<double>(), ix->w_order.as<uint16_t>(),
-                               ix->gcount_ptr(), ix->loff_ptr(), nq, V, quota, seg_max, plan, item_off, tab_off, items,
-                               tabs, nullptr, grp_base, grp_cur, tab_order, vis_list, plan_fb, vis_cap, nullptr, 0);
-        hipLaunchKernelGGL((k_plan<double, true>), dim3(nq), dim3(64), plan_lds, st, ix->w_sorted.as<double>(),
-                           ix->w_order.as<uint16_t>(), ix->gcount_ptr(), ix->loff_ptr(), nq, V, quota,
-                           seg_max, plan, item_off, tab_off, items, tabs, nullptr, grp_base, grp_cur, tab_order, plan_fb);
-        if (n_tabs > 0)
-            launch_tables<double>(n_tabs, tab_lds, st, (const double*)xc, m->d_Cs64, m->d_Rt, m->d_mus, m->d_subs, tabs, tab_order, V,
-                                  h, m->w, nf, K, D, T, m->prog_w, px_buf, d_tot, direct_elig ? T32 : nullptr);
-    }
-    const bool direct = direct_elig;
-    if (direct) {
-    } else if (split_tables && n_tabs > 0) {
+    return CIS_OK;
+}
+
+// second stage of the tables: from the projected residuals, or the float32 copy of the float64 tables
+static void finish_tables(const Batch& b, const Route& r) {
+    cis_model* m = b.ix->m;
+    hipStream_t st = b.st;
+    const int K = m->K, h = m->h, nf = m->nf;
+    const int64_t n_tabs = b.n_tabs;
+    double *T = b.T, *px_buf = b.px_buf;
+    float* T32 = b.T32;
+    TabDesc* tabs = b.tabs;
+    const int64_t* d_tot = b.d_tot;
+    if (r.direct) {
+    } else if (r.split_tables && n_tabs > 0) {
         const bool few = n_tabs <= 1024;   // (d_tot: n_tabs is a bound, the kernel reads the real count)
         dim3 g((unsigned)ceil_div(n_tabs, few ? 8 : 64), (unsigned)nf, 2);
 #define CIS_TFP(WW)                                                                                                                                      \
@@ -5149,395 +5111,492 @@ static int search_batch(cis_index* ix, const void* dQ, int q_dtype, int nq, int6
             default: CIS_TFP(32); break;
         }
 #undef CIS_TFP
-    } else if (fast && n_tabs > 0) {
+    } else if (r.fast && n_tabs > 0) {
         const int64_t ne = n_tabs * nf * K;
         hipLaunchKernelGGL(k_tables_f32, dim3((unsigned)ceil_div(ne, 256)), dim3(256), 0, st, T, ne, nf, K, T32, tabs);
     }
-    if (stream) {
-        // 4''. the HBM-streaming route (lopq_stream.hip): sample -> threshold -> stream -> exact keys of the listed candidates ->
-        // ranking (k_select_topl, ties by retrieval index) -> proof; a failed proof hands the batch to the generic path below
-        CIS_TRY(mark(2));
-        const uint8_t* codes = ix->codes_ptr();
-        const int64_t* ids = ix->ids_ptr();
-        // queries per slot: a pair costs the launch what one query costs (the codes are the bound), four cost ~1.45 of a pair
-        // (profiles/r06_stream_probe.txt) -- worth it when the queries share their cells, i.e. the quota covers most of the index
-        const bool shared_cells = quota >= ix->n_total / 2;
-        const int G = (nq >= 3 && shared_cells && stream_max_group() >= 4) ? 4 : (nq >= 2 ? 2 : 1);
-        const int cap = STREAM_CAP, B = STREAM_B;
-        const SelectPlan sp = select_plan(L, nq, (int64_t)nq * cap);
-        CIS_REQUIRE(sp.sort_lds, "streaming route: limit above the LDS-ranked range");
-        // slots: the work items of one chunk of one cell, G per slot (the slot builder of the scan kernels)
-        int64_t CH = ceil_div(ix->max_cell > 0 ? ix->max_cell : 1, (int64_t)seg_max);
-        CH = CH < 1 ? 1 : (CH > 16 ? 16 : CH);
-        const int64_t nkeys = 2 * ix->ncells * CH;
-        const int64_t max_slots = (n_items + nkeys) / G + nkeys + 2;
-        CIS_TRY(ix->w_order2.reserve((size_t)(64 + 2 * nkeys + 2 * max_slots * G) * sizeof(int)));
-        int* qctr = ix->w_order2.as<int>();
-        int* n_slots = qctr + 8;
-        int* qstart = qctr + 16;
-        int* cell_cnt = qctr + 64;
-        int* slot_off = cell_cnt + nkeys;
-        int* slots = slot_off + nkeys;
-        if (G > 1) {
-            const int64_t ninit = max_slots * G > nkeys ? max_slots * G : nkeys;
-            hipLaunchKernelGGL(k_slots_init, dim3((unsigned)ceil_div(ninit < 16 ? 16 : ninit, 256)), dim3(256), 0, st, qctr, cell_cnt, (int)nkeys, slots, max_slots * G);
-            hipLaunchKernelGGL(k_item_hist, dim3((unsigned)ceil_div(n_items, 256)), dim3(256), 0, st, items, n_items, cell_cnt, (int)ix->ncells, (int)CH, seg_max, d_tot);
-            hipLaunchKernelGGL(k_cell_scan, dim3(1), dim3(1024), 0, st, cell_cnt, slot_off, (int)nkeys, G, n_slots, qstart, (int)CH);
-            hipLaunchKernelGGL(k_item_scatter, dim3((unsigned)ceil_div(n_items, 256)), dim3(256), 0, st, items, n_items, slot_off, cell_cnt, G, slots, (int)ix->ncells, (int)CH, seg_max, d_tot);
-        } else
-            slots = nullptr;   // one query per slot: slot i = work item i (k_stream_prep)
-        // workspace: candidate layout, lists, keys, ranked pairs; the sample buckets live in their own buffer (k_stream_tau leaves them
-        // clean for the next batch; fresh memory is set to "empty" here)
-        {
-            const size_t need = (size_t)nq * B * sizeof(uint32_t);
-            if (need > ix->w_bmin.cap) {
-                CIS_TRY(ix->w_bmin.reserve(need > (size_t)16 * B * sizeof(uint32_t) ? need : (size_t)16 * B * sizeof(uint32_t)));
-                CIS_CHECK_HIP(hipMemsetAsync(ix->w_bmin.p, 0xff, ix->w_bmin.cap, st));
-            }
-        }
-        const size_t n_i64 = (size_t)(n_items + 1) + (size_t)3 * (nq + 2) + (size_t)(max_slots + 2) + (size_t)(max_slots + 1) * ((stream_slot_bytes() + 7) / 8);
-        const size_t bytes = n_i64 * 8 + (size_t)(nq + 2) * 4 * 4 + (size_t)nq * cap * 4 + (size_t)nq * cap * 8 + (size_t)2 * nq * sp.stride * 8 + 1024;
-        CIS_TRY(ix->w_hits.reserve(bytes));
-        int64_t* cand_start = ix->w_hits.as<int64_t>();
-        int64_t* seg = cand_start + (n_items + 1);
-        unsigned long long* qmin = reinterpret_cast<unsigned long long*>(seg + (nq + 2));
-        unsigned long long* qmax = qmin + (nq + 2);
-        int64_t* rowoff = reinterpret_cast<int64_t*>(qmax + (nq + 2));     // [max_slots + 1]: rows of the slots before each (k_stream_prep)
-        void* sdesc = rowoff + (max_slots + 2);                             // [max_slots] slot records (k_stream_prep)
-        uint64_t* skeys = reinterpret_cast<uint64_t*>(rowoff + (max_slots + 2) + (size_t)(max_slots + 1) * ((stream_slot_bytes() + 7) / 8));   // [nq][cap]
-        uint64_t* sel_keys = skeys + (size_t)nq * cap;                     // [nq][stride]
-        uint64_t* sel_vals = sel_keys + (size_t)nq * sp.stride;
-        uint32_t* surv = reinterpret_cast<uint32_t*>(sel_vals + (size_t)nq * sp.stride);  // [nq][cap]
-        uint32_t* bmin = ix->w_bmin.as<uint32_t>();                        // [nq][B]
-        int* cnt = reinterpret_cast<int*>(surv + (size_t)nq * cap);        // [nq + 2]
-        int* nsel = cnt + (nq + 2);
-        float* tau = reinterpret_cast<float*>(nsel + (nq + 2));
-        int* status = reinterpret_cast<int*>(tau + (nq + 2));
-        // candidate layout + slot records + row offsets + resets: one launch of one workgroup
-        launch_stream_prep(st, items, n_items, item_off, nq, n_cand_all, slots, n_slots, G, M, cand_start, seg, qmin, qmax, cnt, status, rowoff, sdesc, d_tot);
-        // sample: every SS-th row; the k-th smallest of the bucket minima lets about k * SS candidates of a query through -- aim at
-        // ~max(4096, 16 limit) of them, with k >= 8 so that the count is stable (relative spread 1 / sqrt(k))
-        const int64_t per_q = n_cand_all / nq;
-        const int row = 64 * (16 / M);
-        int64_t target = 4096 > 16 * L ? 4096 : 16 * L;
-        if (const char* e = getenv("CIS_STREAM_TARGET")) target = atoll(e) > 0 ? atoll(e) : target;
-        int64_t ss = per_q / row / 4096;            // ~4096 sampled rows per query
-        ss = ss < 8 ? 8 : (ss > 4096 ? 4096 : ss);
-        int64_t kth = target / ss;
-        kth = kth < 8 ? 8 : (kth > B / 4 ? B / 4 : kth);
-        if (ix->force_stream && getenv("CIS_STREAM_SS")) { ss = atoll(getenv("CIS_STREAM_SS")); kth = getenv("CIS_STREAM_K") ? atoll(getenv("CIS_STREAM_K")) : kth; }  // tests
-        // a lane folds `flush` of its sampled rows into one bucket: ~4 B bucket writes per query (a query's sampled rows x 64 lanes / flush)
-        int64_t flush = ceil_div(ceil_div(per_q, (int64_t)row * ss) * 64, (int64_t)4 * B);
-        flush = flush < 1 ? 1 : flush;
-        const int grid = stream_grid(M, G, K, ceil_div(n_cand_all, (int64_t)row) + n_items);
-        launch_stream_scan(M, G, true, grid, st, sdesc, n_slots, rowoff, T32, T, codes, K, tau, bmin, B, (int)ss, (int)flush, surv, cnt, cap);
-        launch_stream_tau(st, bmin, B, (int)kth, nq, tau);
-        CIS_TRY(mark(5));
-        pr.has_scan = true;
-        ix->last_scan_kernel = 5;
-        launch_stream_scan(M, G, false, grid, st, sdesc, n_slots, rowoff, T32, T, codes, K, tau, bmin, B, (int)ss, (int)flush, surv, cnt, cap);
-        CIS_TRY(mark(3));
-        launch_stream_keys(M, st, items, cand_start, seg, item_off, n_items, T, codes, K, surv, cnt, cap, nq, skeys, qmin, qmax);
-        hipLaunchKernelGGL((k_select_topl<true, 1024>), dim3((unsigned)nq), dim3(1024), sp.lds, st, skeys, seg, cand_start, item_off, qmin, qmax, n_items, L, sp.p2,
-                           sp.stride, sel_keys, sel_vals, nsel, (int64_t*)nullptr, (int64_t*)nullptr, (const int*)nullptr, surv, cnt, (int64_t)cap);
-        const int64_t sseq = ++ix->stream_batches;
-        launch_stream_finish(st, sel_keys, sel_vals, nsel, sp.stride, cnt, cap, seg, tau, nq, L, M, items, ids, plan, out.hits, out.ids, out.dists, out.n_found,
-                             out.cells, out.pos, out.visited, status, ix->d_h_totals + 6, sseq);
-        CIS_CHECK_HIP(hipGetLastError());
-        CIS_TRY(mark(4));
-        ix->stats[3] += 1;
-        if (ix->profiling) ix->prof.push_back(pr);
-        // the proof: two words behind a sequence number in pinned memory (this route serves scans of hundreds of microseconds and
-        // more: waiting for their end costs the caller nothing it would not wait for anyway)
-        {
-            const auto t0 = std::chrono::steady_clock::now();
-            bool got = false;
-            while (!got) {
-                if (__atomic_load_n(&ix->h_totals[8], __ATOMIC_ACQUIRE) == sseq) { got = true; break; }
-                if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20)) break;
-            }
-            if (!got) {
-                CIS_CHECK_HIP(hipStreamSynchronize(st));
-                CIS_REQUIRE(__atomic_load_n(&ix->h_totals[8], __ATOMIC_ACQUIRE) == sseq, "the streaming route's status did not arrive");
-            }
-        }
-        if (ix->h_totals[6] == 0 && ix->h_totals[7] == 0) return CIS_OK;
-        // a failed proof (an unlucky sample) or an overflowed list (a crowd of equal codes): the generic path answers the batch
-        ++ix->stream_fallbacks;
-        if (getenv("CIS_STREAM_DEBUG"))
-            fprintf(stderr, "[cis] streaming route: %lld failed proofs, %lld overflowed lists of %d queries -> generic path\n", (long long)ix->h_totals[6], (long long)ix->h_totals[7], nq);
-        ix->stream_off = true;
-        const int saved_stats3 = (int)ix->stats[3];
-        for (int i = 0; i < 3; ++i) ix->stats[i] = 0;  // (the generic pass counts the batch again)
-        (void)saved_stats3;
-        const int rc = search_batch(ix, dQ, q_dtype, nq, quota, L, out, st);
-        ix->stream_off = false;
-        return rc;
+}
+
+// ---- slot list: work items grouped by (coarse cell, chunk) with a counting sort, G per slot -------------------------------------
+struct Slots {
+    int* qctr;     // [8] queue counters, [8] n_slots (first), [9] queue starts, [32] fall-back header (scan3)
+    int* n_slots;
+    int* fhdr;
+    int* slots;    // null: slot i = work item i (SLOTS_NONE)
+    int* fslots;
+    int64_t max_slots;
+};
+enum SlotMode {
+    SLOTS_SORTED,    // the counting sort
+    SLOTS_IDENTITY,  // huge V: slot i = work item i, written out (k_identity_slots)
+    SLOTS_NONE       // one query per slot on the streaming route: no list at all (k_stream_prep counts the slots)
+};
+
+static int build_slots(const Batch& b, SlotMode mode, int G, int64_t CH /* chunks per cell that get their own slot keys */, int seg_max, Slots* s) {
+    cis_index* ix = b.ix;
+    hipStream_t st = b.st;
+    const int64_t n_items = b.n_items;
+    const int64_t nkeys = 2 * ix->ncells * CH;
+    const int64_t max_slots = mode == SLOTS_IDENTITY ? n_items : (n_items + nkeys) / G + nkeys + 2;
+    CIS_TRY(ix->w_order2.reserve((size_t)(64 + 2 * nkeys + 2 * max_slots * G) * sizeof(int)));
+    int* qctr = ix->w_order2.as<int>();
+    int* n_slots = qctr + 8;
+    int* qstart = qctr + 16;
+    int* cell_cnt = qctr + 64;
+    int* slot_off = cell_cnt + nkeys;
+    int* slots = slot_off + nkeys;
+    s->qctr = qctr;
+    s->n_slots = n_slots;
+    s->fhdr = qctr + 32;
+    s->slots = mode == SLOTS_NONE ? nullptr : slots;
+    s->fslots = slots + max_slots * G;
+    s->max_slots = max_slots;
+    if (mode == SLOTS_SORTED) {
+        const int64_t ninit = max_slots * G > nkeys ? max_slots * G : nkeys;
+        hipLaunchKernelGGL(k_slots_init, dim3((unsigned)ceil_div(ninit < 16 ? 16 : ninit, 256)), dim3(256), 0, st, qctr, cell_cnt, (int)nkeys, slots, max_slots * G);
+        hipLaunchKernelGGL(k_item_hist, dim3((unsigned)ceil_div(n_items, 256)), dim3(256), 0, st, b.items, n_items, cell_cnt, (int)ix->ncells, (int)CH, seg_max, b.d_tot);
+        hipLaunchKernelGGL(k_cell_scan, dim3(1), dim3(1024), 0, st, cell_cnt, slot_off, (int)nkeys, G, n_slots, qstart, (int)CH);
+        hipLaunchKernelGGL(k_item_scatter, dim3((unsigned)ceil_div(n_items, 256)), dim3(256), 0, st, b.items, n_items, slot_off, cell_cnt, G, slots, (int)ix->ncells, (int)CH, seg_max, b.d_tot);
+    } else if (mode == SLOTS_IDENTITY) {
+        CIS_CHECK_HIP(hipMemsetAsync(qctr, 0, 64 * sizeof(int), st));
+        hipLaunchKernelGGL(k_identity_slots, dim3((unsigned)ceil_div(n_items < 9 ? 9 : n_items, 256)), dim3(256), 0, st, n_items, G, slots, n_slots, qstart);
     }
-    if (big) {
-        // 4'. every candidate's exact distance; then per query either a radix select of the `limit` best (ranked in LDS
-        // for limit <= 3072, by a stable segmented sort of the selected pairs above) or, when `limit` is of the order
-        // of the candidate count, the stable segmented sort of everything
-        CIS_TRY(mark(2));
-        const int64_t n_cand = n_cand_all;
-        CIS_REQUIRE(n_cand < ((int64_t)1 << 32), "query batch too large for the sorted path");
-        const uint8_t* codes = ix->codes_ptr();
-        const int64_t* ids = ix->ids_ptr();
-        const SelectPlan sp = select_plan(L, nq, n_cand);
-        const int64_t n_sel = sp.select ? (int64_t)nq * sp.stride : 0;
-        size_t sort_tmp = 0;
-        if (!sp.sort_lds)
-            CIS_TRY(cis_seg_sort_u64(nullptr, &sort_tmp, nullptr, nullptr, nullptr, nullptr, sp.select ? n_sel : n_cand, nq, nullptr, nullptr, st));
-        const size_t tmp_bytes = (sort_tmp + 255) & ~(size_t)255;
-        const size_t n_i64 = (size_t)2 * (n_items + 1) + (size_t)6 * (nq + 2);
-        const size_t n_pairs = sp.select ? (size_t)(n_cand + 1) + (size_t)(sp.sort_lds ? 2 : 4) * (n_sel + 1) : (size_t)4 * (n_cand + 1);
-        CIS_TRY(ix->w_hits.reserve(n_i64 * 8 + n_pairs * 8 + tmp_bytes + 256));
-        int64_t* lens = ix->w_hits.as<int64_t>();
-        int64_t* cand_start = lens + (n_items + 1);
-        int64_t* seg = cand_start + (n_items + 1);
-        int64_t* seg_b = seg + (nq + 2);
-        int64_t* seg_e = seg_b + (nq + 2);
-        int* nsel = reinterpret_cast<int*>(seg_e + (nq + 2));
-        unsigned long long* qmin = reinterpret_cast<unsigned long long*>(seg_e + 2 * (nq + 2));
-        unsigned long long* qmax = qmin + (nq + 2);
-        uint64_t* keys_in = reinterpret_cast<uint64_t*>(qmax + (nq + 2));
-        uint64_t* b1 = keys_in + (n_cand + 1);  // full sort: keys_out, vals_in, vals_out; select: sel_keys, sel_vals[, sorted copies]
-        const size_t bl = sp.select ? (size_t)(n_sel + 1) : (size_t)(n_cand + 1);
-        uint64_t* b2 = b1 + bl;
-        uint64_t* b3 = b2 + bl;
-        uint64_t* b4 = b3 + bl;
-        void* tmp = reinterpret_cast<void*>(((uintptr_t)(sp.select ? (sp.sort_lds ? b3 : b3 + 2 * bl) : b4) + 255) & ~(uintptr_t)255);
-        if (n_items > 16384 && !d_tot) {
-            const int64_t ntiles = ceil_div(n_items, CAND_TILE);
-            CIS_TRY(ix->w_tiles.reserve((size_t)(ntiles + 1) * sizeof(int64_t)));
-            int64_t* tile_sums = ix->w_tiles.as<int64_t>();
-            hipLaunchKernelGGL(k_cand_tile_sum, dim3((unsigned)ntiles), dim3(256), 0, st, items, n_items, tile_sums);
-            hipLaunchKernelGGL(k_cand_tile_scan, dim3(1), dim3(1024), 0, st, tile_sums, ntiles);
-            hipLaunchKernelGGL(k_cand_tile_apply, dim3((unsigned)ntiles), dim3(256), 0, st, items, n_items, tile_sums, cand_start);
-            hipLaunchKernelGGL(k_seg_begin, dim3((unsigned)ceil_div(nq + 1, 256)), dim3(256), 0, st, cand_start, item_off, nq, n_items, n_cand, seg,
-                               sp.select ? qmin : (unsigned long long*)nullptr, qmax);
-        } else
+    return CIS_OK;
+}
+
+static int search_batch(cis_index* ix, const void* dQ, int q_dtype, int nq, int64_t quota, int L, const SearchOut& out, hipStream_t st);
+
+// 4''. the HBM-streaming route (lopq_stream.hip): sample -> threshold -> stream -> exact keys of the listed candidates ->
+// ranking (k_select_topl, ties by retrieval index) -> proof; a failed proof hands the batch to the generic path
+static int run_stream(Batch& b, const Route& r) {
+    cis_index* ix = b.ix;
+    hipStream_t st = b.st;
+    const int K = ix->m->K, M = ix->m->M, nq = b.nq, L = b.L;
+    const int64_t n_items = b.n_items, n_cand_all = b.n_cand_all;
+    const SearchOut& out = b.out;
+    CIS_TRY(mark(b, 2));
+    const uint8_t* codes = ix->codes_ptr();
+    const int64_t* ids = ix->ids_ptr();
+    // queries per slot: a pair costs the launch what one query costs (the codes are the bound), four cost ~1.45 of a pair
+    // (profiles/r06_stream_probe.txt) -- worth it when the queries share their cells, i.e. the quota covers most of the index
+    const bool shared_cells = b.quota >= ix->n_total / 2;
+    const int G = (nq >= 3 && shared_cells && stream_max_group() >= 4) ? 4 : (nq >= 2 ? 2 : 1);
+    const int cap = STREAM_CAP, B = STREAM_B;
+    const SelectPlan sp = select_plan(L, nq, (int64_t)nq * cap);
+    CIS_REQUIRE(sp.sort_lds, "streaming route: limit above the LDS-ranked range");
+    // slots: the work items of one chunk of one cell, G per slot (the slot builder of the scan kernels); one query per slot:
+    // slot i = work item i (k_stream_prep)
+    int64_t CH = ceil_div(ix->max_cell > 0 ? ix->max_cell : 1, (int64_t)r.seg_max);
+    CH = CH < 1 ? 1 : (CH > 16 ? 16 : CH);
+    Slots sl;
+    CIS_TRY(build_slots(b, G > 1 ? SLOTS_SORTED : SLOTS_NONE, G, CH, r.seg_max, &sl));
+    const int64_t max_slots = sl.max_slots;
+    // workspace: candidate layout, lists, keys, ranked pairs; the sample buckets live in their own buffer (k_stream_tau leaves them
+    // clean for the next batch; fresh memory is set to "empty" here)
+    {
+        const size_t need = (size_t)nq * B * sizeof(uint32_t);
+        if (need > ix->w_bmin.cap) {
+            CIS_TRY(ix->w_bmin.reserve(need > (size_t)16 * B * sizeof(uint32_t) ? need : (size_t)16 * B * sizeof(uint32_t)));
+            CIS_CHECK_HIP(hipMemsetAsync(ix->w_bmin.p, 0xff, ix->w_bmin.cap, st));
+        }
+    }
+    const size_t n_i64 = (size_t)(n_items + 1) + (size_t)3 * (nq + 2) + (size_t)(max_slots + 2) + (size_t)(max_slots + 1) * ((stream_slot_bytes() + 7) / 8);
+    const size_t bytes = n_i64 * 8 + (size_t)(nq + 2) * 4 * 4 + (size_t)nq * cap * 4 + (size_t)nq * cap * 8 + (size_t)2 * nq * sp.stride * 8 + 1024;
+    CIS_TRY(ix->w_hits.reserve(bytes));
+    int64_t* cand_start = ix->w_hits.as<int64_t>();
+    int64_t* seg = cand_start + (n_items + 1);
+    unsigned long long* qmin = reinterpret_cast<unsigned long long*>(seg + (nq + 2));
+    unsigned long long* qmax = qmin + (nq + 2);
+    int64_t* rowoff = reinterpret_cast<int64_t*>(qmax + (nq + 2));     // [max_slots + 1]: rows of the slots before each (k_stream_prep)
+    void* sdesc = rowoff + (max_slots + 2);                             // [max_slots] slot records (k_stream_prep)
+    uint64_t* skeys = reinterpret_cast<uint64_t*>(rowoff + (max_slots + 2) + (size_t)(max_slots + 1) * ((stream_slot_bytes() + 7) / 8));   // [nq][cap]
+    uint64_t* sel_keys = skeys + (size_t)nq * cap;                     // [nq][stride]
+    uint64_t* sel_vals = sel_keys + (size_t)nq * sp.stride;
+    uint32_t* surv = reinterpret_cast<uint32_t*>(sel_vals + (size_t)nq * sp.stride);  // [nq][cap]
+    uint32_t* bmin = ix->w_bmin.as<uint32_t>();                        // [nq][B]
+    int* cnt = reinterpret_cast<int*>(surv + (size_t)nq * cap);        // [nq + 2]
+    int* nsel = cnt + (nq + 2);
+    float* tau = reinterpret_cast<float*>(nsel + (nq + 2));
+    int* status = reinterpret_cast<int*>(tau + (nq + 2));
+    // candidate layout + slot records + row offsets + resets: one launch of one workgroup
+    launch_stream_prep(st, b.items, n_items, b.item_off, nq, n_cand_all, sl.slots, sl.n_slots, G, M, cand_start, seg, qmin, qmax, cnt, status, rowoff, sdesc, b.d_tot);
+    // sample: every SS-th row; the k-th smallest of the bucket minima lets about k * SS candidates of a query through -- aim at
+    // ~max(4096, 16 limit) of them, with k >= 8 so that the count is stable (relative spread 1 / sqrt(k))
+    const int64_t per_q = n_cand_all / nq;
+    const int row = 64 * (16 / M);
+    int64_t target = 4096 > 16 * L ? 4096 : 16 * L;
+    if (const char* e = getenv("CIS_STREAM_TARGET")) target = atoll(e) > 0 ? atoll(e) : target;
+    int64_t ss = per_q / row / 4096;            // ~4096 sampled rows per query
+    ss = ss < 8 ? 8 : (ss > 4096 ? 4096 : ss);
+    int64_t kth = target / ss;
+    kth = kth < 8 ? 8 : (kth > B / 4 ? B / 4 : kth);
+    if (ix->force_stream && getenv("CIS_STREAM_SS")) { ss = atoll(getenv("CIS_STREAM_SS")); kth = getenv("CIS_STREAM_K") ? atoll(getenv("CIS_STREAM_K")) : kth; }  // tests
+    // a lane folds `flush` of its sampled rows into one bucket: ~4 B bucket writes per query (a query's sampled rows x 64 lanes / flush)
+    int64_t flush = ceil_div(ceil_div(per_q, (int64_t)row * ss) * 64, (int64_t)4 * B);
+    flush = flush < 1 ? 1 : flush;
+    const int grid = stream_grid(M, G, K, ceil_div(n_cand_all, (int64_t)row) + n_items);
+    launch_stream_scan(M, G, true, grid, st, sdesc, sl.n_slots, rowoff, b.T32, b.T, codes, K, tau, bmin, B, (int)ss, (int)flush, surv, cnt, cap);
+    launch_stream_tau(st, bmin, B, (int)kth, nq, tau);
+    CIS_TRY(mark(b, 5));
+    b.pr.has_scan = true;
+    ix->last_scan_kernel = 5;
+    launch_stream_scan(M, G, false, grid, st, sdesc, sl.n_slots, rowoff, b.T32, b.T, codes, K, tau, bmin, B, (int)ss, (int)flush, surv, cnt, cap);
+    CIS_TRY(mark(b, 3));
+    launch_stream_keys(M, st, b.items, cand_start, seg, b.item_off, n_items, b.T, codes, K, surv, cnt, cap, nq, skeys, qmin, qmax);
+    hipLaunchKernelGGL((k_select_topl<true, 1024>), dim3((unsigned)nq), dim3(1024), sp.lds, st, skeys, seg, cand_start, b.item_off, qmin, qmax, n_items, L, sp.p2,
+                       sp.stride, sel_keys, sel_vals, nsel, (int64_t*)nullptr, (int64_t*)nullptr, (const int*)nullptr, surv, cnt, (int64_t)cap);
+    const int64_t sseq = ++ix->stream_batches;
+    launch_stream_finish(st, sel_keys, sel_vals, nsel, sp.stride, cnt, cap, seg, tau, nq, L, M, b.items, ids, b.plan, out.hits, out.ids, out.dists, out.n_found,
+                         out.cells, out.pos, out.visited, status, ix->d_h_totals + 6, sseq);
+    CIS_CHECK_HIP(hipGetLastError());
+    CIS_TRY(mark(b, 4));
+    ix->stats[3] += 1;
+    if (ix->profiling) ix->prof.push_back(b.pr);
+    // the proof: two words behind a sequence number in pinned memory (this route serves scans of hundreds of microseconds and
+    // more: waiting for their end costs the caller nothing it would not wait for anyway)
+    {
+        const auto t0 = std::chrono::steady_clock::now();
+        bool got = false;
+        while (!got) {
+            if (__atomic_load_n(&ix->h_totals[8], __ATOMIC_ACQUIRE) == sseq) { got = true; break; }
+            if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20)) break;
+        }
+        if (!got) {
+            CIS_CHECK_HIP(hipStreamSynchronize(st));
+            CIS_REQUIRE(__atomic_load_n(&ix->h_totals[8], __ATOMIC_ACQUIRE) == sseq, "the streaming route's status did not arrive");
+        }
+    }
+    if (ix->h_totals[6] == 0 && ix->h_totals[7] == 0) return CIS_OK;
+    // a failed proof (an unlucky sample) or an overflowed list (a crowd of equal codes): the generic path answers the batch
+    ++ix->stream_fallbacks;
+    if (getenv("CIS_STREAM_DEBUG"))
+        fprintf(stderr, "[cis] streaming route: %lld failed proofs, %lld overflowed lists of %d queries -> generic path\n", (long long)ix->h_totals[6], (long long)ix->h_totals[7], nq);
+    ix->stream_off = true;
+    for (int i = 0; i < 3; ++i) ix->stats[i] = 0;  // (the generic pass counts the batch again)
+    const int rc = search_batch(ix, b.dQ, b.q_dtype, nq, b.quota, L, out, st);
+    ix->stream_off = false;
+    return rc;
+}
+
+// CIS_TINY_DEBUG: counters and phase clocks of k_tiny_select, read back after the launch
+static int dump_tiny_debug(const Batch& b, const unsigned int* dbg, int tch, int ncmax) {
+    const int nq = b.nq;
+    unsigned int hd[24];
+    CIS_CHECK_HIP(hipMemcpyAsync(hd, dbg, 96, hipMemcpyDeviceToHost, b.st));
+    CIS_CHECK_HIP(hipStreamSynchronize(b.st));
+    fprintf(stderr, "[tiny] queries %u  flagged %u  survivors/query %.1f  mean s* %.1f  (pool %d B, ncmax %d; tables/query %.1f, items/query %.1f)\n", hd[0], hd[1],
+            hd[0] ? (double)hd[2] / hd[0] : 0.0, hd[0] ? (double)hd[3] / hd[0] : 0.0, tch, ncmax, (double)b.n_tabs / nq, (double)b.n_items / nq);
+    // 100 MHz ticks of thread 0 per phase, summed over all queries: us per query
+    fprintf(stderr, "[tiny] us/query: top %.1f layout %.1f sample %.1f lookups %.1f rows %.1f tables %.1f last lookups %.1f hist+gather %.1f exact %.1f sums+sort %.1f out %.1f\n",
+            hd[4] / 100.0 / nq, hd[5] / 100.0 / nq, hd[6] / 100.0 / nq, hd[7] / 100.0 / nq, hd[8] / 100.0 / nq, hd[9] / 100.0 / nq,
+            hd[10] / 100.0 / nq, hd[11] / 100.0 / nq, hd[12] / 100.0 / nq, hd[13] / 100.0 / nq, hd[14] / 100.0 / nq);
+    fprintf(stderr, "[tiny] half tables with a candidate: %.1f per query; centroid loads %.1f us/query\n", (double)hd[15] / nq, hd[16] / 100.0 / nq);
+    return CIS_OK;
+}
+
+// 4'. every candidate's exact distance; then per query either a radix select of the `limit` best (ranked in LDS
+// for limit <= 3072, by a stable segmented sort of the selected pairs above) or, when `limit` is of the order
+// of the candidate count, the stable segmented sort of everything
+static int run_all_candidates(Batch& b, const Route& r) {
+    cis_index* ix = b.ix;
+    cis_model* m = ix->m;
+    hipStream_t st = b.st;
+    const int K = m->K, M = m->M, h = m->h, nq = b.nq, L = b.L;
+    const int64_t quota = b.quota, n_items = b.n_items;
+    const WorkItem* items = b.items;
+    const int64_t *item_off = b.item_off, *tab_off = b.tab_off, *d_tot = b.d_tot;
+    double *T = b.T, *px_buf = b.px_buf;
+    const bool direct = r.direct, tiny_cells = r.tiny_cells;
+    const SearchOut& out = b.out;
+    CIS_TRY(mark(b, 2));
+    const int64_t n_cand = b.n_cand_all;
+    CIS_REQUIRE(n_cand < ((int64_t)1 << 32), "query batch too large for the sorted path");
+    const uint8_t* codes = ix->codes_ptr();
+    const int64_t* ids = ix->ids_ptr();
+    const SelectPlan sp = select_plan(L, nq, n_cand);
+    const int64_t n_sel = sp.select ? (int64_t)nq * sp.stride : 0;
+    size_t sort_tmp = 0;
+    if (!sp.sort_lds)
+        CIS_TRY(cis_seg_sort_u64(nullptr, &sort_tmp, nullptr, nullptr, nullptr, nullptr, sp.select ? n_sel : n_cand, nq, nullptr, nullptr, st));
+    const size_t tmp_bytes = (sort_tmp + 255) & ~(size_t)255;
+    const size_t n_i64 = (size_t)2 * (n_items + 1) + (size_t)6 * (nq + 2);
+    const size_t n_pairs = sp.select ? (size_t)(n_cand + 1) + (size_t)(sp.sort_lds ? 2 : 4) * (n_sel + 1) : (size_t)4 * (n_cand + 1);
+    CIS_TRY(ix->w_hits.reserve(n_i64 * 8 + n_pairs * 8 + tmp_bytes + 256));
+    int64_t* lens = ix->w_hits.as<int64_t>();
+    int64_t* cand_start = lens + (n_items + 1);
+    int64_t* seg = cand_start + (n_items + 1);
+    int64_t* seg_b = seg + (nq + 2);
+    int64_t* seg_e = seg_b + (nq + 2);
+    int* nsel = reinterpret_cast<int*>(seg_e + (nq + 2));
+    unsigned long long* qmin = reinterpret_cast<unsigned long long*>(seg_e + 2 * (nq + 2));
+    unsigned long long* qmax = qmin + (nq + 2);
+    uint64_t* keys_in = reinterpret_cast<uint64_t*>(qmax + (nq + 2));
+    uint64_t* b1 = keys_in + (n_cand + 1);  // full sort: keys_out, vals_in, vals_out; select: sel_keys, sel_vals[, sorted copies]
+    const size_t bl = sp.select ? (size_t)(n_sel + 1) : (size_t)(n_cand + 1);
+    uint64_t* b2 = b1 + bl;
+    uint64_t* b3 = b2 + bl;
+    uint64_t* b4 = b3 + bl;
+    void* tmp = reinterpret_cast<void*>(((uintptr_t)(sp.select ? (sp.sort_lds ? b3 : b3 + 2 * bl) : b4) + 255) & ~(uintptr_t)255);
+    if (n_items > 16384 && !d_tot) {
+        const int64_t ntiles = ceil_div(n_items, CAND_TILE);
+        CIS_TRY(ix->w_tiles.reserve((size_t)(ntiles + 1) * sizeof(int64_t)));
+        int64_t* tile_sums = ix->w_tiles.as<int64_t>();
+        hipLaunchKernelGGL(k_cand_tile_sum, dim3((unsigned)ntiles), dim3(256), 0, st, items, n_items, tile_sums);
+        hipLaunchKernelGGL(k_cand_tile_scan, dim3(1), dim3(1024), 0, st, tile_sums, ntiles);
+        hipLaunchKernelGGL(k_cand_tile_apply, dim3((unsigned)ntiles), dim3(256), 0, st, items, n_items, tile_sums, cand_start);
+        hipLaunchKernelGGL(k_seg_begin, dim3((unsigned)ceil_div(nq + 1, 256)), dim3(256), 0, st, cand_start, item_off, nq, n_items, n_cand, seg,
+                           sp.select ? qmin : (unsigned long long*)nullptr, qmax);
+    } else
         hipLaunchKernelGGL(k_cand_layout, dim3(1), dim3(1024), 0, st, items, n_items, item_off, nq, n_cand, cand_start, seg,
                            sp.select ? qmin : (unsigned long long*)nullptr, qmax, d_tot);
-        const uint64_t *rk = nullptr, *rv = nullptr;  // ranked pairs
-        if (!sp.select) {
-            uint64_t *keys_out = b1, *vals_in = b2, *vals_out = b3;
-            if (n_items > 0) {
-                if (!(direct && launch_adc_direct(M, K, m->w, st, items, cand_start, seg, item_off, px_buf, m->d_subs, codes, h, nq, keys_in, vals_in, nullptr, nullptr)))
-                    launch_adc_all(n_items, st, items, cand_start, T, codes, M, K, keys_in, vals_in, nullptr, nullptr, nullptr, seg, item_off, nq, tiny_cells);
-                size_t b = tmp_bytes;
-                CIS_TRY(cis_seg_sort_u64(tmp, &b, keys_in, keys_out, vals_in, vals_out, n_cand, nq, seg, seg + 1, st));
-            }
-            rk = keys_out; rv = vals_out;
-        } else {
-            uint64_t *sel_keys = b1, *sel_vals = b2;
-            // tiny cells, limit a small share of the quota: byte-table prefilter + exact keys of the survivors in ONE kernel per
-            // query (k_tiny_select); the queries it flags go through the exact kernels below
-            int* fbflag = nullptr;
-            // (measured at V = 2048, 8192 queries, limit 100: quota 10000 5.16 against 6.35 ms for the exact kernels, quota 1000 2.19 against
-            // 1.36 -- the sample, the row copies and the sort are fixed costs per query: from 8192 candidates on)
-            const int64_t tiny_min_quota = getenv("CIS_TINY_MIN_QUOTA") ? atoll(getenv("CIS_TINY_MIN_QUOTA")) : 8192;
-            if (direct && sp.sort_lds && n_items > 0 && (int64_t)L * 8 <= (int64_t)quota && (int64_t)quota >= tiny_min_quota && !getenv("CIS_NO_TINY")) {
-                int ncmax = 0;
-                const int tch = tiny_pool(M, K, m->w, h, L, (int64_t)quota + ix->max_cell, &ncmax);  // bytes of the per-query pool
-                if (tch > 0) {
-                    fbflag = nsel + (nq + 2);
-                    static const bool tiny_dbg = getenv("CIS_TINY_DEBUG") != nullptr;
-                    unsigned int* dbg = nullptr;
-                    if (tiny_dbg) {
-                        CIS_TRY(ix->w_slack.reserve(128));
-                        dbg = ix->w_slack.as<unsigned int>();
-                        CIS_CHECK_HIP(hipMemsetAsync(dbg, 0, 96, st));
-                    }
-                    if (!launch_tiny(M, m->w, st, items, cand_start, seg, item_off, tab_off, plan, px_buf, m->d_subs, codes, h, nq, L, ncmax, tch,
-                                     sp.stride, sel_keys, sel_vals, nsel, keys_in, qmin, qmax, fbflag, T32, dbg))
-                        fbflag = nullptr;
-                    else if (tiny_dbg) {
-                        unsigned int hd[24];
-                        CIS_CHECK_HIP(hipMemcpyAsync(hd, dbg, 96, hipMemcpyDeviceToHost, st));
-                        CIS_CHECK_HIP(hipStreamSynchronize(st));
-                        fprintf(stderr, "[tiny] queries %u  flagged %u  survivors/query %.1f  mean s* %.1f  (pool %d B, ncmax %d; tables/query %.1f, items/query %.1f)\n", hd[0], hd[1],
-                                hd[0] ? (double)hd[2] / hd[0] : 0.0, hd[0] ? (double)hd[3] / hd[0] : 0.0, tch, ncmax, (double)n_tabs / nq, (double)n_items / nq);
-                        // 100 MHz ticks of thread 0 per phase, summed over all queries: us per query
-                        fprintf(stderr, "[tiny] us/query: top %.1f layout %.1f sample %.1f lookups %.1f rows %.1f tables %.1f last lookups %.1f hist+gather %.1f exact %.1f sums+sort %.1f out %.1f\n",
-                                hd[4] / 100.0 / nq, hd[5] / 100.0 / nq, hd[6] / 100.0 / nq, hd[7] / 100.0 / nq, hd[8] / 100.0 / nq, hd[9] / 100.0 / nq,
-                                hd[10] / 100.0 / nq, hd[11] / 100.0 / nq, hd[12] / 100.0 / nq, hd[13] / 100.0 / nq, hd[14] / 100.0 / nq);
-                        fprintf(stderr, "[tiny] half tables with a candidate: %.1f per query; centroid loads %.1f us/query\n", (double)hd[15] / nq, hd[16] / 100.0 / nq);
-                    }
+    const uint64_t *rk = nullptr, *rv = nullptr;  // ranked pairs
+    if (!sp.select) {
+        uint64_t *keys_out = b1, *vals_in = b2, *vals_out = b3;
+        if (n_items > 0) {
+            if (!(direct && launch_adc_direct(M, K, m->w, st, items, cand_start, seg, item_off, px_buf, m->d_subs, codes, h, nq, keys_in, vals_in, nullptr, nullptr)))
+                launch_adc_all(n_items, st, items, cand_start, T, codes, M, K, keys_in, vals_in, nullptr, nullptr, nullptr, seg, item_off, nq, tiny_cells);
+            size_t bb = tmp_bytes;
+            CIS_TRY(cis_seg_sort_u64(tmp, &bb, keys_in, keys_out, vals_in, vals_out, n_cand, nq, seg, seg + 1, st));
+        }
+        rk = keys_out; rv = vals_out;
+    } else {
+        uint64_t *sel_keys = b1, *sel_vals = b2;
+        // tiny cells, limit a small share of the quota: byte-table prefilter + exact keys of the survivors in ONE kernel per
+        // query (k_tiny_select); the queries it flags go through the exact kernels below
+        int* fbflag = nullptr;
+        // (measured at V = 2048, 8192 queries, limit 100: quota 10000 5.16 against 6.35 ms for the exact kernels, quota 1000 2.19 against
+        // 1.36 -- the sample, the row copies and the sort are fixed costs per query: from 8192 candidates on)
+        const int64_t tiny_min_quota = getenv("CIS_TINY_MIN_QUOTA") ? atoll(getenv("CIS_TINY_MIN_QUOTA")) : 8192;
+        if (direct && sp.sort_lds && n_items > 0 && (int64_t)L * 8 <= (int64_t)quota && (int64_t)quota >= tiny_min_quota && !getenv("CIS_NO_TINY")) {
+            int ncmax = 0;
+            const int tch = tiny_pool(M, K, m->w, h, L, (int64_t)quota + ix->max_cell, &ncmax);  // bytes of the per-query pool
+            if (tch > 0) {
+                fbflag = nsel + (nq + 2);
+                static const bool tiny_dbg = getenv("CIS_TINY_DEBUG") != nullptr;
+                unsigned int* dbg = nullptr;
+                if (tiny_dbg) {
+                    CIS_TRY(ix->w_slack.reserve(128));
+                    dbg = ix->w_slack.as<unsigned int>();
+                    CIS_CHECK_HIP(hipMemsetAsync(dbg, 0, 96, st));
                 }
-            }
-            if (fbflag) {
-            } else
-            if (n_items > 0 && !(direct && launch_adc_direct(M, K, m->w, st, items, cand_start, seg, item_off, px_buf, m->d_subs, codes, h, nq, keys_in, nullptr, qmin, qmax)))
-                launch_adc_all(n_items, st, items, cand_start, T, codes, M, K, keys_in, nullptr, qmin, qmax, d_tot, seg, item_off, nq, tiny_cells);
-            if (sp.sort_lds) {
-                // fewer queries than CUs: one large workgroup per query walks its keys faster; else two 512-thread ones per CU
-                if (nq <= 256)
-                    hipLaunchKernelGGL((k_select_topl<true, 1024>), dim3((unsigned)nq), dim3(1024), sp.lds, st, keys_in, seg, cand_start, item_off,
-                                       qmin, qmax, n_items, L, sp.p2, sp.stride, sel_keys, sel_vals, nsel, (int64_t*)nullptr, (int64_t*)nullptr,
-                                       (const int*)fbflag);
-                else
-                    hipLaunchKernelGGL((k_select_topl<true, 512>), dim3((unsigned)nq), dim3(512), sp.lds, st, keys_in, seg, cand_start, item_off,
-                                       qmin, qmax, n_items, L, sp.p2, sp.stride, sel_keys, sel_vals, nsel, (int64_t*)nullptr, (int64_t*)nullptr,
-                                       (const int*)fbflag);
-                rk = sel_keys; rv = sel_vals;
-            } else {
-                uint64_t *srt_keys = b3, *srt_vals = b3 + bl;
-                if (nq <= 256)
-                    hipLaunchKernelGGL((k_select_topl<false, 1024>), dim3((unsigned)nq), dim3(1024), sp.lds, st, keys_in, seg, cand_start, item_off,
-                                       qmin, qmax, n_items, L, sp.p2, sp.stride, sel_keys, sel_vals, nsel, seg_b, seg_e, (const int*)nullptr);
-                else
-                    hipLaunchKernelGGL((k_select_topl<false, 512>), dim3((unsigned)nq), dim3(512), sp.lds, st, keys_in, seg, cand_start, item_off,
-                                       qmin, qmax, n_items, L, sp.p2, sp.stride, sel_keys, sel_vals, nsel, seg_b, seg_e, (const int*)nullptr);
-                size_t b = tmp_bytes;
-                CIS_TRY(cis_seg_sort_u64(tmp, &b, sel_keys, srt_keys, sel_vals, srt_vals, n_sel, nq, seg_b, seg_e, st));
-                rk = srt_keys; rv = srt_vals;
+                if (!launch_tiny(M, m->w, st, items, cand_start, seg, item_off, tab_off, b.plan, px_buf, m->d_subs, codes, h, nq, L, ncmax, tch,
+                                 sp.stride, sel_keys, sel_vals, nsel, keys_in, qmin, qmax, fbflag, b.T32, dbg))
+                    fbflag = nullptr;
+                else if (tiny_dbg)
+                    CIS_TRY(dump_tiny_debug(b, dbg, tch, ncmax));
             }
         }
-        CIS_TRY(mark(3));
-        hipLaunchKernelGGL(k_emit_sorted, dim3((unsigned)ceil_div(L, 1024) < 64 ? (unsigned)ceil_div(L, 1024) : 64, (unsigned)nq), dim3(256), 0, st,
-                           rk, rv, seg, sp.select ? nsel : (const int*)nullptr, sp.stride, items, ids, nq, L, out.hits, out.ids, out.dists,
-                           out.n_found, out.cells, out.pos);
-        if (out.visited)
-            hipLaunchKernelGGL(k_copy_visited, dim3((unsigned)ceil_div(nq, 256)), dim3(256), 0, st, plan, nq, out.visited);
-        CIS_CHECK_HIP(hipGetLastError());
-        CIS_TRY(mark(4));
-        if (ix->profiling) ix->prof.push_back(pr);
-        return CIS_OK;
-    }
-    // 4. ADC scan + block top-k
-    CIS_TRY(mark(2));
-    if (n_items > 0) {
-        pr.has_scan = true;
-        const uint8_t* codes = ix->codes_ptr();
-        const int64_t* ids = ix->ids_ptr();
-        cis_hit* hits = ix->w_hits.as<cis_hit>();
-        int* hitn = ix->w_hitn.as<int>();
-        if (fast) {
-            // slot list: work items grouped by coarse cell (counting sort; skipped for huge V), G per slot
-            const bool sort_items = ix->ncells <= 65536;
-            // k_adc_scan5 (round 5): where the sampled form k_adc_scan4 would run -- one threshold per query for the whole batch
-            // instead of one per slot, eight queries per slot.  MEASURED AND LEFT OFF (profiles/r05g_*, r05h_*: C4 sample 64 + thresholds 17 +
-            // main pass 200 + check 12 us against 231 us for the whole of k_adc_scan4, and a merge of 134 instead of 76 us for the longer
-            // lists; both pipes ~40 % busy at three workgroups per CU: the loop is bound by latency, not by instructions).  CIS_SCAN5=1
-            // routes large batches to it, scan mode 7 forces it (tests: every search test passes on it).
-            static const int env_s5 = getenv("CIS_SCAN5") ? atoi(getenv("CIS_SCAN5")) : 0;
-            const bool use5 = use3 && geom3.two_pass == 2 && scan5_supported(M, K, L) && (ix->force_scan5 || (env_s5 != 0 && !ix->force_scan3 && L <= 128));
-            const int G = use5 ? 8 : (use3 ? geom3.G : geom.G);
-            // chunks per cell that get their own slot keys: what the largest cell needs (all shards' sizes bound this shard's)
-            int64_t CH = use3 ? ceil_div(ix->max_cell > 0 ? ix->max_cell : 1, (int64_t)seg_max) : 1;
-            CH = CH < 1 ? 1 : (CH > 16 ? 16 : CH);
-            const int64_t nkeys = 2 * ix->ncells * CH;
-            const int64_t max_slots = sort_items ? (n_items + nkeys) / G + nkeys + 2 : n_items;
-            CIS_TRY(ix->w_order2.reserve((size_t)(64 + 2 * nkeys + 2 * max_slots * G) * sizeof(int)));
-            int* qctr = ix->w_order2.as<int>();  // [8] queue counters, [8] n_slots (first), [9] queue starts, [32] fall-back header (scan3)
-            int* n_slots = qctr + 8;
-            int* qstart = qctr + 16;
-            int* fhdr = qctr + 32;
-            int* cell_cnt = qctr + 64;
-            int* slot_off = cell_cnt + nkeys;
-            int* slots = slot_off + nkeys;
-            int* fslots = slots + max_slots * G;
-            if (sort_items) {
-                const int64_t ninit = max_slots * G > nkeys ? max_slots * G : nkeys;
-                hipLaunchKernelGGL(k_slots_init, dim3((unsigned)ceil_div(ninit < 16 ? 16 : ninit, 256)), dim3(256), 0, st, qctr,
-                                   cell_cnt, (int)nkeys, slots, max_slots * G);
-                hipLaunchKernelGGL(k_item_hist, dim3((unsigned)ceil_div(n_items, 256)), dim3(256), 0, st, items, n_items, cell_cnt,
-                                   (int)ix->ncells, (int)CH, seg_max);
-                hipLaunchKernelGGL(k_cell_scan, dim3(1), dim3(1024), 0, st, cell_cnt, slot_off, (int)nkeys, G, n_slots, qstart, (int)CH);
-                hipLaunchKernelGGL(k_item_scatter, dim3((unsigned)ceil_div(n_items, 256)), dim3(256), 0, st, items, n_items,
-                                   slot_off, cell_cnt, G, slots, (int)ix->ncells, (int)CH, seg_max);
-            } else {
-                CIS_CHECK_HIP(hipMemsetAsync(qctr, 0, 64 * sizeof(int), st));
-                hipLaunchKernelGGL(k_identity_slots, dim3((unsigned)ceil_div(n_items < 9 ? 9 : n_items, 256)), dim3(256), 0, st, n_items, G,
-                                   slots, n_slots, qstart);
-            }
-            CIS_TRY(mark(5));
-            ix->last_scan_kernel = use5 ? 6 : (use3 ? (geom3.two_pass == 2 ? 4 : 3) : 2);  // 4: the sampled single-pass form k_adc_scan4 does the work (k_adc_scan3 only its fall-back slots)
-            if (use5) {
-                CIS_TRY(ix->w_s5.reserve(scan5_workspace_bytes(nq)));
-                launch_scan5(M, geom3, n_items, nq, st, items, tabs, slots, n_slots, plan, T, T32, codes, K, L, qctr, ix->w_hits.as<uint64_t>(), hitn,
-                             ix->w_slack.as<float>(), qbound, fhdr, fslots, ix->w_s5.p, nullptr);
-            } else
-            if (use3) {
-                Scan3Geom g3 = geom3;
-                // M = 16 on the sampled form: the saturating scale of k_adc_scan4 (sums of the near candidates at this fraction of the entry cap)
-                const float sat16 = getenv("CIS_S4_SAT") ? (float)atof(getenv("CIS_S4_SAT")) : 0.75f;
-                if (M == 16 && g3.two_pass == 2) g3.sat = sat16;
-                launch_scan3(M, g3, n_items, st, items, tabs, slots, n_slots, T, T32, codes, K, L, qctr, ix->w_hits.as<uint64_t>(), hitn, ix->w_slack.as<float>(), qbound, fhdr, fslots);
-                if (g3.sat > 0.f && ix->h_totals)  // (slots, fall-back slots) for the back-off above
-                    CIS_CHECK_HIP(hipMemcpyAsync(&ix->h_totals[4], qctr + 9, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-            }
+        if (fbflag) {
+        } else
+        if (n_items > 0 && !(direct && launch_adc_direct(M, K, m->w, st, items, cand_start, seg, item_off, px_buf, m->d_subs, codes, h, nq, keys_in, nullptr, qmin, qmax)))
+            launch_adc_all(n_items, st, items, cand_start, T, codes, M, K, keys_in, nullptr, qmin, qmax, d_tot, seg, item_off, nq, tiny_cells);
+        if (sp.sort_lds) {
+            // fewer queries than CUs: one large workgroup per query walks its keys faster; else two 512-thread ones per CU
+            if (nq <= 256)
+                hipLaunchKernelGGL((k_select_topl<true, 1024>), dim3((unsigned)nq), dim3(1024), sp.lds, st, keys_in, seg, cand_start, item_off,
+                                   qmin, qmax, n_items, L, sp.p2, sp.stride, sel_keys, sel_vals, nsel, (int64_t*)nullptr, (int64_t*)nullptr,
+                                   (const int*)fbflag);
             else
-                launch_scan2(M, geom, n_items, st, items, slots, n_slots, T, T32, codes, ids, K, L, qctr, ix->w_hits.as<uint64_t>(), hitn, qbound);
+                hipLaunchKernelGGL((k_select_topl<true, 512>), dim3((unsigned)nq), dim3(512), sp.lds, st, keys_in, seg, cand_start, item_off,
+                                   qmin, qmax, n_items, L, sp.p2, sp.stride, sel_keys, sel_vals, nsel, (int64_t*)nullptr, (int64_t*)nullptr,
+                                   (const int*)fbflag);
+            rk = sel_keys; rv = sel_vals;
+        } else {
+            uint64_t *srt_keys = b3, *srt_vals = b3 + bl;
+            if (nq <= 256)
+                hipLaunchKernelGGL((k_select_topl<false, 1024>), dim3((unsigned)nq), dim3(1024), sp.lds, st, keys_in, seg, cand_start, item_off,
+                                   qmin, qmax, n_items, L, sp.p2, sp.stride, sel_keys, sel_vals, nsel, seg_b, seg_e, (const int*)nullptr);
+            else
+                hipLaunchKernelGGL((k_select_topl<false, 512>), dim3((unsigned)nq), dim3(512), sp.lds, st, keys_in, seg, cand_start, item_off,
+                                   qmin, qmax, n_items, L, sp.p2, sp.stride, sel_keys, sel_vals, nsel, seg_b, seg_e, (const int*)nullptr);
+            size_t bb = tmp_bytes;
+            CIS_TRY(cis_seg_sort_u64(tmp, &bb, sel_keys, srt_keys, sel_vals, srt_vals, n_sel, nq, seg_b, seg_e, st));
+            rk = srt_keys; rv = srt_vals;
         }
-        else {
-            CIS_TRY(mark(5));
+    }
+    CIS_TRY(mark(b, 3));
+    hipLaunchKernelGGL(k_emit_sorted, dim3((unsigned)ceil_div(L, 1024) < 64 ? (unsigned)ceil_div(L, 1024) : 64, (unsigned)nq), dim3(256), 0, st,
+                       rk, rv, seg, sp.select ? nsel : (const int*)nullptr, sp.stride, items, ids, nq, L, out.hits, out.ids, out.dists,
+                       out.n_found, out.cells, out.pos);
+    if (out.visited)
+        hipLaunchKernelGGL(k_copy_visited, dim3((unsigned)ceil_div(nq, 256)), dim3(256), 0, st, b.plan, nq, out.visited);
+    CIS_CHECK_HIP(hipGetLastError());
+    CIS_TRY(mark(b, 4));
+    if (ix->profiling) ix->prof.push_back(b.pr);
+    return CIS_OK;
+}
+
+// 4. ADC scan + block top-k through the slot list
+static int run_fast_scan(Batch& b, const Route& r) {
+    cis_index* ix = b.ix;
+    hipStream_t st = b.st;
+    const int K = ix->m->K, M = ix->m->M, nq = b.nq, L = b.L;
+    const int64_t n_items = b.n_items;
+    const uint8_t* codes = ix->codes_ptr();
+    const int64_t* ids = ix->ids_ptr();
+    int* hitn = ix->w_hitn.as<int>();
+    const bool use3 = r.use3;
+    const Scan3Geom& geom3 = r.geom3;
+    // slot list: work items grouped by coarse cell (counting sort; skipped for huge V), G per slot
+    const bool sort_items = ix->ncells <= 65536;
+    const bool use5 = r.use5;
+    const int G = use5 ? 8 : (use3 ? geom3.G : r.geom.G);
+    // chunks per cell that get their own slot keys: what the largest cell needs (all shards' sizes bound this shard's)
+    int64_t CH = use3 ? ceil_div(ix->max_cell > 0 ? ix->max_cell : 1, (int64_t)r.seg_max) : 1;
+    CH = CH < 1 ? 1 : (CH > 16 ? 16 : CH);
+    Slots sl;
+    CIS_TRY(build_slots(b, sort_items ? SLOTS_SORTED : SLOTS_IDENTITY, G, CH, r.seg_max, &sl));
+    CIS_TRY(mark(b, 5));
+    ix->last_scan_kernel = use5 ? 6 : (use3 ? (geom3.two_pass == 2 ? 4 : 3) : 2);  // 4: the sampled single-pass form k_adc_scan4 does the work (k_adc_scan3 only its fall-back slots)
+    if (use5) {
+        CIS_TRY(ix->w_s5.reserve(scan5_workspace_bytes(nq)));
+        launch_scan5(M, geom3, n_items, nq, st, b.items, b.tabs, sl.slots, sl.n_slots, b.plan, b.T, b.T32, codes, K, L, sl.qctr, ix->w_hits.as<uint64_t>(), hitn,
+                     ix->w_slack.as<float>(), b.qbound, sl.fhdr, sl.fslots, ix->w_s5.p, nullptr);
+    } else if (use3) {
+        Scan3Geom g3 = geom3;
+        // M = 16 on the sampled form: the saturating scale of k_adc_scan4 (sums of the near candidates at this fraction of the entry cap)
+        const float sat16 = getenv("CIS_S4_SAT") ? (float)atof(getenv("CIS_S4_SAT")) : 0.75f;
+        if (M == 16 && g3.two_pass == 2) g3.sat = sat16;
+        launch_scan3(M, g3, n_items, st, b.items, b.tabs, sl.slots, sl.n_slots, b.T, b.T32, codes, K, L, sl.qctr, ix->w_hits.as<uint64_t>(), hitn, ix->w_slack.as<float>(), b.qbound, sl.fhdr, sl.fslots);
+        if (g3.sat > 0.f && ix->h_totals)  // (slots, fall-back slots) for the back-off in route_hints
+            CIS_CHECK_HIP(hipMemcpyAsync(&ix->h_totals[4], sl.qctr + 9, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+    } else
+        launch_scan2(M, r.geom, n_items, st, b.items, sl.slots, sl.n_slots, b.T, b.T32, codes, ids, K, L, sl.qctr, ix->w_hits.as<uint64_t>(), hitn, b.qbound);
+    return CIS_OK;
+}
+
+// survivors of the float32 scan: exact re-scoring + ranking (limit <= 440 here)
+template <int CAP, int MT>
+static void merge_survivors(const Batch& b, const Route& r, bool many) {
+    cis_index* ix = b.ix;
+    hipStream_t st = b.st;
+    const int nq = b.nq, L = b.L, S = r.S, M = ix->m->M, K = ix->m->K;
+    const SearchOut& out = b.out;
+    const uint64_t* surv = ix->w_hits.as<uint64_t>();
+    const int* hitn = ix->w_hitn.as<int>();
+    const uint8_t* codes = ix->codes_ptr();
+    const int64_t* ids = ix->ids_ptr();
+    const float* slack = r.use3 ? ix->w_slack.as<float>() : (const float*)nullptr;
+    if (many)
+        hipLaunchKernelGGL((k_merge_survivors<CAP, MT, 8>), dim3((unsigned)ceil_div(nq, 4)), dim3(256), (size_t)4 * CAP * 16, st,
+                           surv, hitn, b.item_off, b.items, b.T, codes, ids, nq, M, K, L, S, out.hits, out.ids, out.dists,
+                           out.n_found, out.cells, out.pos, b.plan, out.visited, slack);
+    else
+        hipLaunchKernelGGL((k_merge_survivors<CAP, MT, 4>), dim3((unsigned)ceil_div(nq, 4)), dim3(256), (size_t)4 * CAP * 16, st,
+                           surv, hitn, b.item_off, b.items, b.T, codes, ids, nq, M, K, L, S, out.hits, out.ids, out.dists,
+                           out.n_found, out.cells, out.pos, b.plan, out.visited, slack);
+}
+
+template <int CAP>
+static void merge_survivors_m(const Batch& b, const Route& r, bool many) {
+    const int M = b.ix->m->M;
+    if (M == 4) merge_survivors<CAP, 4>(b, r, many);
+    else if (M == 8) merge_survivors<CAP, 8>(b, r, many);
+    else merge_survivors<CAP, 16>(b, r, many);
+}
+
+// 4. ADC scan + block top-k, 5. per-query merge
+static int run_scan_and_merge(Batch& b, const Route& r) {
+    cis_index* ix = b.ix;
+    hipStream_t st = b.st;
+    const int K = ix->m->K, M = ix->m->M, nq = b.nq, L = b.L, S = r.S;
+    const int64_t n_items = b.n_items;
+    const SearchOut& out = b.out;
+    CIS_TRY(mark(b, 2));
+    if (n_items > 0) {
+        b.pr.has_scan = true;
+        if (r.fast) {
+            CIS_TRY(run_fast_scan(b, r));
+        } else {
+            CIS_TRY(mark(b, 5));
             ix->last_scan_kernel = 1;
-            launch_scan_exact(M, n_items, st, items, T, codes, ids, K, L, S, nullptr, hits, hitn);
+            launch_scan_exact(M, n_items, st, b.items, b.T, ix->codes_ptr(), ix->ids_ptr(), K, L, S, nullptr, ix->w_hits.as<cis_hit>(), ix->w_hitn.as<int>());
         }
         ix->stats[3] += 1;
     }
     // 5. per-query merge
-    CIS_TRY(mark(3));
+    CIS_TRY(mark(b, 3));
     {
         const cis_hit* hits = ix->w_hits.as<cis_hit>();
         const int* hitn = ix->w_hitn.as<int>();
-        if (fast) {
-            // survivors of the float32 scan: exact re-scoring + ranking (limit <= 440 here)
-            const uint64_t* surv = ix->w_hits.as<uint64_t>();
-            const uint8_t* codes = ix->codes_ptr();
-            const int64_t* ids = ix->ids_ptr();
+        if (r.fast) {
             // several lists per query (short cells): the variant whose fast path holds 512 survivors per query
             const bool many = n_items > nq + nq / 4;
-#define CIS_MERGE_SURV(CAP, MT)                                                                                              \
-    do {                                                                                                                     \
-        if (many)                                                                                                            \
-            hipLaunchKernelGGL((k_merge_survivors<CAP, MT, 8>), dim3((unsigned)ceil_div(nq, 4)), dim3(256), (size_t)4 * CAP * 16, st, \
-                               surv, hitn, item_off, items, T, codes, ids, nq, M, K, L, S, out.hits, out.ids, out.dists,     \
-                               out.n_found, out.cells, out.pos, plan, out.visited, use3 ? ix->w_slack.as<float>() : (const float*)nullptr);                            \
-        else                                                                                                                 \
-            hipLaunchKernelGGL((k_merge_survivors<CAP, MT, 4>), dim3((unsigned)ceil_div(nq, 4)), dim3(256), (size_t)4 * CAP * 16, st, \
-                               surv, hitn, item_off, items, T, codes, ids, nq, M, K, L, S, out.hits, out.ids, out.dists,     \
-                               out.n_found, out.cells, out.pos, plan, out.visited, use3 ? ix->w_slack.as<float>() : (const float*)nullptr);                            \
-    } while (0)
-#define CIS_MERGE_SURV_M(CAP)                                                                          \
-    do {                                                                                               \
-        if (M == 4) CIS_MERGE_SURV(CAP, 4); else if (M == 8) CIS_MERGE_SURV(CAP, 8); else CIS_MERGE_SURV(CAP, 16); \
-    } while (0)
-            if (L <= 128) CIS_MERGE_SURV_M(256);
-            else if (L <= 256) CIS_MERGE_SURV_M(512);
-            else if (L <= 440) CIS_MERGE_SURV_M(1024);
-            else CIS_MERGE_SURV_M(2048);
-#undef CIS_MERGE_SURV_M
-#undef CIS_MERGE_SURV
+            if (L <= 128) merge_survivors_m<256>(b, r, many);
+            else if (L <= 256) merge_survivors_m<512>(b, r, many);
+            else if (L <= 440) merge_survivors_m<1024>(b, r, many);
+            else merge_survivors_m<2048>(b, r, many);
         } else if (L <= 512)
-            hipLaunchKernelGGL(k_merge_items<1024>, dim3(nq), dim3(256), (size_t)1024 * 24 + 16, st, hits, hitn, item_off, L, S, out.hits,
+            hipLaunchKernelGGL(k_merge_items<1024>, dim3(nq), dim3(256), (size_t)1024 * 24 + 16, st, hits, hitn, b.item_off, L, S, out.hits,
                                out.ids, out.dists, out.n_found, out.cells, out.pos);
         else if (L <= 1024)
-            hipLaunchKernelGGL(k_merge_items<2048>, dim3(nq), dim3(256), (size_t)2048 * 24 + 16, st, hits, hitn, item_off, L, S, out.hits,
+            hipLaunchKernelGGL(k_merge_items<2048>, dim3(nq), dim3(256), (size_t)2048 * 24 + 16, st, hits, hitn, b.item_off, L, S, out.hits,
                                out.ids, out.dists, out.n_found, out.cells, out.pos);
         else
-            hipLaunchKernelGGL(k_merge_items<4096>, dim3(nq), dim3(256), (size_t)4096 * 24 + 16, st, hits, hitn, item_off, L, S, out.hits,
+            hipLaunchKernelGGL(k_merge_items<4096>, dim3(nq), dim3(256), (size_t)4096 * 24 + 16, st, hits, hitn, b.item_off, L, S, out.hits,
                                out.ids, out.dists, out.n_found, out.cells, out.pos);
     }
-    if (out.visited && !fast)  // the survivor merge writes `visited` itself
-        hipLaunchKernelGGL(k_copy_visited, dim3((unsigned)ceil_div(nq, 256)), dim3(256), 0, st, plan, nq, out.visited);
+    if (out.visited && !r.fast)  // the survivor merge writes `visited` itself
+        hipLaunchKernelGGL(k_copy_visited, dim3((unsigned)ceil_div(nq, 256)), dim3(256), 0, st, b.plan, nq, out.visited);
     CIS_CHECK_HIP(hipGetLastError());
-    CIS_TRY(mark(4));
-    if (ix->profiling) ix->prof.push_back(pr);
+    CIS_TRY(mark(b, 4));
+    if (ix->profiling) ix->prof.push_back(b.pr);
     return CIS_OK;
 }
 
-static int effective_limit(int64_t quota, int limit, int* L) {
-    int64_t l = limit < 0 ? quota : limit;  // search.py:213-214
-    if (l < 0) l = 0;
-    if (l > MAX_LIMIT) {
-        cis_set_error("limit=%lld exceeds the %d ranked results per query supported by this build", (long long)l, MAX_LIMIT);
-        return CIS_EUNSUPPORTED;
+static int search_batch(cis_index* ix, const void* dQ, int q_dtype, int nq, int64_t quota, int L, const SearchOut& out,
+                        hipStream_t st) {
+    const int V = ix->m->V;
+    Batch b{};
+    b.ix = ix; b.dQ = dQ; b.q_dtype = q_dtype; b.nq = nq; b.quota = quota; b.L = L; b.out = out; b.st = st;
+    b.t_entry = std::chrono::steady_clock::now();
+    ix->last_scan_kernel = 0;
+    b.pr.has_scan = false;
+    for (int i = 0; i < 6; ++i) b.pr.ev[i] = nullptr;
+    CIS_TRY(mark(b, 0));
+    // 1., 2. LOPQ-space queries, workspaces of the rank and the plan
+    CIS_TRY(front_prepare(ix, dQ, q_dtype, nq, st, &b.f));
+    CIS_TRY(ix->w_plan.reserve((size_t)nq * sizeof(PlanOut)));
+    CIS_TRY(ix->w_off.reserve((size_t)(2 * (nq + 1) + 4 + nq) * sizeof(int64_t)));
+    b.item_off = ix->w_off.as<int64_t>();
+    b.tab_off = b.item_off + (nq + 1);
+    b.totals = b.tab_off + (nq + 1);
+    b.qbound = reinterpret_cast<unsigned long long*>(b.totals + 4);
+    b.plan = ix->w_plan.as<PlanOut>();
+    b.grp_cur = b.f.grp_cnt + 2 * V * GRP_SUB;
+    b.grp_base = b.f.grp_cnt + 4 * V * GRP_SUB;
+    Route r{};
+    route_hints(ix, nq, quota, L, &r);
+    b.plan_hint = (r.par_plan && !getenv("CIS_NO_PLAN_HINT")) ? ix->plan_hint_ptr() : nullptr;
+    b.hint_slot = (int)((ix->plan_seq + 1) & 1);  // this batch's launches add into this parity and read the other
+    // cells WITH candidates per query the fast plan lists (16 bytes each; the empty cells it walks -- most of them at thousands of coarse
+    // clusters, tens of thousands for an outlier query -- are not listed): 2 GB of lists per batch at most; past the cap the query goes
+    // to the serial frontier walk, ~3 us per cell
+    int64_t vis_cap64 = ((int64_t)1 << 31) / ((int64_t)(nq > 0 ? nq : 1) * 16);
+    if (vis_cap64 < 4096) vis_cap64 = 4096;
+    if (vis_cap64 > (1 << 20)) vis_cap64 = 1 << 20;
+    if (vis_cap64 > (int64_t)V * V) vis_cap64 = (int64_t)V * V;
+    b.vis_cap = (int)vis_cap64;
+    if (r.par_plan) {
+        CIS_TRY(ix->w_planfb.reserve((size_t)2 * nq * sizeof(int)));
+        CIS_TRY(ix->w_vis.reserve((size_t)nq * b.vis_cap * 2 * sizeof(uint64_t)));
+        b.plan_fb = ix->w_planfb.as<int>();
+        b.vis_list = ix->w_vis.as<uint64_t>();
     }
-    *L = (int)l;
-    return CIS_OK;
+    const bool f32 = b.f.ct == CIS_F32;
+    CIS_TRY(f32 ? front_count<float>(b, r) : front_count<double>(b, r));
+    if (r.par_plan && getenv("CIS_DEBUG_PLAN")) CIS_TRY(dump_plan_fallbacks(b));
+    CIS_TRY(plan_totals(b, r));
+    CIS_TRY(route_decide(b, &r));
+    // 3. emit items + table list
+    CIS_TRY(mark(b, 1));  // the plan read-back above is part of the front end
+    CIS_TRY(reserve_batch(b, r));
+    if (f32) emit_and_tables<float>(b, r);
+    else emit_and_tables<double>(b, r);
+    finish_tables(b, r);
+    if (r.stream) return run_stream(b, r);
+    if (r.big) return run_all_candidates(b, r);
+    return run_scan_and_merge(b, r);
 }
 
 static const int QUERY_BATCH = 8192;
@@ -5582,6 +5641,16 @@ static int search_all(cis_index* ix, const void* dQ, int q_dtype, int nq, int64_
         a += bn;
     }
     return CIS_OK;
+}
+
+// lopq_index.h: the door of the packed entry point (lopq_exchange.hip)
+int cis_search_partial(cis_index* ix, const void* dQ, int q_dtype, int nq, int64_t quota, int L, cis_hit* d_hits, int32_t* d_n_found,
+                       int32_t* d_visited, hipStream_t st) {
+    SearchOut o{};
+    o.hits = d_hits;
+    o.n_found = d_n_found;
+    o.visited = d_visited;
+    return search_all(ix, dQ, q_dtype, nq, quota, L, o, st);
 }
 
 // ---- routed cell-sharded search (round 5): which ranks own the cells a query visits ---------------------------------------------
@@ -5645,6 +5714,15 @@ __global__ __launch_bounds__(64) void k_plan_owners(const CT* __restrict__ sorte
     }
 }
 
+template <typename CT>
+static void launch_plan_owners(cis_index* ix, int nq, int64_t quota, int* grp_cnt, const int32_t* d_owner, uint64_t* d_mask, int32_t* d_visited,
+                               hipStream_t st) {
+    const int V = ix->m->V;
+    launch_rank<CT>(ix, nq, false, grp_cnt, st);  // (V <= 4096: k_rank_sort for every V > 256)
+    hipLaunchKernelGGL(k_plan_owners<CT>, dim3(nq), dim3(64), (size_t)V * sizeof(int), st, ix->w_sorted.as<CT>(), ix->w_order.as<uint16_t>(),
+                       ix->gcount_ptr(), d_owner, ix->world, nq, V, quota, (unsigned long long*)d_mask, d_visited);
+}
+
 extern "C" int cis_index_query_owners_dev(cis_index* ix, const void* dQ, int q_dtype, int nq, int64_t quota, uint64_t* d_mask,
                                           int32_t* d_visited, void* stream) {
     CIS_REQUIRE(ix != nullptr, "index is NULL");
@@ -5658,143 +5736,15 @@ extern "C" int cis_index_query_owners_dev(cis_index* ix, const void* dQ, int q_d
     cis_model* m = ix->m;
     CIS_CHECK_HIP(hipSetDevice(m->device));
     hipStream_t st = (hipStream_t)stream;
-    const int V = m->V, D = m->D;
-    CIS_REQUIRE(V <= 4096, "owner walk: V <= 4096");
-    const void* xp = dQ;
-    int xp_dtype = q_dtype;
-    if (m->has_pca) {
-        CIS_TRY(ix->w_xp.reserve((size_t)nq * D * sizeof(float)));
-        CIS_TRY(cis_dev_apply_pca(m, dQ, q_dtype, nq, ix->w_xp.as<float>(), st, &ix->w_y64));
-        xp = ix->w_xp.p;
-        xp_dtype = CIS_F32;
-    }
-    const void* xc;
-    int ct;
-    CIS_TRY(cis_dev_coarse_type(m, xp, xp_dtype, nq, &xc, &ct, st, &ix->w_x64));
-    const size_t csz = (ct == CIS_F32) ? 4 : 8;
-    CIS_TRY(ix->w_cd.reserve((size_t)2 * nq * V * csz));
-    CIS_TRY(ix->w_sorted.reserve((size_t)2 * nq * V * csz));
-    CIS_TRY(ix->w_order.reserve((size_t)2 * nq * V * sizeof(uint16_t)));
-    {
-        const void* grp_before = ix->w_grp.p;
-        CIS_TRY(ix->w_grp.reserve((size_t)(GRP_WORDS(V) + 2 * GRP_TILES(V)) * sizeof(int)));
-        if (ix->w_grp.p != grp_before) CIS_CHECK_HIP(hipMemsetAsync(ix->w_grp.p, 0, ix->w_grp.cap, st));
-    }
-    int* grp_cnt = ix->w_grp.as<int>();  // the rank kernels leave the table-group counters zeroed, as every search expects to find them
-    CIS_TRY(cis_launch_sqdist_both(m, xc, ct, nq, ix->w_cd.p, st));
-    int Vp2 = 64;
-    while (Vp2 < V) Vp2 <<= 1;
+    CIS_REQUIRE(m->V <= 4096, "owner walk: V <= 4096");
+    Front f;  // the rank kernels leave the table-group counters zeroed, as every search expects to find them
+    CIS_TRY(front_prepare(ix, dQ, q_dtype, nq, st, &f));
+    CIS_TRY(cis_launch_sqdist_both(m, f.xc, f.ct, nq, ix->w_cd.p, st));
     const cis_index* own = ix->base ? ix->base : ix;  // a view reads the owner table of its base
     const int32_t* d_owner = own->owner.empty() ? nullptr : own->d_owner.as<int32_t>();
     CIS_REQUIRE(own->owner.empty() || d_owner != nullptr, "owner table not on the device");
-    if (ct == CIS_F32) {
-        if (V > 256) hipLaunchKernelGGL(k_rank_sort<float>, dim3(nq, 2), dim3(256), (size_t)Vp2 * 16, st, ix->w_cd.as<float>(), nq, V, Vp2,
-                                        ix->w_order.as<uint16_t>(), ix->w_sorted.as<float>(), grp_cnt);
-        else hipLaunchKernelGGL(k_rank<float>, dim3(nq, 2), dim3(V <= 64 ? 64 : 256), (size_t)V * 8, st, ix->w_cd.as<float>(), nq, V,
-                                ix->w_order.as<uint16_t>(), ix->w_sorted.as<float>(), grp_cnt);
-        hipLaunchKernelGGL(k_plan_owners<float>, dim3(nq), dim3(64), (size_t)V * sizeof(int), st, ix->w_sorted.as<float>(), ix->w_order.as<uint16_t>(),
-                           ix->gcount_ptr(), d_owner, ix->world, nq, V, quota, (unsigned long long*)d_mask, d_visited);
-    } else {
-        if (V > 256) hipLaunchKernelGGL(k_rank_sort<double>, dim3(nq, 2), dim3(256), (size_t)Vp2 * 16, st, ix->w_cd.as<double>(), nq, V, Vp2,
-                                        ix->w_order.as<uint16_t>(), ix->w_sorted.as<double>(), grp_cnt);
-        else hipLaunchKernelGGL(k_rank<double>, dim3(nq, 2), dim3(V <= 64 ? 64 : 256), (size_t)V * 8, st, ix->w_cd.as<double>(), nq, V,
-                                ix->w_order.as<uint16_t>(), ix->w_sorted.as<double>(), grp_cnt);
-        hipLaunchKernelGGL(k_plan_owners<double>, dim3(nq), dim3(64), (size_t)V * sizeof(int), st, ix->w_sorted.as<double>(), ix->w_order.as<uint16_t>(),
-                           ix->gcount_ptr(), d_owner, ix->world, nq, V, quota, (unsigned long long*)d_mask, d_visited);
-    }
-    CIS_CHECK_HIP(hipGetLastError());
-    return CIS_OK;
-}
-
-// Routing tables of a home rank: slot[d][i] = the row of query i in the buffer that goes to rank d (-1: not sent), in query order;
-// cnt[d] = rows used (at most cap; *overflow = 1 when a destination would need more).  One workgroup per destination.
-__global__ __launch_bounds__(1024) void k_route_slots(const unsigned long long* __restrict__ mask, int nq, int cap, int32_t* __restrict__ slot,
-                                                      int32_t* __restrict__ cnt, int32_t* __restrict__ overflow) {
-    __shared__ int s_w[16];
-    __shared__ int s_base;
-    const int d = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    if (tid == 0) s_base = 0;
-    __syncthreads();
-    for (int i0 = 0; i0 < nq; i0 += 1024) {
-        const int i = i0 + tid;
-        const bool f = i < nq && ((mask[i] >> d) & 1ull);
-        const unsigned long long b = __builtin_amdgcn_ballot_w64(f);
-        const int before = __builtin_popcountll(b & ((1ull << lane) - 1ull));
-        if (lane == 0) s_w[wv] = __builtin_popcountll(b);
-        __syncthreads();
-        int wbase = s_base;
-        for (int w = 0; w < wv; ++w) wbase += s_w[w];
-        if (i < nq) {
-            const int pos = wbase + before;
-            slot[(int64_t)d * nq + i] = (f && pos < cap) ? pos : -1;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            int tot = s_base;
-            for (int w = 0; w < 16; ++w) tot += s_w[w];
-            s_base = tot;
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        cnt[d] = s_base < cap ? s_base : cap;
-        if (s_base > cap) atomicExch(overflow, 1);
-    }
-}
-
-__global__ void k_route_rows(const uint32_t* __restrict__ q, int nq, int W /* 32-bit words per row */, const int32_t* __restrict__ slot, int cap,
-                             uint32_t* __restrict__ out) {
-    const int i = blockIdx.x, d = blockIdx.y;
-    const int sl = slot[(int64_t)d * nq + i];
-    if (sl < 0) return;
-    const uint32_t* src = q + (int64_t)i * W;
-    uint32_t* dst = out + ((int64_t)d * cap + sl) * W;
-    for (int k = threadIdx.x; k < W; k += blockDim.x) dst[k] = src[k];
-}
-
-extern "C" int cis_route_queries_dev(const void* d_q, int nq, int row_bytes, const uint64_t* d_mask, int world, int cap, void* d_out_q,
-                                     int32_t* d_slot, int32_t* d_cnt, int32_t* d_overflow, void* stream) {
-    CIS_REQUIRE(nq >= 0 && row_bytes > 0 && row_bytes % 4 == 0 && world >= 1 && world <= 64 && cap >= 1, "route: sizes out of range");
-    CIS_REQUIRE(d_cnt && d_overflow && (nq == 0 || (d_q && d_mask && d_out_q && d_slot)), "NULL buffer");  // (nq = 0: [world][0] slots)
-    hipStream_t st = (hipStream_t)stream;
-    const int W = row_bytes / 4;
-    CIS_CHECK_HIP(hipMemsetAsync(d_overflow, 0, sizeof(int32_t), st));
-    hipLaunchKernelGGL(k_route_slots, dim3(world), dim3(1024), 0, st, (const unsigned long long*)d_mask, nq, cap, d_slot, d_cnt, d_overflow);
-    if (nq > 0) hipLaunchKernelGGL(k_route_rows, dim3(nq, world), dim3(W >= 256 ? 256 : 64), 0, st, (const uint32_t*)d_q, nq, W, d_slot, cap, (uint32_t*)d_out_q);
-    CIS_CHECK_HIP(hipGetLastError());
-    return CIS_OK;
-}
-
-// Merge tables of the routed search's return trip: the list of home query i from rank d is row base[d] + slot[d][i] of the returned
-// buffer (L records per row, ranked, valid hits first).  off = the row's first record, cnt = its valid hits (0: rank d was not asked).
-struct RouteBase { int64_t v[64]; };
-__global__ void k_routed_tables(const int32_t* __restrict__ slot, int world, int nq, RouteBase base, const cis_hit* __restrict__ hits, int L,
-                                int64_t* __restrict__ off, int32_t* __restrict__ cnt) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (int64_t)world * nq) return;
-    const int d = (int)(t / nq);
-    const int sl = slot[t];
-    if (sl < 0) { off[t] = 0; cnt[t] = 0; return; }
-    const int64_t row = base.v[d] + sl;
-    const cis_hit* h = hits + row * L;
-    int lo = 0, hi = L;  // first empty slot (id < 0): the valid hits are a prefix
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (h[mid].id >= 0) lo = mid + 1; else hi = mid;
-    }
-    off[t] = row * L;
-    cnt[t] = lo;
-}
-
-extern "C" int cis_routed_merge_tables_dev(const int32_t* d_slot, int world, int nq, const int64_t* h_base, const cis_hit* d_hits, int L,
-                                           int64_t* d_off, int32_t* d_cnt, void* stream) {
-    CIS_REQUIRE(world >= 1 && world <= 64 && nq >= 0 && L >= 0, "routed merge tables: sizes out of range");
-    CIS_REQUIRE(nq == 0 || (d_slot && h_base && d_off && d_cnt && (L == 0 || d_hits)), "NULL buffer");
-    if (nq == 0) return CIS_OK;
-    RouteBase b;
-    for (int d = 0; d < 64; ++d) b.v[d] = d < world ? h_base[d] : 0;
-    const int64_t n = (int64_t)world * nq;
-    hipLaunchKernelGGL(k_routed_tables, dim3((unsigned)ceil_div(n, (int64_t)256)), dim3(256), 0, (hipStream_t)stream, d_slot, world, nq, b, d_hits, L, d_off, d_cnt);
+    if (f.ct == CIS_F32) launch_plan_owners<float>(ix, nq, quota, f.grp_cnt, d_owner, d_mask, d_visited, st);
+    else launch_plan_owners<double>(ix, nq, quota, f.grp_cnt, d_owner, d_mask, d_visited, st);
     CIS_CHECK_HIP(hipGetLastError());
     return CIS_OK;
 }
@@ -5809,384 +5759,6 @@ extern "C" int cis_index_search_partial_dev(cis_index* ix, const void* dQ, int q
     return search_all(ix, dQ, q_dtype, nq, quota, L, o, (hipStream_t)stream);
 }
 
-// exclusive scan of the per-query hit counts (single block) and the packing of the valid row prefixes
-__global__ __launch_bounds__(1024) void k_pack_scan(const int32_t* __restrict__ cnt, int nq, int64_t* __restrict__ off,
-                                                    int64_t* __restrict__ total) {
-    __shared__ int64_t s_w[16];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    int64_t run = 0;  // all queries before this block-sized chunk
-    for (int base = 0; base < nq; base += 1024) {
-        const int q = base + tid;
-        const int64_t c = q < nq ? cnt[q] : 0;
-        int64_t x = c;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int64_t y = __shfl_up(x, d);
-            if (lane >= d) x += y;
-        }
-        if (lane == 63) s_w[wv] = x;
-        __syncthreads();
-        int64_t wp = 0, all = 0;
-        for (int k = 0; k < 16; ++k) { const int64_t y = s_w[k]; if (k < wv) wp += y; all += y; }
-        if (q < nq) off[q] = run + wp + x - c;
-        run += all;
-        __syncthreads();
-    }
-    if (tid == 0) *total = run;
-}
-
-__global__ void k_pack_hits(const cis_hit* __restrict__ dense /* [nq][L] */, const int32_t* __restrict__ cnt,
-                            const int64_t* __restrict__ off, int nq, int L, cis_hit* __restrict__ packed) {
-    const int q = blockIdx.x;
-    const int c = cnt[q];
-    const int64_t o = off[q];
-    for (int x = threadIdx.x; x < c; x += blockDim.x) packed[o + x] = dense[(int64_t)q * L + x];
-}
-
-extern "C" int cis_index_search_partial_packed_dev(cis_index* ix, const void* dQ, int q_dtype, int nq, int64_t quota, int limit,
-                                                   cis_hit* d_packed, int32_t* d_cnt, int64_t* d_off, int64_t* d_total,
-                                                   int32_t* d_visited, void* stream) {
-    int L;
-    CIS_TRY(effective_limit(quota, limit, &L));
-    CIS_REQUIRE(ix != nullptr && d_cnt && d_off && d_total && (L == 0 || d_packed), "NULL buffer");
-    hipStream_t st = (hipStream_t)stream;
-    if (nq == 0 || L == 0) {
-        CIS_CHECK_HIP(hipMemsetAsync(d_total, 0, sizeof(int64_t), st));
-        if (nq > 0) {
-            CIS_CHECK_HIP(hipMemsetAsync(d_cnt, 0, (size_t)nq * sizeof(int32_t), st));
-            CIS_CHECK_HIP(hipMemsetAsync(d_off, 0, (size_t)nq * sizeof(int64_t), st));
-        }
-        if (nq == 0) return CIS_OK;
-    }
-    CIS_CHECK_HIP(hipSetDevice(ix->m->device));
-    CIS_TRY(ix->w_part.reserve((size_t)nq * (L > 0 ? L : 1) * sizeof(cis_hit)));
-    SearchOut o{};
-    o.hits = ix->w_part.as<cis_hit>();
-    o.n_found = d_cnt;
-    o.visited = d_visited;
-    CIS_TRY(search_all(ix, dQ, q_dtype, nq, quota, L, o, st));
-    if (L == 0) return CIS_OK;
-    hipLaunchKernelGGL(k_pack_scan, dim3(1), dim3(1024), 0, st, d_cnt, nq, d_off, d_total);
-    hipLaunchKernelGGL(k_pack_hits, dim3(nq), dim3(64), 0, st, ix->w_part.as<cis_hit>(), d_cnt, d_off, nq, L, d_packed);
-    CIS_CHECK_HIP(hipGetLastError());
-    return CIS_OK;
-}
-
-static int merge_parts(const cis_hit* d_parts, int world, int nq, int L, int64_t* d_ids, double* d_dists,
-                       int32_t* d_nf, int32_t* d_cells, uint32_t* d_pos, hipStream_t st) {
-    if (nq == 0 || L == 0) return CIS_OK;
-    if (L <= 512)
-        hipLaunchKernelGGL(k_merge_parts<1024>, dim3(nq), dim3(256), (size_t)1024 * 24 + 16, st, d_parts, world, nq, L, d_ids, d_dists, d_nf, d_cells, d_pos);
-    else if (L <= 1024)
-        hipLaunchKernelGGL(k_merge_parts<2048>, dim3(nq), dim3(256), (size_t)2048 * 24 + 16, st, d_parts, world, nq, L, d_ids, d_dists, d_nf, d_cells, d_pos);
-    else
-        hipLaunchKernelGGL(k_merge_parts<4096>, dim3(nq), dim3(256), (size_t)4096 * 24 + 16, st, d_parts, world, nq, L, d_ids, d_dists, d_nf, d_cells, d_pos);
-    CIS_CHECK_HIP(hipGetLastError());
-    return CIS_OK;
-}
-
-// Records of shard w for query q that really ARRIVED: with the fixed-size exchange a shard that held more than `stride` records was
-// cut there (the overflow flag tells the caller to repeat the exchange); the merge must not read past the cut.
-static __device__ __forceinline__ int arrived(const int32_t* __restrict__ cnt, const int64_t* __restrict__ off, int64_t stride, int w, int nq, int q) {
-    const int64_t o = off[(int64_t)w * nq + q];
-    const int64_t room = stride - o;
-    const int c = cnt[(int64_t)w * nq + q];
-    if (stride == 0) return c;  // one flat buffer, absolute offsets, nothing was cut (the routed search's return trip)
-    return room <= 0 ? 0 : (c < room ? c : (int)room);
-}
-
-// Merge of PACKED per-shard hit lists: shard w contributed parts[w*stride + off[w*nq+q] .. + cnt[w*nq+q]) for query q
-// (its valid hits only, in query order).  One wave per query; same ranking key as everywhere: (dist, visit_rank, pos).
-template <int CAPM, int WPB /* waves (= queries) per workgroup */>
-__global__ __launch_bounds__(WPB * 64) void k_merge_packed(const cis_hit* __restrict__ parts, int world, int64_t stride,
-                                                      const int64_t* __restrict__ off, const int32_t* __restrict__ cnt, int nq,
-                                                      int limit, int64_t* __restrict__ out_ids, double* __restrict__ out_dists,
-                                                      int* __restrict__ out_n, int32_t* __restrict__ out_cells,
-                                                      uint32_t* __restrict__ out_pos) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lane = threadIdx.x & 63, wq = threadIdx.x >> 6;
-    const int q = blockIdx.x * WPB + wq;
-    if (q >= nq) return;
-    uint64_t* ka = reinterpret_cast<uint64_t*>(smem) + (size_t)wq * 3 * CAPM;
-    uint64_t* kb = ka + CAPM;
-    uint64_t* pay = kb + CAPM;  // index of the hit in parts
-    // A query whose hits all come from ONE shard (the rule with few coarse clusters: a V = 16 query visits one or two cells, and a
-    // cell lives on one shard): that list arrives ranked, so it is copied -- no LDS, no sort.  The merge then costs what the number
-    // of non-empty lists costs, not what the number of shards does.
-    {
-        int nonempty = 0, lone = 0, lone_n = 0;
-        for (int w = 0; w < world; ++w) {
-            const int v = arrived(cnt, off, stride, w, nq, q);
-            if (v > 0) { ++nonempty; lone = w; lone_n = v; }
-        }
-        if (nonempty <= 1) {
-            const int nv1 = lone_n < limit ? lone_n : limit;
-            const int64_t base = nonempty ? (int64_t)lone * stride + off[(int64_t)lone * nq + q] : 0;
-            const int64_t o1 = (int64_t)q * limit;
-            for (int x = lane; x < limit; x += 64) {
-                int64_t id = -1;
-                double dist = __longlong_as_double(0x7ff8000000000000LL);
-                int32_t cell = -1;
-                uint32_t pos = 0xffffffffu;
-                if (x < nv1) {
-                    const cis_hit hh = parts[base + x];
-                    id = hh.id; dist = hh.dist; cell = hh.cell; pos = hh.pos;
-                }
-                out_ids[o1 + x] = id;
-                out_dists[o1 + x] = dist;
-                if (out_cells) out_cells[o1 + x] = cell;
-                if (out_pos) out_pos[o1 + x] = pos;
-            }
-            if (lane == 0 && out_n) out_n[q] = nv1;
-            return;
-        }
-    }
-    int have = 0, l = 0, e = 0, total = 0;
-    while (true) {
-        int n = have;
-        int room = CAPM - have;
-        while (l < world && room > 0) {
-            const int valid = arrived(cnt, off, stride, l, nq, q);
-            const int take = (valid - e < room) ? (valid - e) : room;
-            const int64_t base = (int64_t)l * stride + off[(int64_t)l * nq + q] + e;
-            for (int x = lane; x < take; x += 64) {
-                const cis_hit hh = parts[base + x];
-                ka[n + x] = (uint64_t)__double_as_longlong(hh.dist);
-                kb[n + x] = ((uint64_t)hh.visit_rank << 32) | hh.pos;
-                pay[n + x] = (uint64_t)(base + x);
-            }
-            n += take; total += take; room -= take; e += take;
-            if (e >= valid) { ++l; e = 0; }
-        }
-        int ns = 64;
-        while (ns < n) ns <<= 1;
-        for (int x = n + lane; x < ns; x += 64) { ka[x] = ~0ull; kb[x] = ~0ull; pay[x] = ~0ull; }
-        wave_lds_sync();
-        // bitonic sort with payload
-        for (int k = 2; k <= ns; k <<= 1) {
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                for (int t = lane; t < (ns >> 1); t += 64) {
-                    const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                    const int p = i + j;
-                    const bool asc = ((i & k) == 0);
-                    const uint64_t a0 = ka[i], b0 = kb[i], a1 = ka[p], b1 = kb[p];
-                    const bool gt = (a0 > a1) || (a0 == a1 && b0 > b1);
-                    if (gt == asc) {
-                        ka[i] = a1; kb[i] = b1; ka[p] = a0; kb[p] = b0;
-                        const uint64_t y = pay[i]; pay[i] = pay[p]; pay[p] = y;
-                    }
-                }
-                wave_lds_sync();
-            }
-        }
-        have = n < limit ? n : limit;
-        if (l >= world) break;
-    }
-    const int nv = total < limit ? total : limit;
-    const int64_t o = (int64_t)q * limit;
-    for (int x = lane; x < limit; x += 64) {
-        int64_t id = -1;
-        double dist = __longlong_as_double(0x7ff8000000000000LL);
-        int32_t cell = -1;
-        uint32_t pos = 0xffffffffu;
-        if (x < nv) {
-            const cis_hit hh = parts[pay[x]];
-            id = hh.id; dist = hh.dist; cell = hh.cell; pos = hh.pos;
-        }
-        out_ids[o + x] = id;
-        out_dists[o + x] = dist;
-        if (out_cells) out_cells[o + x] = cell;
-        if (out_pos) out_pos[o + x] = pos;
-    }
-    if (lane == 0 && out_n) out_n[q] = nv;
-}
-
-// Any limit (above the 3072 records a wave ranks in LDS): every shard's list arrives ranked by (dist, visit_rank, pos), and the
-// keys of different shards never tie (a cell lives on one shard), so a record's place in the merged ranking is its index in its
-// own list plus, for every other list, the number of records with a smaller key -- binary searches, no sort.  One workgroup per
-// query; records past `limit` are dropped, unused slots padded like every other route (-1 / NaN).
-__global__ __launch_bounds__(256) void k_merge_packed_ranked(const cis_hit* __restrict__ parts, int world, int64_t stride,
-                                                             const int64_t* __restrict__ off, const int32_t* __restrict__ cnt, int nq, int limit,
-                                                             int64_t* __restrict__ out_ids, double* __restrict__ out_dists, int32_t* __restrict__ out_n,
-                                                             int32_t* __restrict__ out_cells, uint32_t* __restrict__ out_pos) {
-    const int q = blockIdx.x;
-    __shared__ int s_tot;
-    if (threadIdx.x == 0) {
-        int t = 0;
-        for (int w = 0; w < world; ++w) t += arrived(cnt, off, stride, w, nq, q);
-        s_tot = t;
-    }
-    __syncthreads();
-    const int total = s_tot;
-    const int64_t o = (int64_t)q * limit;
-    auto less = [](const cis_hit& a, const cis_hit& b) -> bool {
-        const uint64_t da = (uint64_t)__double_as_longlong(a.dist), db = (uint64_t)__double_as_longlong(b.dist);
-        if (da != db) return da < db;  // non-negative doubles order like their bit patterns
-        if (a.visit_rank != b.visit_rank) return a.visit_rank < b.visit_rank;
-        return a.pos < b.pos;
-    };
-    for (int w = 0; w < world; ++w) {
-        const cis_hit* lst = parts + (int64_t)w * stride + off[(int64_t)w * nq + q];
-        const int n = arrived(cnt, off, stride, w, nq, q);
-        for (int a = threadIdx.x; a < n; a += blockDim.x) {
-            const cis_hit e = lst[a];
-            int64_t rank = a;
-            for (int w2 = 0; w2 < world && rank < limit; ++w2) {
-                if (w2 == w) continue;
-                const cis_hit* l2 = parts + (int64_t)w2 * stride + off[(int64_t)w2 * nq + q];
-                int lo = 0, hi = arrived(cnt, off, stride, w2, nq, q);
-                while (lo < hi) {  // records of list w2 with a smaller key
-                    const int mid = (lo + hi) >> 1;
-                    if (less(l2[mid], e)) lo = mid + 1;
-                    else hi = mid;
-                }
-                rank += lo;
-            }
-            if (rank < limit) {
-                out_ids[o + rank] = e.id;
-                out_dists[o + rank] = e.dist;
-                if (out_cells) out_cells[o + rank] = e.cell;
-                if (out_pos) out_pos[o + rank] = e.pos;
-            }
-        }
-    }
-    const int nv = total < limit ? total : limit;
-    for (int x = nv + threadIdx.x; x < limit; x += blockDim.x) {
-        out_ids[o + x] = -1;
-        out_dists[o + x] = __longlong_as_double(0x7ff8000000000000LL);
-        if (out_cells) out_cells[o + x] = -1;
-        if (out_pos) out_pos[o + x] = 0xffffffffu;
-    }
-    if (threadIdx.x == 0 && out_n) out_n[q] = nv;
-}
-
-// Offsets of the packed exchange on the device: cnt_all [world][nq] (what the counts all-gather delivered) -> off [world][nq] =
-// exclusive scan of a shard's counts over the queries, totals[w], and *overflow = 1 when a shard holds more records than the fixed
-// stride of the payload all-gather (the caller then repeats the exchange with the exact stride).  Replaces a torch.cumsum + a host
-// read per batch (round 3).  One workgroup per shard.
-__global__ __launch_bounds__(1024) void k_exchange_offsets(const int32_t* __restrict__ cnt_all, int nq, int64_t stride, int64_t* __restrict__ off,
-                                                           int64_t* __restrict__ totals, int32_t* __restrict__ overflow) {
-    __shared__ int64_t s_w[16];
-    __shared__ int64_t s_run;
-    const int w = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int32_t* c = cnt_all + (int64_t)w * nq;
-    int64_t* o = off + (int64_t)w * nq;
-    if (tid == 0) s_run = 0;
-    __syncthreads();
-    for (int q0 = 0; q0 < nq; q0 += 1024) {
-        const int q = q0 + tid;
-        const int64_t v = q < nq ? (int64_t)c[q] : 0;
-        int64_t x = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int64_t y = __shfl_up(x, d);
-            if (lane >= d) x += y;
-        }
-        if (lane == 63) s_w[wv] = x;
-        __syncthreads();
-        int64_t base = s_run;
-        for (int k = 0; k < wv; ++k) base += s_w[k];
-        if (q < nq) o[q] = base + x - v;
-        __syncthreads();
-        if (tid == 1023) s_run = base + x;
-        __syncthreads();
-    }
-    if (tid == 0) {
-        totals[w] = s_run;
-        if (s_run > stride) atomicExch(overflow, 1);
-    }
-}
-
-extern "C" int cis_exchange_offsets_dev(const int32_t* d_cnt_all, int world, int nq, int64_t stride, int64_t* d_off, int64_t* d_totals,
-                                        int32_t* d_overflow, void* stream) {
-    CIS_REQUIRE(world >= 1 && nq >= 0 && stride >= 0, "bad exchange arguments");
-    CIS_REQUIRE(d_totals && d_overflow && (nq == 0 || (d_cnt_all && d_off)), "NULL buffer");  // (nq = 0: empty [world][0] arrays)
-    CIS_TRY(cis_lazy_init());
-    hipStream_t st = (hipStream_t)stream;
-    CIS_CHECK_HIP(hipMemsetAsync(d_overflow, 0, sizeof(int32_t), st));
-    hipLaunchKernelGGL(k_exchange_offsets, dim3((unsigned)world), dim3(1024), 0, st, d_cnt_all, nq, stride, d_off, d_totals, d_overflow);
-    CIS_CHECK_HIP(hipGetLastError());
-    return CIS_OK;
-}
-
-extern "C" int cis_merge_packed_dev(const cis_hit* d_parts, int world, int64_t stride, const int64_t* d_off,
-                                    const int32_t* d_cnt, int nq, int limit, int64_t* d_ids, double* d_dists,
-                                    int32_t* d_n_found, int32_t* d_cells, uint32_t* d_pos, void* stream) {
-    CIS_REQUIRE(world >= 1 && nq >= 0 && limit >= 0 && limit <= MAX_LIMIT && stride >= 0, "bad merge arguments");
-    CIS_REQUIRE(nq == 0 || limit == 0 || (d_parts && d_off && d_cnt && d_ids && d_dists), "NULL buffer");
-    CIS_TRY(cis_lazy_init());
-    if (nq == 0 || limit == 0) return CIS_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 g((unsigned)ceil_div(nq, 4));
-    if (limit <= 128)
-        hipLaunchKernelGGL((k_merge_packed<256, 4>), g, dim3(256), (size_t)4 * 3 * 256 * 8, st, d_parts, world, stride, d_off, d_cnt, nq, limit,
-                           d_ids, d_dists, d_n_found, d_cells, d_pos);
-    else if (limit <= 512)
-        hipLaunchKernelGGL((k_merge_packed<1024, 4>), g, dim3(256), (size_t)4 * 3 * 1024 * 8, st, d_parts, world, stride, d_off, d_cnt, nq,
-                           limit, d_ids, d_dists, d_n_found, d_cells, d_pos);
-    else if (limit <= 3072)  // one wave per workgroup with 96 KB of LDS: 4096 keys per round, `limit` of them carried over
-        hipLaunchKernelGGL((k_merge_packed<4096, 1>), dim3((unsigned)nq), dim3(64), (size_t)3 * 4096 * 8, st, d_parts, world, stride, d_off,
-                           d_cnt, nq, limit, d_ids, d_dists, d_n_found, d_cells, d_pos);
-    else  // any limit: places by binary search in the other shards' ranked lists
-        hipLaunchKernelGGL(k_merge_packed_ranked, dim3((unsigned)nq), dim3(256), 0, st, d_parts, world, stride, d_off, d_cnt, nq, limit,
-                           d_ids, d_dists, d_n_found, d_cells, d_pos);
-    CIS_CHECK_HIP(hipGetLastError());
-    return CIS_OK;
-}
-
-// ---- exact re-ranking with resident features (searcher_lopqhbase.py:864-912): true L2 distance of a query to the
-// original features of its first `L` results.  One wave per (query, result); arithmetic in the feature dtype like
-// np.linalg.norm(normed_feat - res_fts[pos]) (float32 features -> float32 distance), returned as float64.
-template <typename T>
-__global__ __launch_bounds__(256) void k_rerank(const T* __restrict__ feats, int64_t n_feats, int D, const T* __restrict__ Q,
-                                                const int64_t* __restrict__ rows, int64_t n_pairs, int L,
-                                                double* __restrict__ dists) {
-    const int lane = threadIdx.x & 63;
-    const int64_t pair = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (pair >= n_pairs) return;
-    const int64_t r = rows[pair];
-    if (r < 0 || r >= n_feats) {  // feature not resident: the caller keeps the ADC distance (reference :889-893)
-        if (lane == 0) dists[pair] = __longlong_as_double(0x7ff8000000000000LL);
-        return;
-    }
-    const T* x = feats + r * D;
-    const T* q = Q + (pair / L) * D;
-    T acc = (T)0;
-    for (int i = lane; i < D; i += 64) {
-        const T df = q[i] - x[i];
-        acc = fma(df, df, acc);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc = acc + __shfl_xor(acc, o);
-    if (lane == 0) dists[pair] = (double)(T)sqrt(acc);
-}
-
-extern "C" int cis_rerank_dev(const void* d_feats, int f_dtype, int64_t n_feats, int D, const void* d_q, int nq,
-                              const int64_t* d_rows, int L, double* d_dists, void* stream) {
-    CIS_REQUIRE(f_dtype == CIS_F32 || f_dtype == CIS_F64, "f_dtype must be 4 or 8");
-    CIS_REQUIRE(n_feats >= 0 && D > 0 && nq >= 0 && L >= 0, "bad re-ranking arguments");
-    if (nq == 0 || L == 0) return CIS_OK;
-    CIS_REQUIRE(d_feats && d_q && d_rows && d_dists, "NULL buffer");
-    CIS_TRY(cis_lazy_init());
-    const int64_t n_pairs = (int64_t)nq * L;
-    const dim3 g((unsigned)ceil_div(n_pairs, 4));
-    hipStream_t st = (hipStream_t)stream;
-    if (f_dtype == CIS_F32)
-        hipLaunchKernelGGL(k_rerank<float>, g, dim3(256), 0, st, (const float*)d_feats, n_feats, D, (const float*)d_q, d_rows, n_pairs, L, d_dists);
-    else
-        hipLaunchKernelGGL(k_rerank<double>, g, dim3(256), 0, st, (const double*)d_feats, n_feats, D, (const double*)d_q, d_rows, n_pairs, L, d_dists);
-    CIS_CHECK_HIP(hipGetLastError());
-    return CIS_OK;
-}
-
-extern "C" int cis_merge_hits_dev(const cis_hit* d_parts, int world, int nq, int limit, int64_t* d_ids,
-                                  double* d_dists, int32_t* d_n_found, int32_t* d_cells, uint32_t* d_pos,
-                                  void* stream) {
-    CIS_REQUIRE(world >= 1 && nq >= 0 && limit >= 0 && limit <= MAX_LDS_LIMIT, "bad merge arguments (limit <= 3072)");
-    CIS_TRY(cis_lazy_init());
-    return merge_parts(d_parts, world, nq, limit, d_ids, d_dists, d_n_found, d_cells, d_pos, (hipStream_t)stream);
-}
-
 extern "C" int cis_index_search_dev(cis_index* ix, const void* dQ, int q_dtype, int nq, int64_t quota, int limit,
                                     int64_t* d_ids, double* d_dists, int32_t* d_n_found, int32_t* d_visited,
                                     int32_t* d_cells, uint32_t* d_pos, void* stream) {
@@ -6197,191 +5769,4 @@ extern "C" int cis_index_search_dev(cis_index* ix, const void* dQ, int q_dtype, 
     o.ids = d_ids; o.dists = d_dists; o.n_found = d_n_found; o.cells = d_cells; o.pos = d_pos; o.visited = d_visited;
     if (L == 0 && d_n_found) CIS_CHECK_HIP(hipMemsetAsync(d_n_found, 0, (size_t)nq * sizeof(int32_t), (hipStream_t)stream));
     return search_all(ix, dQ, q_dtype, nq, quota, L, o, (hipStream_t)stream);
-}
-
-// ---- host-pointer entry points: asynchronous form + pinned memory ------------------------------------------------------------
-// The reference's callers hold their queries and want their results in HOST memory (searcher_lopqhbase.py:849-857).  Rounds 1-4 moved
-// them with blocking hipMemcpy on the null stream around the search and a device-wide synchronisation: pageable copies are staged page
-// by page, nothing overlapped, and a batch through this door ran at 31 % of the resident rate.  Now every handle owns a stream:
-// cis_index_search_async enqueues copy-in, search and copy-out on it and returns as soon as the search's own launches are queued (the
-// plan read-back in the middle of a large batch still waits ~0.1 ms); cis_index_search_wait blocks until the results have landed.
-// With the buffers in pinned memory (cis_host_alloc) the copies are DMA transfers that overlap the searches of the other handles --
-// views of one index (cis_index_create_view) give several batches in flight.
-static std::mutex g_copy_mu;
-static hipStream_t g_copy_stream[64] = {nullptr};
-static int cis_copy_stream(int device, hipStream_t* out) {
-    std::lock_guard<std::mutex> lk(g_copy_mu);
-    const int d = device & 63;
-    if (!g_copy_stream[d]) CIS_CHECK_HIP(hipStreamCreateWithFlags(&g_copy_stream[d], hipStreamNonBlocking));
-    *out = g_copy_stream[d];
-    return CIS_OK;
-}
-
-// Copy-outs ahead of their wait (round 6).  cis_index_search_wait used to enqueue its handle's copy-out and block for it: 13 MB of
-// results of a C4 batch are 0.25 ms during which the calling thread launched nothing -- with the plan read-back of the next launch that
-// made the host the bottleneck of the host-facing path (0.57 ms per step against 0.375 ms resident).  Now every call that holds the copy
-// stream's lock looks at the OTHER handles with a search in flight: where the search has finished (hipEventQuery) the copy-out goes onto
-// the copy stream there and then, and runs while the caller launches its own batch; the owner's wait finds it under way or landed.
-static std::vector<cis_index*> g_host_pending;  // guarded by g_copy_mu: search enqueued, copy-out not yet
-
-static hipError_t host_copy_out_locked(cis_index* ix, hipStream_t cp) {
-    const cis_index::HostOut& o = ix->h_out;
-    const int nq = o.nq, L = o.L;
-    hipError_t e = hipSuccess;
-    auto cpy = [&](void* dst, const void* src, size_t bytes) { if (e == hipSuccess && dst) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, cp); };
-    if (nq > 0) {
-        if (L > 0) {
-            cpy(o.ids, ix->w_oids.p, (size_t)nq * L * sizeof(int64_t));
-            cpy(o.dists, ix->w_odists.p, (size_t)nq * L * sizeof(double));
-            cpy(o.cells, ix->w_ocell.p, (size_t)nq * L * sizeof(int32_t));
-            cpy(o.pos, ix->w_opos.p, (size_t)nq * L * sizeof(uint32_t));
-        }
-        cpy(o.n_found, ix->w_onf.p, (size_t)nq * sizeof(int32_t));
-        cpy(o.visited, ix->w_ovis.p, (size_t)nq * sizeof(int32_t));
-    }
-    if (e == hipSuccess) e = hipEventRecord(ix->h_ev_done, cp);
-    if (e == hipSuccess) ix->h_out_enqueued = true;
-    return e;
-}
-
-static void host_pump_locked(int device, hipStream_t cp, const cis_index* self) {
-    for (size_t i = 0; i < g_host_pending.size();) {
-        cis_index* o = g_host_pending[i];
-        if (o != self && o->m->device == device && hipEventQuery(o->h_ev_out) == hipSuccess && host_copy_out_locked(o, cp) == hipSuccess) {
-            g_host_pending[i] = g_host_pending.back();
-            g_host_pending.pop_back();
-        } else {
-            ++i;
-        }
-    }
-    (void)hipGetLastError();  // (hipEventQuery's hipErrorNotReady is not an error of this call)
-}
-
-void cis_host_forget(cis_index* ix) {
-    std::lock_guard<std::mutex> lk(g_copy_mu);
-    g_host_pending.erase(std::remove(g_host_pending.begin(), g_host_pending.end(), ix), g_host_pending.end());
-}
-
-extern "C" int cis_host_alloc(void** out, size_t bytes) {
-    CIS_REQUIRE(out != nullptr, "out is NULL");
-    *out = nullptr;
-    CIS_TRY(cis_lazy_init());
-    hipError_t e = hipHostMalloc(out, bytes > 0 ? bytes : 1, hipHostMallocDefault);
-    if (e != hipSuccess) {
-        cis_set_error("hipHostMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-        *out = nullptr;
-        return CIS_ENOMEM;
-    }
-    return CIS_OK;
-}
-
-extern "C" void cis_host_free(void* p) {
-    if (p) (void)hipHostFree(p);
-}
-
-extern "C" int cis_index_search_wait(cis_index* ix);
-
-extern "C" int cis_index_search_async(cis_index* ix, const void* Q, int q_dtype, int nq, int64_t quota, int limit,
-                                      int64_t* ids, double* dists, int32_t* n_found, int32_t* visited, int32_t* cells,
-                                      uint32_t* pos) {
-    CIS_REQUIRE(ix != nullptr, "index is NULL");
-    CIS_REQUIRE(q_dtype == CIS_F32 || q_dtype == CIS_F64, "q_dtype must be 4 or 8");
-    int L;
-    CIS_TRY(effective_limit(quota, limit, &L));
-    if (nq == 0) return CIS_OK;
-    CIS_REQUIRE(Q && n_found && visited && (L == 0 || (ids && dists)), "NULL buffer");
-    CIS_TRY(cis_lazy_init());
-    CIS_CHECK_HIP(hipSetDevice(ix->m->device));
-    // (the copy stream is made before the first handle's stream: the GPU dispatches from four hardware pipes, streams are dealt onto them
-    // in the order they first submit work, and two compute streams on one pipe do not overlap -- with the copy stream first, the fourth
-    // handle's stream shares a pipe with it and not with the first handle's: tools/r06_queue_probe.py)
-    hipStream_t cp = nullptr;
-    CIS_TRY(cis_copy_stream(ix->m->device, &cp));
-    if (!ix->h_stream) {
-        CIS_CHECK_HIP(hipStreamCreateWithFlags(&ix->h_stream, hipStreamNonBlocking));
-        CIS_CHECK_HIP(hipEventCreateWithFlags(&ix->h_ev_in, hipEventDisableTiming));
-        CIS_CHECK_HIP(hipEventCreateWithFlags(&ix->h_ev_out, hipEventDisableTiming));
-        CIS_CHECK_HIP(hipEventCreateWithFlags(&ix->h_ev_done, hipEventDisableTiming));
-    }
-    hipStream_t st = ix->h_stream;
-    // Every copy of every handle goes through ONE copy stream per device: a copy-in and a copy-out that run at the same time collapse
-    // on this platform (measured with pinned memory: 52-56 GB/s in either direction alone, 11 GB/s combined when both run --
-    // profiles/archive/r05b/r05_pcie_probe.txt), so the copies are serialised among themselves and overlap only the searches.
-    if (ix->h_pending) CIS_TRY(cis_index_search_wait(ix));  // one batch in flight per handle: its buffers are this handle's workspaces
-    const size_t qbytes = (size_t)nq * ix->m->D_in * q_dtype;
-    const int Lk = L > 0 ? L : 1;
-    CIS_TRY(ix->w_q.reserve(qbytes));
-    CIS_TRY(ix->w_oids.reserve((size_t)nq * Lk * sizeof(int64_t)));
-    CIS_TRY(ix->w_odists.reserve((size_t)nq * Lk * sizeof(double)));
-    CIS_TRY(ix->w_onf.reserve((size_t)nq * sizeof(int32_t)));
-    CIS_TRY(ix->w_ovis.reserve((size_t)nq * sizeof(int32_t)));
-    CIS_TRY(ix->w_ocell.reserve((size_t)nq * Lk * sizeof(int32_t)));
-    CIS_TRY(ix->w_opos.reserve((size_t)nq * Lk * sizeof(uint32_t)));
-    {
-        std::lock_guard<std::mutex> lk(g_copy_mu);  // (enqueue order on the shared stream: a handle's copy and its event stay adjacent)
-        CIS_CHECK_HIP(hipMemcpyAsync(ix->w_q.p, Q, qbytes, hipMemcpyHostToDevice, cp));
-        CIS_CHECK_HIP(hipEventRecord(ix->h_ev_in, cp));
-        // finished searches of the other handles: their results leave BEHIND this copy-in (4 MB against 13 MB: the launch below blocks
-        // on this batch's plan read-back, which waits for the copy-in)
-        host_pump_locked(ix->m->device, cp, ix);
-    }
-    // h_pending is set LAST, with this batch's h_out in place: an error exit in between must not leave the flag set over the previous
-    // call's h_out (whose host buffers may be gone) -- cis_index_search_wait / cis_index_destroy would copy results into them.  Every
-    // error exit below drains the stream (the copy-in may still be reading Q) and leaves the handle idle.
-    struct Guard {
-        cis_index* ix; hipStream_t st; bool armed;
-        ~Guard() { if (armed) { (void)hipStreamSynchronize(st); ix->h_pending = false; ix->h_out = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0}; } }
-    } guard{ix, st, true};
-    CIS_CHECK_HIP(hipStreamWaitEvent(st, ix->h_ev_in, 0));
-    int rc = cis_index_search_dev(ix, ix->w_q.p, q_dtype, nq, quota, limit, ix->w_oids.as<int64_t>(),
-                                  ix->w_odists.as<double>(), ix->w_onf.as<int32_t>(), ix->w_ovis.as<int32_t>(),
-                                  ix->w_ocell.as<int32_t>(), ix->w_opos.as<uint32_t>(), st);
-    if (rc != CIS_OK) return rc;
-    CIS_CHECK_HIP(hipEventRecord(ix->h_ev_out, st));
-    // the copy-out is enqueued by cis_index_search_wait, once the search has finished: enqueued here it would sit at the head of the
-    // shared copy stream, waiting for the search, with every later copy-in of the other handles stuck behind it
-    ix->h_out = {ids, dists, n_found, visited, cells, pos, nq, L};
-    ix->h_out_enqueued = false;
-    ix->h_pending = true;
-    guard.armed = false;
-    {
-        // (no copy-outs from here: one enqueued now would be in the next call's copy-in's way -- that call's launch blocks on its plan
-        // read-back, the read-back waits for the copy-in, and the copy stream is first in, first out)
-        std::lock_guard<std::mutex> lk(g_copy_mu);
-        g_host_pending.push_back(ix);
-    }
-    return CIS_OK;
-}
-
-extern "C" int cis_index_search_wait(cis_index* ix) {
-    CIS_REQUIRE(ix != nullptr, "index is NULL");
-    if (ix->h_stream && ix->h_pending) {
-        CIS_CHECK_HIP(hipSetDevice(ix->m->device));
-        ix->h_pending = false;
-        hipStream_t cp = nullptr;
-        CIS_TRY(cis_copy_stream(ix->m->device, &cp));
-        bool enq;
-        {
-            std::lock_guard<std::mutex> lk(g_copy_mu);
-            enq = ix->h_out_enqueued;   // another handle's call may have put this handle's copy-out on the copy stream already
-        }
-        if (!enq) {
-            CIS_CHECK_HIP(hipEventSynchronize(ix->h_ev_out));
-            std::lock_guard<std::mutex> lk(g_copy_mu);
-            if (!ix->h_out_enqueued) {
-                g_host_pending.erase(std::remove(g_host_pending.begin(), g_host_pending.end(), ix), g_host_pending.end());
-                CIS_CHECK_HIP(host_copy_out_locked(ix, cp));
-            }
-            host_pump_locked(ix->m->device, cp, ix);
-        }
-        CIS_CHECK_HIP(hipEventSynchronize(ix->h_ev_done));
-    }
-    return CIS_OK;
-}
-
-extern "C" int cis_index_search(cis_index* ix, const void* Q, int q_dtype, int nq, int64_t quota, int limit,
-                                int64_t* ids, double* dists, int32_t* n_found, int32_t* visited, int32_t* cells,
-                                uint32_t* pos) {
-    CIS_TRY(cis_index_search_async(ix, Q, q_dtype, nq, quota, limit, ids, dists, n_found, visited, cells, pos));
-    return cis_index_search_wait(ix);
 }

@@ -1,5 +1,6 @@
 // Device helpers shared by the ADC scan kernels (lopq_search.hip: float32-prefilter scan; lopq_scan3.hip: 16-bit
-// fixed-point scan): work-item layout, wave-level primitives on the VALU only, code loads, exact re-scoring.
+// fixed-point scan): work-item layout, wave-level primitives on the VALU only, code loads, exact re-scoring; and by the
+// merges of ranked hit lists (lopq_search.hip, lopq_exchange.hip).
 #pragma once
 #include "lopq_model.h"
 
@@ -280,3 +281,103 @@ size_t scan5_workspace_bytes(int nq);
 void launch_scan5(int M, const Scan3Geom& g, int64_t n_items, int nq, hipStream_t st, const WorkItem* items, const TabDesc* tabs, const int* slots,
                   const int* n_slots, const PlanOut* plan, const double* T, const float* T32, const uint8_t* codes, int K, int L, int* qctr, uint64_t* hits,
                   int* hitn, float* slack, unsigned long long* qbound, int* fhdr, int* fslots, void* ws, hipEvent_t ev_main);
+
+// ---- merges of ranked hit lists: the work items of a query (lopq_search.hip), the shards' partial results (lopq_exchange.hip) ----
+// block-wide bitonic sort of N (a power of two, chosen at run time) keys (a, b) with an optional payload, in LDS: the merge sorts
+// only as many slots as it actually filled
+template <int NT, bool PAY>
+__device__ __forceinline__ void block_bitonic_rt(uint64_t* ka, uint64_t* kb, int64_t* pay, int N) {
+    for (int k = 2; k <= N; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = threadIdx.x; t < N / 2; t += NT) {
+                const int i = ((t / j) * 2 * j) + (t % j);
+                const int p = i + j;
+                const bool asc = ((i & k) == 0);
+                const uint64_t a0 = ka[i], b0 = kb[i], a1 = ka[p], b1 = kb[p];
+                const bool gt = (a0 > a1) || (a0 == a1 && b0 > b1);
+                if (gt == asc) {
+                    ka[i] = a1; kb[i] = b1; ka[p] = a0; kb[p] = b0;
+                    if (PAY) { const int64_t x = pay[i]; pay[i] = pay[p]; pay[p] = x; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// ================================================================================================
+// kernel: per-query merge of ranked lists -> top `limit` by (dist, visit_rank, pos)
+// ================================================================================================
+// Lists of query q: entries src[lo .. hi) in groups: list l has `stride` slots of which cnt[l]
+// are valid (cnt == nullptr: a slot is valid when id >= 0).  Used twice: (a) merging the work
+// items of a query, (b) merging the per-shard partial results after the all-gather.
+template <int CAPM>
+__device__ void merge_lists(const cis_hit* __restrict__ src, const int* __restrict__ cnt, int64_t first_list,
+                            int n_lists, int64_t list_stride /* distance between lists, in hits */,
+                            int slots, int limit, uint64_t* ka, uint64_t* kb, int64_t* pay, int* s_n,
+                            cis_hit* __restrict__ out_hits /* [limit] or null */, int64_t* __restrict__ out_ids,
+                            double* __restrict__ out_dists, int* __restrict__ out_n, int32_t* __restrict__ out_cells,
+                            uint32_t* __restrict__ out_pos) {
+    const int tid = threadIdx.x;
+    int have = 0;      // sorted survivors currently in [0, have)
+    int l = 0, e = 0;  // cursor: list l, entry e (uniform over the block)
+    // rounds: append up to CAPM - have entries, sort, keep `limit`.  pay = index of the hit in src.
+    while (true) {
+        int n = have;
+        int room = CAPM - have;
+        while (l < n_lists && room > 0) {
+            const int64_t lbase = (first_list + l) * list_stride;
+            const int valid = cnt ? cnt[first_list + l] : slots;
+            const int take = (valid - e < room) ? (valid - e) : room;
+            for (int x = tid; x < take; x += blockDim.x) {
+                const cis_hit hh = src[lbase + e + x];
+                const bool ok = hh.id >= 0;
+                ka[n + x] = ok ? (uint64_t)__double_as_longlong(hh.dist) : ~0ull;
+                kb[n + x] = ok ? (((uint64_t)hh.visit_rank << 32) | hh.pos) : ~0ull;
+                pay[n + x] = ok ? (lbase + e + x) : -1;
+            }
+            n += take;
+            room -= take;
+            e += take;
+            if (e >= valid) { ++l; e = 0; }
+        }
+        int ns = 64;  // sort only the next power of two above what was filled
+        while (ns < n) ns <<= 1;
+        for (int x = n + tid; x < ns; x += blockDim.x) { ka[x] = ~0ull; kb[x] = ~0ull; pay[x] = -1; }
+        __syncthreads();
+        block_bitonic_rt<256, true>(ka, kb, pay, ns);
+        have = n < limit ? n : limit;
+        if (l >= n_lists) break;
+    }
+    // empty slots (id < 0) carry all-ones keys and therefore sit behind every real hit
+    if (tid == 0) *s_n = 0;
+    __syncthreads();
+    int local = 0;
+    for (int x = tid; x < have; x += blockDim.x) local += (pay[x] >= 0) ? 1 : 0;
+    if (local) atomicAdd(s_n, local);
+    __syncthreads();
+    const int nv = *s_n;
+    for (int x = tid; x < limit; x += blockDim.x) {
+        cis_hit hh;
+        if (x < nv) {
+            hh = src[pay[x]];
+        } else {
+            hh.dist = __longlong_as_double(0x7ff0000000000000LL);
+            hh.visit_rank = 0xffffffffu; hh.pos = 0xffffffffu; hh.id = -1; hh.cell = -1; hh.reserved = 0;
+        }
+        if (out_hits) out_hits[x] = hh;
+        if (out_ids) {
+            out_ids[x] = hh.id;
+            out_dists[x] = (x < nv) ? hh.dist : __longlong_as_double(0x7ff8000000000000LL);
+        }
+        if (out_cells) out_cells[x] = hh.cell;
+        if (out_pos) out_pos[x] = hh.pos;
+    }
+    if (tid == 0 && out_n) *out_n = nv;
+}
+
+static __device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
