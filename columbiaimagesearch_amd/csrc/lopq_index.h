@@ -1,5 +1,5 @@
-// Internal view of the LOPQ index handle, shared by lopq_index.hip (storage: device-side insert), lopq_search.hip
-// (search pipeline), lopq_exchange.hip (cell-sharded exchange) and lopq_host.hip (host-pointer entry points).
+// Internal view of the LOPQ index handle, shared by lopq_index.hip (storage: device-side insert), lopq_search.hip and lopq_plan.hip
+// (search pipeline and its plan stage), lopq_exchange.hip (cell-sharded exchange) and lopq_host.hip (host-pointer entry points).
 //
 // The index lives in HBM and only there.  Inserts -- from host arrays (cis_index_add) or from device arrays
 // (cis_index_add_dev) -- are merged into the cell-contiguous arrays by kernels (lopq_index.hip); the host keeps no copy

@@ -1,6 +1,7 @@
 // Device helpers shared by the ADC scan kernels (lopq_search.hip: float32-prefilter scan; lopq_scan3.hip: 16-bit
 // fixed-point scan): work-item layout, wave-level primitives on the VALU only, code loads, exact re-scoring; and by the
-// merges of ranked hit lists (lopq_search.hip, lopq_exchange.hip).
+// merges of ranked hit lists (lopq_search.hip, lopq_exchange.hip); the work item, table and plan records the plan stage
+// (lopq_plan.hip) writes for them.
 #pragma once
 #include "lopq_model.h"
 
@@ -23,6 +24,10 @@ struct PlanOut {  // per query
     int visited, n_items, ntab0, ntab1;
     int64_t ncand;
 };
+
+// distances are >= 0, so their bit patterns order like the values
+static __device__ __forceinline__ uint64_t f2bits(double d) { return (uint64_t)__double_as_longlong(d); }
+static __device__ __forceinline__ uint64_t f2bits(float f) { return (uint64_t)__float_as_uint(f); }
 
 // value of lane (l ^ LJ) for every lane l, on the VALU only (DPP / permlane swaps): the LDS pipe is the
 // scan's bottleneck, so the in-register sorts must not use ds_bpermute.

@@ -30,7 +30,7 @@ def test_pmc_source_names_a_stale_summary(tmp_path):
     sys.path.insert(0, os.path.join(REPO, "tools"))
     from pmc_stamp import kernel_sources_sha1
     have = kernel_sources_sha1()
-    assert set(have) >= {"lopq_scan3.hip", "lopq_search.hip", "lopq_stream.hip"} and all(v and len(v) == 40 for v in have.values())
+    assert set(have) >= {"lopq_scan3.hip", "lopq_search.hip", "lopq_plan.hip", "lopq_stream.hip"} and all(v and len(v) == 40 for v in have.values())
     p = os.path.join(REPO, "profiles", "scan_binding_c4.json")
     fresh = {"kernel": "void k_adc_scan4<8, 2, 4, 4, 1016>", "commit": "abc", "kernel_sources_sha1": dict(have)}
     s = bench.pmc_source(p, fresh)

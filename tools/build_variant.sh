@@ -1,5 +1,6 @@
 #!/bin/bash
 # usage: tools/build_variant.sh NAME "-DFLAG ..." [source stem, default lopq_search]  -> columbiaimagesearch_amd/lib/libcis_NAME.so
+# The stem names the file that reads the flag: lopq_plan for the plan's switches (CIS_PLAN_DBG, CIS_PLAN_WPE), lopq_scan3, lopq_stream, ...
 # A build of the library with ONE source file compiled with extra flags (A/B experiments, tools/gpu_ab.sh).
 set -e
 cd "$(dirname "$0")/../columbiaimagesearch_amd/csrc"

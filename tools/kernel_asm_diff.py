@@ -2,7 +2,7 @@
 the kernel of the same name in the listings after it (make -C columbiaimagesearch_amd/csrc build/x.s).  Compared per kernel: the
 instruction text of the body, the .amdhsa_* descriptor and the register / spill / scratch / LDS figures of the metadata; only local
 label numbers, line-info directives and comments are normalised.  Exit status 1 when a kernel is missing, new or different.
-usage: kernel_asm_diff.py old/lopq_search.s -- new/lopq_search.s new/lopq_exchange.s new/lopq_host.s"""
+usage: kernel_asm_diff.py old/lopq_search.s -- new/lopq_search.s new/lopq_plan.s"""
 import difflib, re, sys
 
 META = r"^    \.(vgpr_spill_count|sgpr_spill_count|vgpr_count|agpr_count|sgpr_count|private_segment_fixed_size|group_segment_fixed_size|max_flat_workgroup_size):"

@@ -13,7 +13,7 @@ import subprocess
 import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNEL_SOURCES = ("lopq_scan3.hip", "lopq_search.hip", "lopq_stream.hip", "scan_common.h", "common.h")
+KERNEL_SOURCES = ("lopq_scan3.hip", "lopq_search.hip", "lopq_plan.hip", "lopq_stream.hip", "lopq_batch.h", "scan_common.h", "common.h")
 
 
 def kernel_sources_sha1():
