@@ -15,27 +15,6 @@ static const int GRP_SUB = 32;
 
 static const int PLAN_PAR_STAGE = 4096; // d0 / d1 staged in LDS: the kernel takes V <= 4096
 
-struct SearchOut {  // any of these may be null; all are [nq][L] except n_found / visited [nq]
-    cis_hit* hits;
-    int64_t* ids;
-    double* dists;
-    int32_t* n_found;
-    int32_t* cells;
-    uint32_t* pos;
-    int32_t* visited;
-    SearchOut at(int64_t q0, int L) const {
-        SearchOut o = *this;
-        if (o.hits) o.hits += q0 * L;
-        if (o.ids) o.ids += q0 * L;
-        if (o.dists) o.dists += q0 * L;
-        if (o.cells) o.cells += q0 * L;
-        if (o.pos) o.pos += q0 * L;
-        if (o.n_found) o.n_found += q0;
-        if (o.visited) o.visited += q0;
-        return o;
-    }
-};
-
 // ---- front end: LOPQ-space queries, coarse type, the rank workspaces (the batch search and the owner walk of the routed search) ----
 struct Front {
     const void* xc;  // the queries as the coarse quantizers read them

@@ -2468,10 +2468,24 @@ bool scan5_supported(int M, int K, int L) { return (M == 4 || M == 8) && K <= 25
 static const int S5_B = 512;
 size_t scan5_workspace_bytes(int nq) { return (size_t)nq * S5_B * 4 + (size_t)nq * 4 * 4 + 256; }
 
+// k_adc_scan3 over the batch's slot list in the form g.two_pass, or (fallback) over the slots a sampled form could not settle -- a second
+// slot header (fhdr: queue counters [0..7], queue starts [16..24] of which only [17] = count is used): the two-pass form for short chunks,
+// the streaming form for long ones
 template <int M, int NR>
-static void launch_scan5_t(const Scan3Geom& g, int64_t n_items, int nq, hipStream_t st, const WorkItem* items, const TabDesc* tabs, const int* slots,
-                           const int* n_slots, const PlanOut* plan, const double* T, const float* T32, const uint8_t* codes, int K, int L, int* qctr,
-                           uint64_t* hits, int* hitn, float* slack, unsigned long long* qbound, int* fhdr, int* fslots, void* ws, hipEvent_t ev_main) {
+static void launch_scan3_k(const Scan3Geom& g, const ScanArgs& a, bool fallback) {
+    // waves per SIMD the kernel is compiled for (register budget): what the LDS footprint lets a CU hold anyway
+    constexpr int U = 4, NW = 4;  // (U = 2 at 5 waves per SIMD measured slower: 0.535 against 0.497 ms on c4)
+    constexpr int WPE = M == 16 ? 3 : 4;
+    const int by_lds = (int)(163840 / g.lds), by_waves = (WPE * 4) / NW;
+    const unsigned grid = fallback ? 256u : persistent_grid(a, g.G, by_lds < by_waves ? by_lds : by_waves);
+    hipLaunchKernelGGL((k_adc_scan3<M, NR, U, NW, WPE>), dim3(grid), dim3(NW * 64), g.lds, a.st, a.items, a.tabs, fallback ? a.fslots : a.slots,
+                       fallback ? a.fhdr + 8 : a.n_slots, a.T, a.T32, a.codes, a.K, a.L, g.S, fallback ? a.fhdr : a.qctr, a.hits, a.hitn, a.slack, a.qbound,
+                       fallback ? (g.long_chunks ? 0 : 1) : g.two_pass, fallback ? 1 : 0);
+}
+
+template <int M, int NR>
+static void launch_scan5_t(const Scan3Geom& g, const ScanArgs& a, void* ws) {
+    const int nq = a.nq;
     uint32_t* bmin = reinterpret_cast<uint32_t*>(ws);
     int* ints = reinterpret_cast<int*>(bmin + (size_t)nq * S5_B);
     int* nsamp = ints;
@@ -2479,47 +2493,36 @@ static void launch_scan5_t(const Scan3Geom& g, int64_t n_items, int nq, hipStrea
     int* ovf = ints + 2 * nq;
     float* tau = reinterpret_cast<float*>(ints + 3 * nq);
     const int64_t n_b = (int64_t)nq * S5_B;
-    hipLaunchKernelGGL(k_scan5_init, dim3((unsigned)((n_b + 255) / 256)), dim3(256), 0, st, bmin, n_b, ints, 3 * nq);
-    (void)hipMemsetAsync(hitn, 0, (size_t)(n_items + 1) * sizeof(int), st);
+    hipLaunchKernelGGL(k_scan5_init, dim3((unsigned)((n_b + 255) / 256)), dim3(256), 0, a.st, bmin, n_b, ints, 3 * nq);
+    (void)hipMemsetAsync(a.hitn, 0, (size_t)(a.n_items + 1) * sizeof(int), a.st);
     constexpr int WPE = 4;
-    const size_t lds = scan5_lds(M, K);
+    const size_t lds = scan5_lds(M, a.K);
     const int by_lds = (int)(163840 / lds);
     const int per_cu = by_lds < WPE ? by_lds : WPE;
     const unsigned grid = 256u * (unsigned)(per_cu < 1 ? 1 : per_cu);
     static const int P_env = getenv("CIS_S5_P") ? atoi(getenv("CIS_S5_P")) : 0;
     static const int ss_env = getenv("CIS_S5_SS") ? atoi(getenv("CIS_S5_SS")) : 4;
-    const int P = P_env > 0 ? P_env : (L < 100 ? 240 : (int)(2.4 * L));
-    hipLaunchKernelGGL((k_adc_scan5<M, true, WPE>), dim3(grid), dim3(256), lds, st, items, tabs, slots, n_slots, T32, T, codes, K, g.S, (const float*)nullptr, bmin,
-                       S5_B, nsamp, ss_env, hits, hitn, slack, cnt_ok, ovf);
-    hipLaunchKernelGGL(k_scan5_tau<S5_B / 64>, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st, bmin, S5_B, nsamp, plan, nq, P, tau);
-    if (ev_main) (void)hipEventRecord(ev_main, st);
-    hipLaunchKernelGGL((k_adc_scan5<M, false, WPE>), dim3(grid), dim3(256), lds, st, items, tabs, slots, n_slots, T32, T, codes, K, g.S, tau, bmin, S5_B, nsamp,
-                       ss_env, hits, hitn, slack, cnt_ok, ovf);
-    const int64_t max_slots = n_items + 8;  // (an upper bound of the slot count: the kernel reads the real one)
-    hipLaunchKernelGGL(k_scan5_check, dim3((unsigned)((max_slots + 255) / 256)), dim3(256), 0, st, slots, n_slots, items, plan, cnt_ok, ovf, L, fhdr, fslots, hitn,
-                       qctr + 9);
+    const int P = P_env > 0 ? P_env : (a.L < 100 ? 240 : (int)(2.4 * a.L));
+    auto pass = [&](auto sample, const float* thr) {
+        hipLaunchKernelGGL((k_adc_scan5<M, decltype(sample)::value, WPE>), dim3(grid), dim3(256), lds, a.st, a.items, a.tabs, a.slots, a.n_slots, a.T32, a.T, a.codes, a.K,
+                           g.S, thr, bmin, S5_B, nsamp, ss_env, a.hits, a.hitn, a.slack, cnt_ok, ovf);
+    };
+    pass(std::true_type{}, nullptr);
+    hipLaunchKernelGGL(k_scan5_tau<S5_B / 64>, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, a.st, bmin, S5_B, nsamp, a.plan, nq, P, tau);
+    pass(std::false_type{}, tau);
+    const int64_t max_slots = a.n_items + 8;  // (an upper bound of the slot count: the kernel reads the real one)
+    hipLaunchKernelGGL(k_scan5_check, dim3((unsigned)((max_slots + 255) / 256)), dim3(256), 0, a.st, a.slots, a.n_slots, a.items, a.plan, cnt_ok, ovf, a.L, a.fhdr, a.fslots,
+                       a.hitn, a.qctr + 9);
     if (getenv("CIS_SCAN5_DEBUG")) {
         int h[6] = {0, 0, 0, 0, 0, 0};
-        if (hipMemcpyAsync(h, qctr + 9, sizeof(h), hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess)
+        if (hipMemcpyAsync(h, a.qctr + 9, sizeof(h), hipMemcpyDeviceToHost, a.st) == hipSuccess && hipStreamSynchronize(a.st) == hipSuccess)
             fprintf(stderr, "[cis] k_adc_scan5: %d slots to the fall-back list\n", h[1]);
     }
-    // the slots it could not settle: k_adc_scan3's two-pass form for short chunks, its streaming form for long ones (as after k_adc_scan4)
-    constexpr int U = 4, NW = 4;
-    constexpr int WPE3 = 4;
-    hipLaunchKernelGGL((k_adc_scan3<M, NR, U, NW, WPE3>), dim3(256), dim3(NW * 64), g.lds, st, items, tabs, fslots, fhdr + 8, T, T32, codes, K, L, g.S, fhdr, hits, hitn,
-                       slack, qbound, g.long_chunks ? 0 : 1, 1);
+    launch_scan3_k<M, NR>(g, a, true);  // the slots it could not settle (as after k_adc_scan4)
 }
 
-void launch_scan5(int M, const Scan3Geom& g, int64_t n_items, int nq, hipStream_t st, const WorkItem* items, const TabDesc* tabs, const int* slots,
-                  const int* n_slots, const PlanOut* plan, const double* T, const float* T32, const uint8_t* codes, int K, int L, int* qctr, uint64_t* hits,
-                  int* hitn, float* slack, unsigned long long* qbound, int* fhdr, int* fslots, void* ws, hipEvent_t ev_main) {
-    if (M == 4) {
-        if (L <= 184) launch_scan5_t<4, 4>(g, n_items, nq, st, items, tabs, slots, n_slots, plan, T, T32, codes, K, L, qctr, hits, hitn, slack, qbound, fhdr, fslots, ws, ev_main);
-        else launch_scan5_t<4, 8>(g, n_items, nq, st, items, tabs, slots, n_slots, plan, T, T32, codes, K, L, qctr, hits, hitn, slack, qbound, fhdr, fslots, ws, ev_main);
-    } else {
-        if (L <= 184) launch_scan5_t<8, 4>(g, n_items, nq, st, items, tabs, slots, n_slots, plan, T, T32, codes, K, L, qctr, hits, hitn, slack, qbound, fhdr, fslots, ws, ev_main);
-        else launch_scan5_t<8, 8>(g, n_items, nq, st, items, tabs, slots, n_slots, plan, T, T32, codes, K, L, qctr, hits, hitn, slack, qbound, fhdr, fslots, ws, ev_main);
-    }
+void launch_scan5(int M, const Scan3Geom& g, const ScanArgs& a, void* ws) {  // (scan5_supported: M = 4 or 8, limit <= 440)
+    dispatch_int<4, 8>(M, [&](auto m) { dispatch_nr<8>(a.L, [&](auto nr) { launch_scan5_t<decltype(m)::value, decltype(nr)::value>(g, a, ws); }); });
 }
 
 bool scan3_supported(int M, int K, int L) {
@@ -2561,95 +2564,55 @@ Scan3Geom scan3_geom(int M, int K, int L, int64_t avg_chunk, int force_two_pass)
     return g;
 }
 
-template <int M, int NR, int NW>
-static void launch_scan3_t(const Scan3Geom& g, int64_t n_items, hipStream_t st, const WorkItem* items, const TabDesc* tabs,
-                           const int* slots, const int* n_slots, const double* T, const float* T32, const uint8_t* codes, int K,
-                           int L, int* qctr, uint64_t* hits, int* hitn, float* slack, unsigned long long* qbound, int* fhdr, int* fslots) {
-    // waves per SIMD the kernel is compiled for (register budget): what the LDS footprint lets a CU hold anyway
-    constexpr int U = 4;  // (U = 2 at 5 waves per SIMD measured slower: 0.535 against 0.497 ms on c4)
-    constexpr int WPE = M == 16 ? (NW == 4 ? 3 : 2) : (NW == 4 ? 4 : (NW == 2 ? 3 : 2));
-    const int by_lds = (int)(163840 / g.lds), by_waves = (WPE * 4) / NW;
-    const int per_cu = by_lds < by_waves ? by_lds : by_waves;
-    const int64_t resident = 256 * (per_cu < 1 ? 1 : per_cu);  // persistent grid: what the chip can hold
-    const int64_t want = (n_items + g.G - 1) / g.G + 8;
-    const unsigned grid = (unsigned)(want < resident ? ((want + 7) / 8) * 8 : resident);
-    if constexpr (NW == 4) {
-        if (g.two_pass == 2) {
-            // k_adc_scan4, then the slots it could not settle (normally none) through this kernel's two-pass form: the fall-back
-            // list is a second slot header (fhdr: queue counters [0..7], queue starts [16..24] of which only [17] = count is used)
-            // read per call (A/B runs and the fall-back tests set them between calls)
-            const float z_short = getenv("CIS_S4_ZS") ? (float)atof(getenv("CIS_S4_ZS")) : CIS_S4_Z;
-            // long chunks, measured on C4 (profiles/r03m_scan_long.txt): z 4 / 4.5 / 5 -> 0.326 / 0.332 / 0.335 ms, no verification
-            // failure in 100 k lists at z = 4; static schedule 0.301 against 0.326 ms with slots from a counter; one row in 8 / 10 /
-            // 16 as the sample -> 0.321 / 0.326 / 0.45 ms; at most 128 sample rows (64: the 65536-candidate chunks overflow their lists)
-            const float z_long = getenv("CIS_S4_ZL") ? (float)atof(getenv("CIS_S4_ZL")) : 4.5f;
-            const int frac_long = getenv("CIS_S4_FRAC") ? atoi(getenv("CIS_S4_FRAC")) : 8;
-            const int nsx_long = getenv("CIS_S4_NSX") ? atoi(getenv("CIS_S4_NSX")) : 128;
-            const int dyn_long = getenv("CIS_S4_DYN") ? atoi(getenv("CIS_S4_DYN")) : 0;
-            int* dbg4 = qctr + 9;
-            // waves per slot (NW4) and waves per SIMD the variant is compiled for (WPS): 4 x 64 threads at 4 (long chunks) / 6 (short) waves
-            // per SIMD were rounds 2-3; 8 waves per slot halve a slot's main pass, and three such workgroups per CU are 24 waves
-            const int nw4_long = getenv("CIS_S4_NWL") ? atoi(getenv("CIS_S4_NWL")) : CIS_S4_NW_LONG;
-            const int nw4_short = getenv("CIS_S4_NWS") ? atoi(getenv("CIS_S4_NWS")) : CIS_S4_NW_SHORT;
-            auto grid_of = [&](size_t lds4, int wps, int nw4) -> unsigned {
-                const int by_lds4 = (int)(163840 / lds4), by_waves4 = (wps * 4) / nw4;
-                int per_cu4 = by_lds4 < by_waves4 ? by_lds4 : by_waves4;
-                if (const char* e = getenv("CIS_S4_PER_CU")) per_cu4 = atoi(e) > 0 && atoi(e) < per_cu4 ? atoi(e) : per_cu4;  // A/B: room for other batches' kernels
-                const int64_t resident4 = 256 * (per_cu4 < 1 ? 1 : per_cu4);
-                return (unsigned)(want < resident4 ? ((want + 7) / 8) * 8 : resident4);
-            };
-            if (!g.long_chunks) {
-                constexpr int WPE4 = (M == 16) ? 4 : CIS_S4_WPE;  // (M = 16: 41 KB of LDS hold three workgroups per CU anyway)
-                if (nw4_short == 8 && M != 16) {
-                    const size_t lds4 = scan4_lds(M, K, S4_LCAP, 8);
-                    hipLaunchKernelGGL((k_adc_scan4<M, CIS_S4_U, 8, WPE4, S4_LCAP>), dim3(grid_of(lds4, WPE4, 8)), dim3(8 * 64), lds4, st, items, tabs, slots,
-                                       n_slots, T32, T, codes, K, L, g.S, dbg4, fhdr, fslots, hits, hitn, slack, qbound, z_short, 1 << 20, S4_NS, 0, g.sat);
-                } else {
-                    const size_t lds4 = scan4_lds(M, K, S4_LCAP, NW);
-                    hipLaunchKernelGGL((k_adc_scan4<M, CIS_S4_U, NW, WPE4, S4_LCAP>), dim3(grid_of(lds4, WPE4, NW)), dim3(NW * 64), lds4, st, items, tabs, slots,
-                                       n_slots, T32, T, codes, K, L, g.S, dbg4, fhdr, fslots, hits, hitn, slack, qbound, z_short, 1 << 20, S4_NS, 0, g.sat);
-                }
-            } else {
-                constexpr int WPE4 = (M == 16) ? 3 : ((CIS_S4_DEFER != 0 && CIS_S4_GLISTS != 0) ? CIS_S4_WPE_LONG : 4);  // (M = 16: 49 KB of LDS = three workgroups per CU, 168 registers)
-                if (nw4_long == 8 && M != 16) {
-                    constexpr int WPE8 = CIS_S4_WPE8;
-                    const size_t lds4 = scan4_lds(M, K, S4_LCAP_LONG, 8);
-                    hipLaunchKernelGGL((k_adc_scan4<M, CIS_S4_UL, 8, WPE8, S4_LCAP_LONG>), dim3(grid_of(lds4, WPE8, 8)), dim3(8 * 64), lds4, st, items, tabs, slots,
-                                       n_slots, T32, T, codes, K, L, g.S, dbg4, fhdr, fslots, hits, hitn, slack, qbound, z_long, frac_long, nsx_long, dyn_long, g.sat);
-                } else {
-                    const size_t lds4 = scan4_lds(M, K, S4_LCAP_LONG, NW);
-                    hipLaunchKernelGGL((k_adc_scan4<M, CIS_S4_UL, NW, WPE4, S4_LCAP_LONG>), dim3(grid_of(lds4, WPE4, NW)), dim3(NW * 64), lds4, st, items, tabs, slots,
-                                       n_slots, T32, T, codes, K, L, g.S, dbg4, fhdr, fslots, hits, hitn, slack, qbound, z_long, frac_long, nsx_long, dyn_long, g.sat);
-                }
-            }
-            if (getenv("CIS_SCAN4_DEBUG")) {  // diagnosis: how many slots the sample misjudged (blocks)
-                int h[6] = {0, 0, 0, 0, 0, 0};
-                if (hipMemcpyAsync(h, qctr + 9, sizeof(h), hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess)
-                    fprintf(stderr, "[cis] k_adc_scan4: %d slots, %d to the fall-back list (lists: %d overflowed, %d failed the verification, %d crowds at the cut; %d slots with items of different chunks)\n",
-                            h[0], h[1], h[2], h[3], h[4], h[5]);
-            }
-            // the slots it could not settle: the two-pass form for short chunks, the streaming form for long ones
-            hipLaunchKernelGGL((k_adc_scan3<M, NR, U, NW, WPE>), dim3(256), dim3(NW * 64), g.lds, st, items, tabs, fslots, fhdr + 8, T, T32,
-                               codes, K, L, g.S, fhdr, hits, hitn, slack, qbound, g.long_chunks ? 0 : 1, 1);
-            return;
-        }
-    }
-    hipLaunchKernelGGL((k_adc_scan3<M, NR, U, NW, WPE>), dim3(grid), dim3(NW * 64), g.lds, st, items, tabs, slots, n_slots, T, T32,
-                       codes, K, L, g.S, qctr, hits, hitn, slack, qbound, g.two_pass, 0);
+// k_adc_scan4 with NW waves per slot, compiled for WPE waves per SIMD, lists of LCAP entries per query
+template <int M, int U, int NW, int WPE, int LCAP>
+static void launch_scan4(const Scan3Geom& g, const ScanArgs& a, float z, int frac, int sample_rows, int dyn) {
+    const size_t lds = scan4_lds(M, a.K, LCAP, NW);
+    const int by_lds = (int)(163840 / lds), by_waves = (WPE * 4) / NW;
+    int per_cu = by_lds < by_waves ? by_lds : by_waves;
+    if (const char* e = getenv("CIS_S4_PER_CU")) per_cu = atoi(e) > 0 && atoi(e) < per_cu ? atoi(e) : per_cu;  // A/B: room for other batches' kernels
+    hipLaunchKernelGGL((k_adc_scan4<M, U, NW, WPE, LCAP>), dim3(persistent_grid(a, g.G, per_cu)), dim3(NW * 64), lds, a.st, a.items, a.tabs, a.slots, a.n_slots, a.T32, a.T,
+                       a.codes, a.K, a.L, g.S, a.qctr + 9, a.fhdr, a.fslots, a.hits, a.hitn, a.slack, a.qbound, z, frac, sample_rows, dyn, g.sat);
 }
 
-void launch_scan3(int M, const Scan3Geom& g, int64_t n_items, hipStream_t st, const WorkItem* items, const TabDesc* tabs,
-                  const int* slots, const int* n_slots, const double* T, const float* T32, const uint8_t* codes, int K, int L,
-                  int* qctr, uint64_t* hits, int* hitn, float* slack, unsigned long long* qbound, int* fhdr, int* fslots) {
-#define CIS_S3_NW(MM, RR) launch_scan3_t<MM, RR, 4>(g, n_items, st, items, tabs, slots, n_slots, T, T32, codes, K, L, qctr, hits, hitn, slack, qbound, fhdr, fslots)
-#define CIS_S3(MM)                   \
-    do {                             \
-        if (L <= 184) CIS_S3_NW(MM, 4); \
-        else CIS_S3_NW(MM, 8);       \
-    } while (0)
-    if (M == 4) CIS_S3(4);
-    else if (M == 8) CIS_S3(8);
-    else CIS_S3(16);
-#undef CIS_S3
-#undef CIS_S3_NW
+template <int M, int NR>
+static void launch_scan3_t(const Scan3Geom& g, const ScanArgs& a) {
+    if (g.two_pass != 2) {
+        launch_scan3_k<M, NR>(g, a, false);
+        return;
+    }
+    // k_adc_scan4, then the slots it could not settle (normally none) through k_adc_scan3.  Its switches are
+    // read per call (A/B runs and the fall-back tests set them between calls)
+    const float z_short = getenv("CIS_S4_ZS") ? (float)atof(getenv("CIS_S4_ZS")) : CIS_S4_Z;
+    // long chunks, measured on C4 (profiles/r03m_scan_long.txt): z 4 / 4.5 / 5 -> 0.326 / 0.332 / 0.335 ms, no verification
+    // failure in 100 k lists at z = 4; static schedule 0.301 against 0.326 ms with slots from a counter; one row in 8 / 10 /
+    // 16 as the sample -> 0.321 / 0.326 / 0.45 ms; at most 128 sample rows (64: the 65536-candidate chunks overflow their lists)
+    const float z_long = getenv("CIS_S4_ZL") ? (float)atof(getenv("CIS_S4_ZL")) : 4.5f;
+    const int frac_long = getenv("CIS_S4_FRAC") ? atoi(getenv("CIS_S4_FRAC")) : 8;
+    const int nsx_long = getenv("CIS_S4_NSX") ? atoi(getenv("CIS_S4_NSX")) : 128;
+    const int dyn_long = getenv("CIS_S4_DYN") ? atoi(getenv("CIS_S4_DYN")) : 0;
+    // waves per slot (NW4) and waves per SIMD the variant is compiled for (WPS): 4 x 64 threads at 4 (long chunks) / 6 (short) waves
+    // per SIMD were rounds 2-3; 8 waves per slot halve a slot's main pass, and three such workgroups per CU are 24 waves
+    const int nw4_long = getenv("CIS_S4_NWL") ? atoi(getenv("CIS_S4_NWL")) : CIS_S4_NW_LONG;
+    const int nw4_short = getenv("CIS_S4_NWS") ? atoi(getenv("CIS_S4_NWS")) : CIS_S4_NW_SHORT;
+    if (!g.long_chunks) {
+        constexpr int WPE4 = (M == 16) ? 4 : CIS_S4_WPE;  // (M = 16: 41 KB of LDS hold three workgroups per CU anyway)
+        if (nw4_short == 8 && M != 16) launch_scan4<M, CIS_S4_U, 8, WPE4, S4_LCAP>(g, a, z_short, 1 << 20, S4_NS, 0);
+        else launch_scan4<M, CIS_S4_U, 4, WPE4, S4_LCAP>(g, a, z_short, 1 << 20, S4_NS, 0);
+    } else {
+        constexpr int WPE4 = (M == 16) ? 3 : ((CIS_S4_DEFER != 0 && CIS_S4_GLISTS != 0) ? CIS_S4_WPE_LONG : 4);  // (M = 16: 49 KB of LDS = three workgroups per CU, 168 registers)
+        if (nw4_long == 8 && M != 16) launch_scan4<M, CIS_S4_UL, 8, CIS_S4_WPE8, S4_LCAP_LONG>(g, a, z_long, frac_long, nsx_long, dyn_long);
+        else launch_scan4<M, CIS_S4_UL, 4, WPE4, S4_LCAP_LONG>(g, a, z_long, frac_long, nsx_long, dyn_long);
+    }
+    if (getenv("CIS_SCAN4_DEBUG")) {  // diagnosis: how many slots the sample misjudged (blocks)
+        int h[6] = {0, 0, 0, 0, 0, 0};
+        if (hipMemcpyAsync(h, a.qctr + 9, sizeof(h), hipMemcpyDeviceToHost, a.st) == hipSuccess && hipStreamSynchronize(a.st) == hipSuccess)
+            fprintf(stderr, "[cis] k_adc_scan4: %d slots, %d to the fall-back list (lists: %d overflowed, %d failed the verification, %d crowds at the cut; %d slots with items of different chunks)\n",
+                    h[0], h[1], h[2], h[3], h[4], h[5]);
+    }
+    launch_scan3_k<M, NR>(g, a, true);
+}
+
+void launch_scan3(int M, const Scan3Geom& g, const ScanArgs& a) {  // (scan3_supported: M = 4, 8 or 16, limit <= 440)
+    dispatch_int<4, 8, 16>(M, [&](auto m) { dispatch_nr<8>(a.L, [&](auto nr) { launch_scan3_t<decltype(m)::value, decltype(nr)::value>(g, a); }); });
 }

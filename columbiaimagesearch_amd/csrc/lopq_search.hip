@@ -1870,34 +1870,20 @@ extern "C" int cis_index_last_stats(cis_index* ix, int64_t stats[4]) {
 // ================================================================================================
 // host: search pipeline
 // ================================================================================================
-template <int M, int CAP, int U>
-static void launch_scan(int64_t n_items, size_t lds, hipStream_t st, const WorkItem* items, const double* T,
-                        const uint8_t* codes, const int64_t* ids, int Mrt, int K, int limit, int S, const int* flag,
-                        cis_hit* hits, int* hitn) {
-    hipLaunchKernelGGL((k_adc_scan<M, CAP, U>), dim3((unsigned)n_items), dim3(256), lds, st, items, T, codes, ids, Mrt,
-                       K, limit, S, flag, hits, hitn);
-}
-
 // exact float64 kernel (v1); flag != nullptr restricts it to the items the fast kernel flagged
 template <int CAP, int U>
-static void launch_scan_m(int M, int64_t n_items, hipStream_t st, const WorkItem* items, const double* T,
-                          const uint8_t* codes, const int64_t* ids, int K, int limit, int S, const int* flag,
-                          cis_hit* hits, int* hitn) {
-    const size_t lds = (size_t)CAP * 16 + (size_t)M * K * sizeof(double) + 16;
-    switch (M) {
-        case 4: launch_scan<4, CAP, U>(n_items, lds, st, items, T, codes, ids, M, K, limit, S, flag, hits, hitn); break;
-        case 8: launch_scan<8, CAP, U>(n_items, lds, st, items, T, codes, ids, M, K, limit, S, flag, hits, hitn); break;
-        case 16: launch_scan<16, CAP, U>(n_items, lds, st, items, T, codes, ids, M, K, limit, S, flag, hits, hitn); break;
-        default: launch_scan<0, CAP, U>(n_items, lds, st, items, T, codes, ids, M, K, limit, S, flag, hits, hitn); break;
-    }
+static void launch_scan_m(int M, const ScanArgs& a, int S, const int* flag) {
+    const size_t lds = (size_t)CAP * 16 + (size_t)M * a.K * sizeof(double) + 16;
+    dispatch_int<0, 4, 8, 16>((M == 4 || M == 8 || M == 16) ? M : 0, [&](auto m) {  // 0: any M
+        hipLaunchKernelGGL((k_adc_scan<decltype(m)::value, CAP, U>), dim3((unsigned)a.n_items), dim3(256), lds, a.st, a.items, a.T, a.codes, a.ids, M, a.K, a.L, S, flag,
+                           reinterpret_cast<cis_hit*>(a.hits), a.hitn);
+    });
 }
 
-static void launch_scan_exact(int M, int64_t n_items, hipStream_t st, const WorkItem* items, const double* T,
-                              const uint8_t* codes, const int64_t* ids, int K, int L, int S, const int* flag,
-                              cis_hit* hits, int* hitn) {
-    if (L <= 512) launch_scan_m<1024, 2>(M, n_items, st, items, T, codes, ids, K, L, S, flag, hits, hitn);
-    else if (L <= 1024) launch_scan_m<2048, 4>(M, n_items, st, items, T, codes, ids, K, L, S, flag, hits, hitn);
-    else launch_scan_m<4096, 4>(M, n_items, st, items, T, codes, ids, K, L, S, flag, hits, hitn);
+static void launch_scan_exact(int M, const ScanArgs& a, int S, const int* flag) {
+    if (a.L <= 512) launch_scan_m<1024, 2>(M, a, S, flag);
+    else if (a.L <= 1024) launch_scan_m<2048, 4>(M, a, S, flag);
+    else launch_scan_m<4096, 4>(M, a, S, flag);
 }
 
 // float32-prefilter kernel (v2): M in {4, 8, 16}, K <= 256, L <= 952 (a wave region of NR * 64 - 8 entries holds L + 64; 16 registers
@@ -1927,28 +1913,17 @@ static Scan2Geom scan2_geom(int M, int K, int L, int nq) {
 }
 
 template <int M, int NR, int G, int NW, int U>
-static void launch_scan2_t(int64_t n_items, hipStream_t st, const WorkItem* items, const int* slots, const int* n_slots,
-                           const double* T, const float* T32, const uint8_t* codes, const int64_t* ids, int K, int L, int S, size_t lds,
-                           int* qctr, uint64_t* hits, int* hitn, unsigned long long* qbound) {
+static void launch_scan2_t(const Scan2Geom& g, const ScanArgs& a) {
     const float eps = 2.0f * (float)M * 5.9604645e-8f;  // 2 * M * 2^-24
     const float margin = 1.0f + 3.0f * eps;
-    const int per_cu = (int)(163840 / lds) < (32 / NW) ? (int)(163840 / lds) : (32 / NW);
-    const int64_t resident = 256 * (per_cu < 1 ? 1 : per_cu);  // persistent grid: what the chip can hold
-    const int64_t want = (n_items + G - 1) / G + 8;
-    const unsigned grid = (unsigned)(want < resident ? ((want + 7) / 8) * 8 : resident);
-    hipLaunchKernelGGL((k_adc_scan2<M, NR, U, G, NW>), dim3(grid), dim3(NW * 64), lds, st, items, slots, n_slots, T, T32, codes, ids,
-                       K, L, S, margin, qctr, hits, hitn, qbound);
+    const int per_cu = (int)(163840 / g.lds) < (32 / NW) ? (int)(163840 / g.lds) : (32 / NW);
+    hipLaunchKernelGGL((k_adc_scan2<M, NR, U, G, NW>), dim3(persistent_grid(a, G, per_cu)), dim3(NW * 64), g.lds, a.st, a.items, a.slots, a.n_slots, a.T, a.T32, a.codes, a.ids,
+                       a.K, a.L, g.S, margin, a.qctr, a.hits, a.hitn, a.qbound);
 }
 
 template <int M, int NR>
-static void launch_scan2_mr(const Scan2Geom& g, int64_t n_items, hipStream_t st, const WorkItem* items, const int* slots,
-                            const int* n_slots, const double* T, const float* T32, const uint8_t* codes, const int64_t* ids, int K, int L,
-                            int* qctr, uint64_t* hits, int* hitn, unsigned long long* qbound) {
-#define CIS_SCAN2_CASE(GG, WW, UU)                                                                                    \
-    if (g.G == GG && g.NW == WW && g.U == UU) {                                                                       \
-        launch_scan2_t<M, NR, GG, WW, UU>(n_items, st, items, slots, n_slots, T, T32, codes, ids, K, L, g.S, g.lds, qctr, hits, hitn, qbound); \
-        return;                                                                                                       \
-    }
+static void launch_scan2_mr(const Scan2Geom& g, const ScanArgs& a) {
+#define CIS_SCAN2_CASE(GG, WW, UU) if (g.G == GG && g.NW == WW && g.U == UU) return launch_scan2_t<M, NR, GG, WW, UU>(g, a);
     CIS_SCAN2_CASE(1, 4, 2)
     if constexpr (NR != 16) {  // limit 441 ... 952 (NR = 16): one query per workgroup only
         CIS_SCAN2_CASE(1, 4, 4)
@@ -1962,21 +1937,8 @@ static void launch_scan2_mr(const Scan2Geom& g, int64_t n_items, hipStream_t st,
 #undef CIS_SCAN2_CASE
 }
 
-template <int M>
-static void launch_scan2_m(const Scan2Geom& g, int64_t n_items, hipStream_t st, const WorkItem* items, const int* slots,
-                           const int* n_slots, const double* T, const float* T32, const uint8_t* codes, const int64_t* ids, int K, int L,
-                           int* qctr, uint64_t* hits, int* hitn, unsigned long long* qbound) {
-    if (L <= 184) launch_scan2_mr<M, 4>(g, n_items, st, items, slots, n_slots, T, T32, codes, ids, K, L, qctr, hits, hitn, qbound);
-    else if (L <= 440) launch_scan2_mr<M, 8>(g, n_items, st, items, slots, n_slots, T, T32, codes, ids, K, L, qctr, hits, hitn, qbound);
-    else launch_scan2_mr<M, 16>(g, n_items, st, items, slots, n_slots, T, T32, codes, ids, K, L, qctr, hits, hitn, qbound);
-}
-
-static void launch_scan2(int M, const Scan2Geom& g, int64_t n_items, hipStream_t st, const WorkItem* items, const int* slots,
-                         const int* n_slots, const double* T, const float* T32, const uint8_t* codes, const int64_t* ids, int K, int L,
-                         int* qctr, uint64_t* hits, int* hitn, unsigned long long* qbound) {
-    if (M == 4) launch_scan2_m<4>(g, n_items, st, items, slots, n_slots, T, T32, codes, ids, K, L, qctr, hits, hitn, qbound);
-    else if (M == 8) launch_scan2_m<8>(g, n_items, st, items, slots, n_slots, T, T32, codes, ids, K, L, qctr, hits, hitn, qbound);
-    else launch_scan2_m<16>(g, n_items, st, items, slots, n_slots, T, T32, codes, ids, K, L, qctr, hits, hitn, qbound);
+static void launch_scan2(int M, const Scan2Geom& g, const ScanArgs& a) {  // (scan2_supported: M = 4, 8 or 16)
+    dispatch_int<4, 8, 16>(M, [&](auto m) { dispatch_nr<16>(a.L, [&](auto nr) { launch_scan2_mr<decltype(m)::value, decltype(nr)::value>(g, a); }); });
 }
 
 // ---- large `limit` (above what the LDS top-k kernels hold): exact distance of EVERY candidate, stable segmented
@@ -2326,25 +2288,17 @@ static int direct_jp(int M, int K, int w) {
 }
 
 template <int MT, int W, int JP>
-static void launch_adc_direct_t(hipStream_t st, const WorkItem* items, const int64_t* cand_start, const int64_t* seg,
-                                const int64_t* item_off, const double* px, const double* subs, const uint8_t* codes, int K, int h,
-                                int nq, uint64_t* keys, uint64_t* vals, unsigned long long* qmin, unsigned long long* qmax) {
-    const size_t lds = (size_t)JP * K * W * sizeof(double) + (size_t)FLAT_ITEMS * sizeof(int);
-    const unsigned grid = (unsigned)(nq < 256 ? nq : 256);
+static void launch_adc_direct_t(const CandArgs& c, const double* px, const double* subs, int h, uint64_t* keys, uint64_t* vals) {
+    const size_t lds = (size_t)JP * c.K * W * sizeof(double) + (size_t)FLAT_ITEMS * sizeof(int);
+    const unsigned grid = (unsigned)(c.nq < 256 ? c.nq : 256);
     for (int ph = 0; ph < MT / JP; ++ph)
-        hipLaunchKernelGGL((k_adc_direct<MT, W, JP>), dim3(grid), dim3(1024), lds, st, items, cand_start, seg, item_off, px, subs, codes, K, h,
-                           ph, nq, keys, vals, qmin, qmax);
+        hipLaunchKernelGGL((k_adc_direct<MT, W, JP>), dim3(grid), dim3(1024), lds, c.st, c.items, c.cand_start, c.seg, c.item_off, px, subs, c.codes, c.K, h,
+                           ph, c.nq, keys, vals, c.qmin, c.qmax);
 }
 
-static bool launch_adc_direct(int M, int K, int w, hipStream_t st, const WorkItem* items, const int64_t* cand_start, const int64_t* seg,
-                              const int64_t* item_off, const double* px, const double* subs, const uint8_t* codes, int h, int nq,
-                              uint64_t* keys, uint64_t* vals, unsigned long long* qmin, unsigned long long* qmax) {
-    const int jp = direct_jp(M, K, w);
-#define CIS_DIRECT(MT, W, JP)                                                                                                     \
-    if (M == MT && w == W && jp == JP) {                                                                                          \
-        launch_adc_direct_t<MT, W, JP>(st, items, cand_start, seg, item_off, px, subs, codes, K, h, nq, keys, vals, qmin, qmax);  \
-        return true;                                                                                                              \
-    }
+static bool launch_adc_direct(int M, int w, const CandArgs& c, const double* px, const double* subs, int h, uint64_t* keys, uint64_t* vals) {
+    const int jp = direct_jp(M, c.K, w);
+#define CIS_DIRECT(MT, W, JP) if (M == MT && w == W && jp == JP) return launch_adc_direct_t<MT, W, JP>(c, px, subs, h, keys, vals), true;
     // K = 256: 128 KB hold 64 / w sub-quantizers
     CIS_DIRECT(8, 16, 4) CIS_DIRECT(16, 16, 4) CIS_DIRECT(4, 16, 4) CIS_DIRECT(8, 8, 8) CIS_DIRECT(16, 8, 8) CIS_DIRECT(4, 8, 4)
     CIS_DIRECT(4, 32, 2) CIS_DIRECT(8, 32, 2) CIS_DIRECT(16, 32, 2) CIS_DIRECT(4, 4, 4) CIS_DIRECT(8, 4, 8) CIS_DIRECT(16, 4, 16)
@@ -2352,24 +2306,24 @@ static bool launch_adc_direct(int M, int K, int w, hipStream_t st, const WorkIte
     return false;
 }
 
-static void launch_adc_all(int64_t n_items, hipStream_t st, const WorkItem* items, const int64_t* cand_start, const double* T,
-                           const uint8_t* codes, int M, int K, uint64_t* keys, uint64_t* vals, unsigned long long* qmin,
-                           unsigned long long* qmax, const int64_t* d_totals = nullptr, const int64_t* seg = nullptr,
-                           const int64_t* item_off = nullptr, int nq = 0, bool flat = false) {
-    if (flat && seg && item_off && nq > 0 && !d_totals) {
-        const dim3 gf((unsigned)nq, 8);
-        if (K <= 256 && M == 4) hipLaunchKernelGGL(k_adc_all_flat<4>, gf, dim3(256), 0, st, items, cand_start, seg, item_off, T, codes, M, K, keys, vals, qmin, qmax);
-        else if (K <= 256 && M == 8) hipLaunchKernelGGL(k_adc_all_flat<8>, gf, dim3(256), 0, st, items, cand_start, seg, item_off, T, codes, M, K, keys, vals, qmin, qmax);
-        else if (K <= 256 && M == 16) hipLaunchKernelGGL(k_adc_all_flat<16>, gf, dim3(256), 0, st, items, cand_start, seg, item_off, T, codes, M, K, keys, vals, qmin, qmax);
-        else hipLaunchKernelGGL(k_adc_all_flat<0>, gf, dim3(256), 0, st, items, cand_start, seg, item_off, T, codes, M, K, keys, vals, qmin, qmax);
+// every candidate's exact key from the float64 tables: a workgroup row per query that finds its items itself (flat: tiny cells, exact totals),
+// else eight workgroups per work item
+static void launch_adc_all(const CandArgs& c, const double* T, int M, uint64_t* keys, uint64_t* vals, const int64_t* d_totals, bool flat) {
+    const bool m_lds = c.K <= 256 && (M == 4 || M == 8 || M == 16);  // the table of one work item in LDS, code bytes unpacked at compile time
+    if (flat && c.nq > 0 && !d_totals) {
+        dispatch_int<0, 4, 8, 16>(m_lds ? M : 0, [&](auto m) {
+            hipLaunchKernelGGL(k_adc_all_flat<decltype(m)::value>, dim3((unsigned)c.nq, 8), dim3(256), 0, c.st, c.items, c.cand_start, c.seg, c.item_off, T, c.codes, M, c.K,
+                               keys, vals, c.qmin, c.qmax);
+        });
         return;
     }
-    const dim3 g((unsigned)n_items, 8);
-    const size_t lds = (size_t)M * K * sizeof(double);
-    if (K <= 256 && M == 4) hipLaunchKernelGGL(k_adc_all_lds<4>, g, dim3(256), lds, st, items, cand_start, T, codes, K, keys, vals, qmin, qmax, d_totals);
-    else if (K <= 256 && M == 8) hipLaunchKernelGGL(k_adc_all_lds<8>, g, dim3(256), lds, st, items, cand_start, T, codes, K, keys, vals, qmin, qmax, d_totals);
-    else if (K <= 256 && M == 16) hipLaunchKernelGGL(k_adc_all_lds<16>, g, dim3(256), lds, st, items, cand_start, T, codes, K, keys, vals, qmin, qmax, d_totals);
-    else hipLaunchKernelGGL(k_adc_all, g, dim3(256), 0, st, items, cand_start, T, codes, M, K, keys, vals, qmin, qmax, d_totals);
+    const dim3 g((unsigned)c.n_items, 8);
+    if (m_lds)
+        dispatch_int<4, 8, 16>(M, [&](auto m) {
+            hipLaunchKernelGGL(k_adc_all_lds<decltype(m)::value>, g, dim3(256), (size_t)M * c.K * sizeof(double), c.st, c.items, c.cand_start, T, c.codes, c.K, keys, vals,
+                               c.qmin, c.qmax, d_totals);
+        });
+    else hipLaunchKernelGGL(k_adc_all, g, dim3(256), 0, c.st, c.items, c.cand_start, T, c.codes, M, c.K, keys, vals, c.qmin, c.qmax, d_totals);
 }
 
 __global__ void k_emit_sorted(const uint64_t* __restrict__ keys, const uint64_t* __restrict__ vals, const int64_t* __restrict__ seg,
@@ -3253,30 +3207,58 @@ static int tiny_pool(int M, int K, int w, int h, int L, int64_t ncmax_need, int*
     return pool;
 }
 
+// a selection's operands: the keys it reads, where it leaves the ranked pairs of a query (sp.stride slots, nsel[q] of them filled)
+struct SelectArgs {
+    const uint64_t* keys;  // every candidate's exact key (k_tiny_select: written for the queries it flags)
+    int L;
+    SelectPlan sp;
+    uint64_t *sel_keys, *sel_vals;
+    int* nsel;
+    int64_t *seg_b, *seg_e;  // null, or the segments of the selected pairs for the segmented sort
+    const int* only;         // null, or ranked: flagged queries only
+    // the streaming route's indirect keys (see k_select_topl): null / 0 elsewhere
+    const uint32_t* rid;
+    const int* kcnt;
+    int64_t kstride;
+};
+
+struct TinyArgs {  // what k_tiny_select reads besides the candidate layout and the selection's outputs
+    const int64_t* tab_off;
+    const PlanOut* plan;
+    const double *px, *subs;
+    int h, ncmax, tch;
+    uint64_t* keys_fb;  // = SelectArgs::keys, written
+    int* fbflag;
+    float* px32_ws;
+    unsigned int* dbg;
+};
+
 template <int MT, int W>
-static void launch_tiny_t(hipStream_t st, const WorkItem* items, const int64_t* cand_start, const int64_t* seg, const int64_t* item_off,
-                          const int64_t* tab_off, const PlanOut* plan, const double* px, const double* subs, const uint8_t* codes, int h, int nq,
-                          int L, int ncmax, int tch, int64_t stride, uint64_t* sel_keys, uint64_t* sel_vals, int* nsel, uint64_t* keys_fb,
-                          unsigned long long* qmin, unsigned long long* qmax, int* fbflag, float* px32_ws, unsigned int* dbg) {
-    const size_t lds = tiny_lds_bytes(ncmax, tch);
-    const unsigned grid = (unsigned)(nq < 256 ? nq : 256);
-    hipLaunchKernelGGL((k_tiny_select<MT, W>), dim3(grid), dim3(1024), lds, st, items, cand_start, seg, item_off, tab_off, plan, px, subs, codes,
-                       h, nq, L, ncmax, tch, stride, sel_keys, sel_vals, nsel, keys_fb, qmin, qmax, fbflag, px32_ws, dbg);
+static void launch_tiny_t(const CandArgs& c, const SelectArgs& s, const TinyArgs& t) {
+    const size_t lds = tiny_lds_bytes(t.ncmax, t.tch);
+    const unsigned grid = (unsigned)(c.nq < 256 ? c.nq : 256);
+    hipLaunchKernelGGL((k_tiny_select<MT, W>), dim3(grid), dim3(1024), lds, c.st, c.items, c.cand_start, c.seg, c.item_off, t.tab_off, t.plan, t.px, t.subs, c.codes,
+                       t.h, c.nq, s.L, t.ncmax, t.tch, s.sp.stride, s.sel_keys, s.sel_vals, s.nsel, t.keys_fb, c.qmin, c.qmax, t.fbflag, t.px32_ws, t.dbg);
 }
 
-static bool launch_tiny(int M, int w, hipStream_t st, const WorkItem* items, const int64_t* cand_start, const int64_t* seg,
-                        const int64_t* item_off, const int64_t* tab_off, const PlanOut* plan, const double* px, const double* subs,
-                        const uint8_t* codes, int h, int nq, int L, int ncmax, int tch, int64_t stride, uint64_t* sel_keys, uint64_t* sel_vals,
-                        int* nsel, uint64_t* keys_fb, unsigned long long* qmin, unsigned long long* qmax, int* fbflag, float* px32_ws, unsigned int* dbg) {
-#define CIS_TINY(MT, W)                                                                                                            \
-    if (M == MT && w == W) {                                                                                                       \
-        launch_tiny_t<MT, W>(st, items, cand_start, seg, item_off, tab_off, plan, px, subs, codes, h, nq, L, ncmax, tch, stride,   \
-                             sel_keys, sel_vals, nsel, keys_fb, qmin, qmax, fbflag, px32_ws, dbg);                                 \
-        return true;                                                                                                               \
-    }
+static bool launch_tiny(int M, int w, const CandArgs& c, const SelectArgs& s, const TinyArgs& t) {
+#define CIS_TINY(MT, W) if (M == MT && w == W) return launch_tiny_t<MT, W>(c, s, t), true;
     CIS_TINY(8, 16) CIS_TINY(16, 8) CIS_TINY(4, 32) CIS_TINY(16, 16) CIS_TINY(8, 32) CIS_TINY(8, 8) CIS_TINY(4, 16) CIS_TINY(16, 4)
 #undef CIS_TINY
     return false;
+}
+
+template <bool SORT_LDS, int NT>
+static void launch_select_nt(const CandArgs& c, const SelectArgs& s) {
+    hipLaunchKernelGGL((k_select_topl<SORT_LDS, NT>), dim3((unsigned)c.nq), dim3(NT), s.sp.lds, c.st, s.keys, c.seg, c.cand_start, c.item_off, c.qmin, c.qmax, c.n_items, s.L,
+                       s.sp.p2, s.sp.stride, s.sel_keys, s.sel_vals, s.nsel, s.seg_b, s.seg_e, s.only, s.rid, s.kcnt, s.kstride);
+}
+
+// fewer queries than CUs: one large workgroup per query walks its keys faster; else two 512-thread ones per CU
+template <bool SORT_LDS>
+static void launch_select(const CandArgs& c, const SelectArgs& s) {
+    if (c.nq <= 256) launch_select_nt<SORT_LDS, 1024>(c, s);
+    else launch_select_nt<SORT_LDS, 512>(c, s);
 }
 
 // one sub-batch of queries (device pointers); writes ranked partial hits [nq][L] and visited [nq]
@@ -3536,8 +3518,16 @@ static int run_stream(Batch& b, const Route& r) {
     int* nsel = cnt + (nq + 2);
     float* tau = reinterpret_cast<float*>(nsel + (nq + 2));
     int* status = reinterpret_cast<int*>(tau + (nq + 2));
+    const CandArgs c{st, b.items, n_items, b.item_off, cand_start, seg, qmin, qmax, nq, codes, K};
+    StreamArgs s{};
+    s.M = M; s.G = G; s.L = L;
+    s.slots = sl.slots; s.n_slots = sl.n_slots; s.rowoff = rowoff; s.desc = sdesc;
+    s.T = b.T; s.T32 = b.T32; s.tau = tau; s.bmin = bmin; s.B = B;
+    s.surv = surv; s.cnt = cnt; s.cap = cap; s.keys = skeys;
+    s.sel_keys = sel_keys; s.sel_vals = sel_vals; s.nsel = nsel; s.stride = sp.stride;
+    s.ids = ids; s.plan = b.plan; s.status = status;
     // candidate layout + slot records + row offsets + resets: one launch of one workgroup
-    launch_stream_prep(st, b.items, n_items, b.item_off, nq, n_cand_all, sl.slots, sl.n_slots, G, M, cand_start, seg, qmin, qmax, cnt, status, rowoff, sdesc, b.d_tot);
+    launch_stream_prep(c, s, n_cand_all, b.d_tot);
     // sample: every SS-th row; the k-th smallest of the bucket minima lets about k * SS candidates of a query through -- aim at
     // ~max(4096, 16 limit) of them, with k >= 8 so that the count is stable (relative spread 1 / sqrt(k))
     const int64_t per_q = n_cand_all / nq;
@@ -3552,20 +3542,19 @@ static int run_stream(Batch& b, const Route& r) {
     // a lane folds `flush` of its sampled rows into one bucket: ~4 B bucket writes per query (a query's sampled rows x 64 lanes / flush)
     int64_t flush = ceil_div(ceil_div(per_q, (int64_t)row * ss) * 64, (int64_t)4 * B);
     flush = flush < 1 ? 1 : flush;
-    const int grid = stream_grid(M, G, K, ceil_div(n_cand_all, (int64_t)row) + n_items);
-    launch_stream_scan(M, G, true, grid, st, sdesc, sl.n_slots, rowoff, b.T32, b.T, codes, K, tau, bmin, B, (int)ss, (int)flush, surv, cnt, cap);
-    launch_stream_tau(st, bmin, B, (int)kth, nq, tau);
+    s.grid = stream_grid(M, G, K, ceil_div(n_cand_all, (int64_t)row) + n_items);
+    s.sample_stride = (int)ss; s.flush = (int)flush;
+    launch_stream_scan(c, s, true);
+    launch_stream_tau(c, s, (int)kth);
     CIS_TRY(mark(b, 5));
     b.pr.has_scan = true;
     ix->last_scan_kernel = 5;
-    launch_stream_scan(M, G, false, grid, st, sdesc, sl.n_slots, rowoff, b.T32, b.T, codes, K, tau, bmin, B, (int)ss, (int)flush, surv, cnt, cap);
+    launch_stream_scan(c, s, false);
     CIS_TRY(mark(b, 3));
-    launch_stream_keys(M, st, b.items, cand_start, seg, b.item_off, n_items, b.T, codes, K, surv, cnt, cap, nq, skeys, qmin, qmax);
-    hipLaunchKernelGGL((k_select_topl<true, 1024>), dim3((unsigned)nq), dim3(1024), sp.lds, st, skeys, seg, cand_start, b.item_off, qmin, qmax, n_items, L, sp.p2,
-                       sp.stride, sel_keys, sel_vals, nsel, (int64_t*)nullptr, (int64_t*)nullptr, (const int*)nullptr, surv, cnt, (int64_t)cap);
+    launch_stream_keys(c, s);
+    launch_select_nt<true, 1024>(c, SelectArgs{skeys, L, sp, sel_keys, sel_vals, nsel, nullptr, nullptr, nullptr, surv, cnt, (int64_t)cap});
     const int64_t sseq = ++ix->stream_batches;
-    launch_stream_finish(st, sel_keys, sel_vals, nsel, sp.stride, cnt, cap, seg, tau, nq, L, M, b.items, ids, b.plan, out.hits, out.ids, out.dists, out.n_found,
-                         out.cells, out.pos, out.visited, status, ix->d_h_totals + 6, sseq);
+    launch_stream_finish(c, s, out, ix->d_h_totals + 6, sseq);
     CIS_CHECK_HIP(hipGetLastError());
     CIS_TRY(mark(b, 4));
     ix->stats[3] += 1;
@@ -3655,6 +3644,8 @@ static int run_all_candidates(Batch& b, const Route& r) {
     uint64_t* b3 = b2 + bl;
     uint64_t* b4 = b3 + bl;
     void* tmp = reinterpret_cast<void*>(((uintptr_t)(sp.select ? (sp.sort_lds ? b3 : b3 + 2 * bl) : b4) + 255) & ~(uintptr_t)255);
+    // (the full sort selects nothing by the key range: the exact kernels do not write it there)
+    const CandArgs c{st, items, n_items, item_off, cand_start, seg, sp.select ? qmin : nullptr, sp.select ? qmax : nullptr, nq, codes, K};
     if (n_items > 16384 && !d_tot) {
         const int64_t ntiles = ceil_div(n_items, CAND_TILE);
         CIS_TRY(ix->w_tiles.reserve((size_t)(ntiles + 1) * sizeof(int64_t)));
@@ -3671,14 +3662,14 @@ static int run_all_candidates(Batch& b, const Route& r) {
     if (!sp.select) {
         uint64_t *keys_out = b1, *vals_in = b2, *vals_out = b3;
         if (n_items > 0) {
-            if (!(direct && launch_adc_direct(M, K, m->w, st, items, cand_start, seg, item_off, px_buf, m->d_subs, codes, h, nq, keys_in, vals_in, nullptr, nullptr)))
-                launch_adc_all(n_items, st, items, cand_start, T, codes, M, K, keys_in, vals_in, nullptr, nullptr, nullptr, seg, item_off, nq, tiny_cells);
+            if (!(direct && launch_adc_direct(M, m->w, c, px_buf, m->d_subs, h, keys_in, vals_in)))
+                launch_adc_all(c, T, M, keys_in, vals_in, nullptr, tiny_cells);
             size_t bb = tmp_bytes;
             CIS_TRY(cis_seg_sort_u64(tmp, &bb, keys_in, keys_out, vals_in, vals_out, n_cand, nq, seg, seg + 1, st));
         }
         rk = keys_out; rv = vals_out;
     } else {
-        uint64_t *sel_keys = b1, *sel_vals = b2;
+        SelectArgs s{keys_in, L, sp, b1, b2, nsel};
         // tiny cells, limit a small share of the quota: byte-table prefilter + exact keys of the survivors in ONE kernel per
         // query (k_tiny_select); the queries it flags go through the exact kernels below
         int* fbflag = nullptr;
@@ -3697,8 +3688,7 @@ static int run_all_candidates(Batch& b, const Route& r) {
                     dbg = ix->w_slack.as<unsigned int>();
                     CIS_CHECK_HIP(hipMemsetAsync(dbg, 0, 96, st));
                 }
-                if (!launch_tiny(M, m->w, st, items, cand_start, seg, item_off, tab_off, b.plan, px_buf, m->d_subs, codes, h, nq, L, ncmax, tch,
-                                 sp.stride, sel_keys, sel_vals, nsel, keys_in, qmin, qmax, fbflag, b.T32, dbg))
+                if (!launch_tiny(M, m->w, c, s, TinyArgs{tab_off, b.plan, px_buf, m->d_subs, h, ncmax, tch, keys_in, fbflag, b.T32, dbg}))
                     fbflag = nullptr;
                 else if (tiny_dbg)
                     CIS_TRY(dump_tiny_debug(b, dbg, tch, ncmax));
@@ -3706,29 +3696,18 @@ static int run_all_candidates(Batch& b, const Route& r) {
         }
         if (fbflag) {
         } else
-        if (n_items > 0 && !(direct && launch_adc_direct(M, K, m->w, st, items, cand_start, seg, item_off, px_buf, m->d_subs, codes, h, nq, keys_in, nullptr, qmin, qmax)))
-            launch_adc_all(n_items, st, items, cand_start, T, codes, M, K, keys_in, nullptr, qmin, qmax, d_tot, seg, item_off, nq, tiny_cells);
+        if (n_items > 0 && !(direct && launch_adc_direct(M, m->w, c, px_buf, m->d_subs, h, keys_in, nullptr)))
+            launch_adc_all(c, T, M, keys_in, nullptr, d_tot, tiny_cells);
         if (sp.sort_lds) {
-            // fewer queries than CUs: one large workgroup per query walks its keys faster; else two 512-thread ones per CU
-            if (nq <= 256)
-                hipLaunchKernelGGL((k_select_topl<true, 1024>), dim3((unsigned)nq), dim3(1024), sp.lds, st, keys_in, seg, cand_start, item_off,
-                                   qmin, qmax, n_items, L, sp.p2, sp.stride, sel_keys, sel_vals, nsel, (int64_t*)nullptr, (int64_t*)nullptr,
-                                   (const int*)fbflag);
-            else
-                hipLaunchKernelGGL((k_select_topl<true, 512>), dim3((unsigned)nq), dim3(512), sp.lds, st, keys_in, seg, cand_start, item_off,
-                                   qmin, qmax, n_items, L, sp.p2, sp.stride, sel_keys, sel_vals, nsel, (int64_t*)nullptr, (int64_t*)nullptr,
-                                   (const int*)fbflag);
-            rk = sel_keys; rv = sel_vals;
+            s.only = fbflag;
+            launch_select<true>(c, s);
+            rk = s.sel_keys; rv = s.sel_vals;
         } else {
             uint64_t *srt_keys = b3, *srt_vals = b3 + bl;
-            if (nq <= 256)
-                hipLaunchKernelGGL((k_select_topl<false, 1024>), dim3((unsigned)nq), dim3(1024), sp.lds, st, keys_in, seg, cand_start, item_off,
-                                   qmin, qmax, n_items, L, sp.p2, sp.stride, sel_keys, sel_vals, nsel, seg_b, seg_e, (const int*)nullptr);
-            else
-                hipLaunchKernelGGL((k_select_topl<false, 512>), dim3((unsigned)nq), dim3(512), sp.lds, st, keys_in, seg, cand_start, item_off,
-                                   qmin, qmax, n_items, L, sp.p2, sp.stride, sel_keys, sel_vals, nsel, seg_b, seg_e, (const int*)nullptr);
+            s.seg_b = seg_b; s.seg_e = seg_e;
+            launch_select<false>(c, s);
             size_t bb = tmp_bytes;
-            CIS_TRY(cis_seg_sort_u64(tmp, &bb, sel_keys, srt_keys, sel_vals, srt_vals, n_sel, nq, seg_b, seg_e, st));
+            CIS_TRY(cis_seg_sort_u64(tmp, &bb, s.sel_keys, srt_keys, s.sel_vals, srt_vals, n_sel, nq, seg_b, seg_e, st));
             rk = srt_keys; rv = srt_vals;
         }
     }
@@ -3744,15 +3723,24 @@ static int run_all_candidates(Batch& b, const Route& r) {
     return CIS_OK;
 }
 
+// what the scans of this batch read and write (sl: the slot list, empty for the exact scan)
+static ScanArgs scan_args(const Batch& b, const Slots& sl) {
+    cis_index* ix = b.ix;
+    ScanArgs a{};
+    a.st = b.st; a.items = b.items; a.n_items = b.n_items; a.nq = b.nq; a.tabs = b.tabs;
+    a.slots = sl.slots; a.n_slots = sl.n_slots; a.plan = b.plan;
+    a.T = b.T; a.T32 = b.T32; a.codes = ix->codes_ptr(); a.ids = ix->ids_ptr();
+    a.K = ix->m->K; a.L = b.L;
+    a.qctr = sl.qctr; a.hits = ix->w_hits.as<uint64_t>(); a.hitn = ix->w_hitn.as<int>(); a.slack = ix->w_slack.as<float>(); a.qbound = b.qbound;
+    a.fhdr = sl.fhdr; a.fslots = sl.fslots;
+    return a;
+}
+
 // 4. ADC scan + block top-k through the slot list
 static int run_fast_scan(Batch& b, const Route& r) {
     cis_index* ix = b.ix;
     hipStream_t st = b.st;
-    const int K = ix->m->K, M = ix->m->M, nq = b.nq, L = b.L;
-    const int64_t n_items = b.n_items;
-    const uint8_t* codes = ix->codes_ptr();
-    const int64_t* ids = ix->ids_ptr();
-    int* hitn = ix->w_hitn.as<int>();
+    const int M = ix->m->M;
     const bool use3 = r.use3;
     const Scan3Geom& geom3 = r.geom3;
     // slot list: work items grouped by coarse cell (counting sort; skipped for huge V), G per slot
@@ -3766,26 +3754,26 @@ static int run_fast_scan(Batch& b, const Route& r) {
     CIS_TRY(build_slots(b, sort_items ? SLOTS_SORTED : SLOTS_IDENTITY, G, CH, r.seg_max, &sl));
     CIS_TRY(mark(b, 5));
     ix->last_scan_kernel = use5 ? 6 : (use3 ? (geom3.two_pass == 2 ? 4 : 3) : 2);  // 4: the sampled single-pass form k_adc_scan4 does the work (k_adc_scan3 only its fall-back slots)
+    const ScanArgs a = scan_args(b, sl);
     if (use5) {
-        CIS_TRY(ix->w_s5.reserve(scan5_workspace_bytes(nq)));
-        launch_scan5(M, geom3, n_items, nq, st, b.items, b.tabs, sl.slots, sl.n_slots, b.plan, b.T, b.T32, codes, K, L, sl.qctr, ix->w_hits.as<uint64_t>(), hitn,
-                     ix->w_slack.as<float>(), b.qbound, sl.fhdr, sl.fslots, ix->w_s5.p, nullptr);
+        CIS_TRY(ix->w_s5.reserve(scan5_workspace_bytes(b.nq)));
+        launch_scan5(M, geom3, a, ix->w_s5.p);
     } else if (use3) {
         Scan3Geom g3 = geom3;
         // M = 16 on the sampled form: the saturating scale of k_adc_scan4 (sums of the near candidates at this fraction of the entry cap)
         const float sat16 = getenv("CIS_S4_SAT") ? (float)atof(getenv("CIS_S4_SAT")) : 0.75f;
         if (M == 16 && g3.two_pass == 2) g3.sat = sat16;
-        launch_scan3(M, g3, n_items, st, b.items, b.tabs, sl.slots, sl.n_slots, b.T, b.T32, codes, K, L, sl.qctr, ix->w_hits.as<uint64_t>(), hitn, ix->w_slack.as<float>(), b.qbound, sl.fhdr, sl.fslots);
+        launch_scan3(M, g3, a);
         if (g3.sat > 0.f && ix->h_totals)  // (slots, fall-back slots) for the back-off in route_hints
             CIS_CHECK_HIP(hipMemcpyAsync(&ix->h_totals[4], sl.qctr + 9, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
     } else
-        launch_scan2(M, r.geom, n_items, st, b.items, sl.slots, sl.n_slots, b.T, b.T32, codes, ids, K, L, sl.qctr, ix->w_hits.as<uint64_t>(), hitn, b.qbound);
+        launch_scan2(M, r.geom, a);
     return CIS_OK;
 }
 
 // survivors of the float32 scan: exact re-scoring + ranking (limit <= 440 here)
-template <int CAP, int MT>
-static void merge_survivors(const Batch& b, const Route& r, bool many) {
+template <int CAP, int MT, int NEMAX>
+static void merge_survivors(const Batch& b, const Route& r) {
     cis_index* ix = b.ix;
     hipStream_t st = b.st;
     const int nq = b.nq, L = b.L, S = r.S, M = ix->m->M, K = ix->m->K;
@@ -3795,29 +3783,32 @@ static void merge_survivors(const Batch& b, const Route& r, bool many) {
     const uint8_t* codes = ix->codes_ptr();
     const int64_t* ids = ix->ids_ptr();
     const float* slack = r.use3 ? ix->w_slack.as<float>() : (const float*)nullptr;
-    if (many)
-        hipLaunchKernelGGL((k_merge_survivors<CAP, MT, 8>), dim3((unsigned)ceil_div(nq, 4)), dim3(256), (size_t)4 * CAP * 16, st,
-                           surv, hitn, b.item_off, b.items, b.T, codes, ids, nq, M, K, L, S, out.hits, out.ids, out.dists,
-                           out.n_found, out.cells, out.pos, b.plan, out.visited, slack);
-    else
-        hipLaunchKernelGGL((k_merge_survivors<CAP, MT, 4>), dim3((unsigned)ceil_div(nq, 4)), dim3(256), (size_t)4 * CAP * 16, st,
-                           surv, hitn, b.item_off, b.items, b.T, codes, ids, nq, M, K, L, S, out.hits, out.ids, out.dists,
-                           out.n_found, out.cells, out.pos, b.plan, out.visited, slack);
+    hipLaunchKernelGGL((k_merge_survivors<CAP, MT, NEMAX>), dim3((unsigned)ceil_div(nq, 4)), dim3(256), (size_t)4 * CAP * 16, st,
+                       surv, hitn, b.item_off, b.items, b.T, codes, ids, nq, M, K, L, S, out.hits, out.ids, out.dists,
+                       out.n_found, out.cells, out.pos, b.plan, out.visited, slack);
 }
 
+// many: several lists per query (short cells) -- the variant whose fast path holds 512 survivors per query
 template <int CAP>
 static void merge_survivors_m(const Batch& b, const Route& r, bool many) {
-    const int M = b.ix->m->M;
-    if (M == 4) merge_survivors<CAP, 4>(b, r, many);
-    else if (M == 8) merge_survivors<CAP, 8>(b, r, many);
-    else merge_survivors<CAP, 16>(b, r, many);
+    dispatch_int<4, 8, 16>(b.ix->m->M, [&](auto m) {  // (the fast scans serve no other M)
+        dispatch_int<4, 8>(many ? 8 : 4, [&](auto ne) { merge_survivors<CAP, decltype(m)::value, decltype(ne)::value>(b, r); });
+    });
+}
+
+// the exact scan's hits: per-query merge of the work items' ranked lists
+template <int CAPM>
+static void merge_items(const Batch& b, int S) {
+    const SearchOut& out = b.out;
+    hipLaunchKernelGGL(k_merge_items<CAPM>, dim3(b.nq), dim3(256), (size_t)CAPM * 24 + 16, b.st, b.ix->w_hits.as<cis_hit>(), b.ix->w_hitn.as<int>(), b.item_off, b.L, S,
+                       out.hits, out.ids, out.dists, out.n_found, out.cells, out.pos);
 }
 
 // 4. ADC scan + block top-k, 5. per-query merge
 static int run_scan_and_merge(Batch& b, const Route& r) {
     cis_index* ix = b.ix;
     hipStream_t st = b.st;
-    const int K = ix->m->K, M = ix->m->M, nq = b.nq, L = b.L, S = r.S;
+    const int M = ix->m->M, nq = b.nq, L = b.L, S = r.S;
     const int64_t n_items = b.n_items;
     const SearchOut& out = b.out;
     CIS_TRY(mark(b, 2));
@@ -3828,32 +3819,21 @@ static int run_scan_and_merge(Batch& b, const Route& r) {
         } else {
             CIS_TRY(mark(b, 5));
             ix->last_scan_kernel = 1;
-            launch_scan_exact(M, n_items, st, b.items, b.T, ix->codes_ptr(), ix->ids_ptr(), K, L, S, nullptr, ix->w_hits.as<cis_hit>(), ix->w_hitn.as<int>());
+            launch_scan_exact(M, scan_args(b, Slots{}), S, nullptr);
         }
         ix->stats[3] += 1;
     }
     // 5. per-query merge
     CIS_TRY(mark(b, 3));
-    {
-        const cis_hit* hits = ix->w_hits.as<cis_hit>();
-        const int* hitn = ix->w_hitn.as<int>();
-        if (r.fast) {
-            // several lists per query (short cells): the variant whose fast path holds 512 survivors per query
-            const bool many = n_items > nq + nq / 4;
-            if (L <= 128) merge_survivors_m<256>(b, r, many);
-            else if (L <= 256) merge_survivors_m<512>(b, r, many);
-            else if (L <= 440) merge_survivors_m<1024>(b, r, many);
-            else merge_survivors_m<2048>(b, r, many);
-        } else if (L <= 512)
-            hipLaunchKernelGGL(k_merge_items<1024>, dim3(nq), dim3(256), (size_t)1024 * 24 + 16, st, hits, hitn, b.item_off, L, S, out.hits,
-                               out.ids, out.dists, out.n_found, out.cells, out.pos);
-        else if (L <= 1024)
-            hipLaunchKernelGGL(k_merge_items<2048>, dim3(nq), dim3(256), (size_t)2048 * 24 + 16, st, hits, hitn, b.item_off, L, S, out.hits,
-                               out.ids, out.dists, out.n_found, out.cells, out.pos);
-        else
-            hipLaunchKernelGGL(k_merge_items<4096>, dim3(nq), dim3(256), (size_t)4096 * 24 + 16, st, hits, hitn, b.item_off, L, S, out.hits,
-                               out.ids, out.dists, out.n_found, out.cells, out.pos);
-    }
+    if (r.fast) {
+        const bool many = n_items > nq + nq / 4;
+        if (L <= 128) merge_survivors_m<256>(b, r, many);
+        else if (L <= 256) merge_survivors_m<512>(b, r, many);
+        else if (L <= 440) merge_survivors_m<1024>(b, r, many);
+        else merge_survivors_m<2048>(b, r, many);
+    } else if (L <= 512) merge_items<1024>(b, S);
+    else if (L <= 1024) merge_items<2048>(b, S);
+    else merge_items<4096>(b, S);
     if (out.visited && !r.fast)  // the survivor merge writes `visited` itself
         hipLaunchKernelGGL(k_copy_visited, dim3((unsigned)ceil_div(nq, 256)), dim3(256), 0, st, b.plan, nq, out.visited);
     CIS_CHECK_HIP(hipGetLastError());

@@ -613,23 +613,13 @@ size_t stream_lds(int M, int K, int G) { return (size_t)K * stream_copies(M, G) 
 int stream_max_group() { return 4; }
 
 template <int M, int G, bool SAMPLE>
-static void launch_stream_t(int grid, hipStream_t st, const StreamSlot* desc, const int* n_slots, const int64_t* rowoff, const float* T32,
-                            const double* T, const uint8_t* codes, int K, const float* tau, uint32_t* bmin, int B,
-                            int sample_stride, int flush, uint32_t* surv, int* cnt, int cap) {
-    hipLaunchKernelGGL((k_adc_stream<M, G, SAMPLE>), dim3((unsigned)grid), dim3(64 * CIS_STREAM_NW), stream_lds(M, K, G), st, desc, n_slots, rowoff, T32, T,
-                       codes, K, tau, bmin, B, sample_stride, flush < 1 ? 1 : flush, surv, cnt, cap);
+static void launch_stream_t(const CandArgs& c, const StreamArgs& s) {
+    hipLaunchKernelGGL((k_adc_stream<M, G, SAMPLE>), dim3((unsigned)s.grid), dim3(64 * CIS_STREAM_NW), stream_lds(M, c.K, G), c.st, static_cast<const StreamSlot*>(s.desc),
+                       s.n_slots, s.rowoff, s.T32, s.T, c.codes, c.K, s.tau, s.bmin, s.B, s.sample_stride, s.flush < 1 ? 1 : s.flush, s.surv, s.cnt, s.cap);
 }
 
-void launch_stream_scan(int M, int G, bool sample, int grid, hipStream_t st, const void* desc_, const int* n_slots, const int64_t* rowoff,
-                        const float* T32, const double* T, const uint8_t* codes, int K, const float* tau,
-                        uint32_t* bmin, int B, int sample_stride, int flush, uint32_t* surv, int* cnt, int cap) {
-    const StreamSlot* desc = static_cast<const StreamSlot*>(desc_);
-#define CIS_STREAM(MM, GG)                                                                                                              \
-    if (M == MM && G == GG) {                                                                                                           \
-        if (sample) launch_stream_t<MM, GG, true>(grid, st, desc, n_slots, rowoff, T32, T, codes, K, tau, bmin, B, sample_stride, flush, surv, cnt, cap);  \
-        else launch_stream_t<MM, GG, false>(grid, st, desc, n_slots, rowoff, T32, T, codes, K, tau, bmin, B, sample_stride, flush, surv, cnt, cap);        \
-        return;                                                                                                                         \
-    }
+void launch_stream_scan(const CandArgs& c, const StreamArgs& s, bool sample) {
+#define CIS_STREAM(MM, GG) if (s.M == MM && s.G == GG) return sample ? launch_stream_t<MM, GG, true>(c, s) : launch_stream_t<MM, GG, false>(c, s);
     CIS_STREAM(8, 1) CIS_STREAM(8, 2) CIS_STREAM(8, 4) CIS_STREAM(4, 1) CIS_STREAM(4, 2) CIS_STREAM(4, 4) CIS_STREAM(16, 1) CIS_STREAM(16, 2) CIS_STREAM(16, 4)
 #undef CIS_STREAM
 }
@@ -647,32 +637,26 @@ int stream_grid(int M, int G, int K, int64_t max_rows) {
     return (int)(g < 1 ? 1 : g);
 }
 
-void launch_stream_prep(hipStream_t st, const WorkItem* items, int64_t n_items, const int64_t* item_off, int nq, int64_t n_cand, const int* slots, int* n_slots,
-                        int G, int M, int64_t* cand_start, int64_t* seg, unsigned long long* qmin, unsigned long long* qmax, int* cnt, int* status, int64_t* rowoff,
-                        void* desc, const int64_t* d_totals) {
-    hipLaunchKernelGGL(k_stream_prep, dim3(1), dim3(1024), 0, st, items, n_items, item_off, nq, n_cand, slots, n_slots, G, 64 * (16 / M), cand_start, seg, qmin, qmax,
-                       cnt, status, rowoff, static_cast<StreamSlot*>(desc), d_totals);
+void launch_stream_prep(const CandArgs& c, const StreamArgs& s, int64_t n_cand, const int64_t* d_totals) {
+    hipLaunchKernelGGL(k_stream_prep, dim3(1), dim3(1024), 0, c.st, c.items, c.n_items, c.item_off, c.nq, n_cand, s.slots, s.n_slots, s.G, 64 * (16 / s.M), c.cand_start, c.seg,
+                       c.qmin, c.qmax, s.cnt, s.status, s.rowoff, static_cast<StreamSlot*>(s.desc), d_totals);
 }
 
-void launch_stream_tau(hipStream_t st, uint32_t* bmin, int B, int k, int nq, float* tau) {
+void launch_stream_tau(const CandArgs& c, const StreamArgs& s, int k) {
     // B = STREAM_B = 1024 threads x PER
-    hipLaunchKernelGGL(k_stream_tau<STREAM_B / 1024>, dim3((unsigned)nq), dim3(1024), 0, st, bmin, B, k, tau);
+    hipLaunchKernelGGL(k_stream_tau<STREAM_B / 1024>, dim3((unsigned)c.nq), dim3(1024), 0, c.st, s.bmin, s.B, k, s.tau);
 }
 
-void launch_stream_keys(int M, hipStream_t st, const WorkItem* items, const int64_t* cand_start, const int64_t* seg, const int64_t* item_off,
-                        int64_t n_items, const double* T, const uint8_t* codes, int K, const uint32_t* surv, const int* cnt, int cap, int nq,
-                        uint64_t* keys, unsigned long long* qmin, unsigned long long* qmax) {
-    const dim3 g((unsigned)ceil_div(cap, 256), (unsigned)nq);
-    if (M == 4) hipLaunchKernelGGL(k_stream_keys<4>, g, dim3(256), 0, st, items, cand_start, seg, item_off, n_items, T, codes, K, surv, cnt, cap, keys, qmin, qmax);
-    else if (M == 8) hipLaunchKernelGGL(k_stream_keys<8>, g, dim3(256), 0, st, items, cand_start, seg, item_off, n_items, T, codes, K, surv, cnt, cap, keys, qmin, qmax);
-    else hipLaunchKernelGGL(k_stream_keys<16>, g, dim3(256), 0, st, items, cand_start, seg, item_off, n_items, T, codes, K, surv, cnt, cap, keys, qmin, qmax);
+void launch_stream_keys(const CandArgs& c, const StreamArgs& s) {
+    const dim3 g((unsigned)ceil_div(s.cap, 256), (unsigned)c.nq);
+    dispatch_int<4, 8, 16>(s.M, [&](auto m) {  // (stream_supported admits no other M)
+        hipLaunchKernelGGL(k_stream_keys<decltype(m)::value>, g, dim3(256), 0, c.st, c.items, c.cand_start, c.seg, c.item_off, c.n_items, s.T, c.codes, c.K, s.surv, s.cnt,
+                           s.cap, s.keys, c.qmin, c.qmax);
+    });
 }
 
-void launch_stream_finish(hipStream_t st, const uint64_t* sel_keys, const uint64_t* sel_vals, const int* nsel, int64_t stride, const int* cnt, int cap,
-                          const int64_t* seg, const float* tau, int nq, int L, int M, const WorkItem* items, const int64_t* ids, const PlanOut* plan,
-                          cis_hit* out_hits, int64_t* out_ids, double* out_dists, int* out_n, int32_t* out_cells, uint32_t* out_pos, int32_t* out_visited,
-                          int* status, int64_t* status_host_dev, int64_t seq) {
-    const double eps = 2.0 * M * 5.9604644775390625e-08;  // 2 M 2^-24
-    hipLaunchKernelGGL(k_stream_finish, dim3((unsigned)nq), dim3(256), 0, st, sel_keys, sel_vals, nsel, stride, cnt, cap, seg, tau, nq, L, eps, items, ids, plan,
-                       out_hits, out_ids, out_dists, out_n, out_cells, out_pos, out_visited, status, status_host_dev, seq);
+void launch_stream_finish(const CandArgs& c, const StreamArgs& s, const SearchOut& out, int64_t* status_host_dev, int64_t seq) {
+    const double eps = 2.0 * s.M * 5.9604644775390625e-08;  // 2 M 2^-24
+    hipLaunchKernelGGL(k_stream_finish, dim3((unsigned)c.nq), dim3(256), 0, c.st, s.sel_keys, s.sel_vals, s.nsel, s.stride, s.cnt, s.cap, c.seg, s.tau, c.nq, s.L, eps, c.items,
+                       s.ids, s.plan, out.hits, out.ids, out.dists, out.n_found, out.cells, out.pos, out.visited, s.status, status_host_dev, seq);
 }

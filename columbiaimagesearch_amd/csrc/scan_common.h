@@ -3,6 +3,8 @@
 // merges of ranked hit lists (lopq_search.hip, lopq_exchange.hip); the work item, table and plan records the plan stage
 // (lopq_plan.hip) writes for them.
 #pragma once
+#include <type_traits>
+
 #include "lopq_model.h"
 
 struct WorkItem {
@@ -246,16 +248,94 @@ static __device__ __forceinline__ float tab_f1(const float* __restrict__ T32, co
     return T32 ? T32[idx] : (float)T[idx];
 }
 
+// ---- host: a run-time value as a compile-time constant -----------------------------------------------------------------------------
+// f(std::integral_constant<int, V>) for the V of the list that equals v; false when none does.  Every M ladder of the launchers is one
+// call of this; what a branch instantiates is narrowed with `if constexpr` inside f.
+template <int... Vs, typename F>
+static inline bool dispatch_int(int v, F&& f) {
+    return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+// registers per lane of a wave's hit region (it holds NR * 64 - 8 entries): 4 up to limit 184, 8 up to 440, 16 above where NR_MAX allows
+template <int NR_MAX, typename F>
+static inline void dispatch_nr(int L, F&& f) {
+    static_assert(NR_MAX == 8 || NR_MAX == 16, "dispatch_nr: the scans hold 8 or 16 registers per lane at most");
+    if (L <= 184) f(std::integral_constant<int, 4>{});
+    else if (NR_MAX == 8 || L <= 440) f(std::integral_constant<int, 8>{});
+    else if constexpr (NR_MAX == 16) f(std::integral_constant<int, 16>{});
+}
+
+// ---- host: the operands of the launchers, filled once per batch ------------------------------------------------------------------------
+struct SearchOut {  // any of these may be null; all are [nq][L] except n_found / visited [nq]
+    cis_hit* hits;
+    int64_t* ids;
+    double* dists;
+    int32_t* n_found;
+    int32_t* cells;
+    uint32_t* pos;
+    int32_t* visited;
+    SearchOut at(int64_t q0, int L) const {
+        SearchOut o = *this;
+        if (o.hits) o.hits += q0 * L;
+        if (o.ids) o.ids += q0 * L;
+        if (o.dists) o.dists += q0 * L;
+        if (o.cells) o.cells += q0 * L;
+        if (o.pos) o.pos += q0 * L;
+        if (o.n_found) o.n_found += q0;
+        if (o.visited) o.visited += q0;
+        return o;
+    }
+};
+
+// what every scan through the slot list reads and writes (run_fast_scan; the exact scan reads the work items alone)
+struct ScanArgs {
+    hipStream_t st;
+    const WorkItem* items;
+    int64_t n_items;
+    int nq;
+    const TabDesc* tabs;
+    const int *slots, *n_slots;
+    const PlanOut* plan;
+    const double* T;
+    const float* T32;  // null: the scans convert from T
+    const uint8_t* codes;
+    const int64_t* ids;
+    int K, L;
+    int* qctr;
+    uint64_t* hits;  // survivors, S per work item (the exact scan: whole cis_hit records in the same workspace)
+    int* hitn;
+    float* slack;
+    unsigned long long* qbound;
+    int* fhdr;       // [32] zeroed: fall-back slot header of the sampled forms
+    int* fslots;     // [n_slots * G]
+};
+
+// the candidate layout of the all-candidates and the streaming routes: candidates in retrieval order, query q owns seg[q] .. seg[q + 1)
+struct CandArgs {
+    hipStream_t st;
+    const WorkItem* items;
+    int64_t n_items;
+    const int64_t* item_off;
+    int64_t *cand_start, *seg;
+    unsigned long long *qmin, *qmax;  // key range per query (null where nothing selects by it)
+    int nq;
+    const uint8_t* codes;
+    int K;
+};
+
+// workgroups of a persistent scan: what the chip holds at `per_cu` per CU, fewer when the batch has fewer slots (of G work items) than that
+static inline unsigned persistent_grid(const ScanArgs& a, int G, int per_cu) {
+    const int64_t resident = 256 * (per_cu < 1 ? 1 : per_cu);
+    const int64_t want = (a.n_items + G - 1) / G + 8;
+    return (unsigned)(want < resident ? ((want + 7) / 8) * 8 : resident);
+}
+
 // ---- ADC scan v3 (lopq_scan3.hip): 16-bit fixed-point tables, four queries per workgroup ---------------------------
 struct Scan3Geom { int G, NW, U, S, two_pass, long_chunks; size_t lds;
                    float sat = 0.f; };  // > 0: the sampled form's SATURATING scale (M = 16) -- see k_adc_scan4
 bool scan3_supported(int M, int K, int L);
 Scan3Geom scan3_geom(int M, int K, int L, int64_t avg_chunk /* candidates per work item of the batch */,
                      int force_two_pass /* -1: by chunk length, 0: streaming form, 1: two-pass form */);
-void launch_scan3(int M, const Scan3Geom& g, int64_t n_items, hipStream_t st, const WorkItem* items, const TabDesc* tabs,
-                  const int* slots, const int* n_slots, const double* T, const float* T32, const uint8_t* codes, int K, int L,
-                  int* qctr, uint64_t* hits, int* hitn, float* slack, unsigned long long* qbound,
-                  int* fhdr /* [32] zeroed: fall-back slot header of the sampled form */, int* fslots /* [n_slots * G] */);
+void launch_scan3(int M, const Scan3Geom& g, const ScanArgs& a);
 
 // ---- the HBM-streaming scan (lopq_stream.hip): few queries, very many candidates each --------------------------------------
 static const int STREAM_B = 4096;     // buckets of sample minima per query (k_stream_tau: 1024 threads x 4; the k-th smallest of them, k <= B / 4, bounds the k-th smallest sample)
@@ -263,29 +343,39 @@ static const int STREAM_CAP = 16384;  // listed candidates per query at most
 bool stream_supported(int M, int K, int L);
 int stream_grid(int M, int G, int K, int64_t max_rows);
 int stream_max_group();  // queries per slot at most (1, 2 or 4 are instantiated)
-size_t stream_slot_bytes();  // one record per slot (lopq_stream.hip: StreamSlot), written by launch_stream_init
-void launch_stream_prep(hipStream_t st, const WorkItem* items, int64_t n_items, const int64_t* item_off, int nq, int64_t n_cand,
-                        const int* slots /* null: slot i = work item i alone */, int* n_slots, int G, int M, int64_t* cand_start, int64_t* seg,
-                        unsigned long long* qmin, unsigned long long* qmax, int* cnt, int* status, int64_t* rowoff /* [n_slots + 1]: rows of the slots before each */,
-                        void* desc /* [max_slots] records */, const int64_t* d_totals /* null, or the plan totals: n_items and n_cand are bounds */);
-void launch_stream_scan(int M, int G, bool sample, int grid, hipStream_t st, const void* desc, const int* n_slots, const int64_t* rowoff,
-                        const float* T32, const double* T, const uint8_t* codes, int K, const float* tau,
-                        uint32_t* bmin, int B, int sample_stride, int flush /* sampled rows a lane folds into one bucket */, uint32_t* surv, int* cnt, int cap);
-void launch_stream_tau(hipStream_t st, uint32_t* bmin /* read, then reset */, int B, int k, int nq, float* tau);
-void launch_stream_keys(int M, hipStream_t st, const WorkItem* items, const int64_t* cand_start, const int64_t* seg, const int64_t* item_off,
-                        int64_t n_items, const double* T, const uint8_t* codes, int K, const uint32_t* surv, const int* cnt, int cap, int nq,
-                        uint64_t* keys, unsigned long long* qmin, unsigned long long* qmax);
-void launch_stream_finish(hipStream_t st, const uint64_t* sel_keys, const uint64_t* sel_vals, const int* nsel, int64_t stride, const int* cnt, int cap,
-                          const int64_t* seg, const float* tau, int nq, int L, int M, const WorkItem* items, const int64_t* ids, const PlanOut* plan,
-                          cis_hit* out_hits, int64_t* out_ids, double* out_dists, int* out_n, int32_t* out_cells, uint32_t* out_pos, int32_t* out_visited,
-                          int* status, int64_t* status_host_dev, int64_t seq);
+size_t stream_slot_bytes();  // one record per slot (lopq_stream.hip: StreamSlot), written by launch_stream_prep
+struct StreamArgs {  // the route's own buffers, next to the candidate layout
+    int M, G, L, grid;
+    const int* slots;  // null: slot i = work item i alone
+    int* n_slots;
+    int64_t* rowoff;   // [n_slots + 1]: rows of the slots before each
+    void* desc;        // [max_slots] records
+    const double* T;
+    const float* T32;
+    float* tau;
+    uint32_t* bmin;    // [nq][B] sample minima (k_stream_tau reads, then resets them)
+    int B, sample_stride, flush /* sampled rows a lane folds into one bucket */;
+    uint32_t* surv;    // [nq][cap] listed candidates, cnt[q] of them
+    int* cnt;
+    int cap;
+    uint64_t* keys;    // [nq][cap] their exact keys
+    const uint64_t *sel_keys, *sel_vals;  // [nq][stride] ranked pairs, nsel[q] of them
+    const int* nsel;
+    int64_t stride;
+    const int64_t* ids;
+    const PlanOut* plan;
+    int* status;
+};
+void launch_stream_prep(const CandArgs& c, const StreamArgs& s, int64_t n_cand, const int64_t* d_totals /* null, or the plan totals: n_items and n_cand are bounds */);
+void launch_stream_scan(const CandArgs& c, const StreamArgs& s, bool sample);
+void launch_stream_tau(const CandArgs& c, const StreamArgs& s, int k);
+void launch_stream_keys(const CandArgs& c, const StreamArgs& s);
+void launch_stream_finish(const CandArgs& c, const StreamArgs& s, const SearchOut& out, int64_t* status_host_dev, int64_t seq);
 
 // ---- k_adc_scan5 (lopq_scan3.hip): one threshold per query for the whole batch, eight queries per slot -----------------------
 bool scan5_supported(int M, int K, int L);
 size_t scan5_workspace_bytes(int nq);
-void launch_scan5(int M, const Scan3Geom& g, int64_t n_items, int nq, hipStream_t st, const WorkItem* items, const TabDesc* tabs, const int* slots,
-                  const int* n_slots, const PlanOut* plan, const double* T, const float* T32, const uint8_t* codes, int K, int L, int* qctr, uint64_t* hits,
-                  int* hitn, float* slack, unsigned long long* qbound, int* fhdr, int* fslots, void* ws, hipEvent_t ev_main);
+void launch_scan5(int M, const Scan3Geom& g, const ScanArgs& a, void* ws);
 
 // ---- merges of ranked hit lists: the work items of a query (lopq_search.hip), the shards' partial results (lopq_exchange.hip) ----
 // block-wide bitonic sort of N (a power of two, chosen at run time) keys (a, b) with an optional payload, in LDS: the merge sorts

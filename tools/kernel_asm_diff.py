@@ -11,7 +11,7 @@ META = r"^    \.(vgpr_spill_count|sgpr_spill_count|vgpr_count|agpr_count|sgpr_co
 def norm(line):
     line = line.split(";")[0].rstrip()
     line = re.sub(r"\.LBB\d+_", ".LBB_", line)
-    return re.sub(r"\.L(tmp|func_begin|func_end|BB_end|sec_end)\d+", r".L\1", line)
+    return re.sub(r"\.L(tmp|func_begin|func_end|BB_end|sec_end|post_getpc)\d+", r".L\1", line)
 
 
 def kernels(paths):
