@@ -69,7 +69,9 @@ __global__ void k_km_update(float* __restrict__ C, float* __restrict__ sums, int
 // X [n][d] float32 (host), centroids [k][d] float32: initial values in, final values out.  assign [n] (or NULL) and
 // *inertia describe the assignment to the RETURNED centroids (one extra assignment pass after the last update).
 extern "C" int cis_kmeans(const float* X, int64_t n, int d, int k, int iters, float* centroids, int32_t* assign, double* inertia) {
-    CIS_REQUIRE(X && centroids && n > 0 && d > 0 && k > 0 && iters >= 0, "bad k-means arguments");
+    CIS_REQUIRE(X && centroids && d > 0 && k > 0, "bad k-means arguments");
+    CIS_REQUIRE(n > 0, "n must be > 0 (k-means of no points)");
+    CIS_REQUIRE(iters >= 0, "iters must be >= 0");
     CIS_REQUIRE((size_t)k * d <= 7680, "k * d must be <= 7680 (centroids and block sums live in LDS)");
     CIS_TRY(cis_lazy_init());
     float *dX = nullptr, *dC = nullptr, *dS = nullptr;

@@ -121,7 +121,8 @@ struct TrainBufs {
 };
 
 extern "C" int cis_train_gram(const double* X, int64_t n, int d, const int64_t* group_off, int groups, double* G, double* S) {
-    CIS_REQUIRE(X && group_off && G && n >= 0 && d > 0 && groups > 0, "bad arguments");
+    CIS_REQUIRE(X && group_off && G && n >= 0 && d > 0, "bad arguments");
+    CIS_REQUIRE(groups > 0, "groups must be > 0");
     CIS_REQUIRE(group_off[0] == 0 && group_off[groups] == n, "group offsets must cover [0, n)");
     CIS_TRY(cis_lazy_init());
     TrainBufs b;
@@ -146,7 +147,8 @@ extern "C" int cis_train_gram(const double* X, int64_t n, int d, const int64_t* 
 
 extern "C" int cis_train_project(const double* X, int64_t n, int d, const int64_t* group_off, int groups, const double* R,
                                  const double* mu, double* Y) {
-    CIS_REQUIRE(X && group_off && R && mu && Y && n >= 0 && d > 0 && groups > 0, "bad arguments");
+    CIS_REQUIRE(X && group_off && R && mu && Y && n >= 0 && d > 0, "bad arguments");
+    CIS_REQUIRE(groups > 0, "groups must be > 0");
     CIS_REQUIRE(group_off[0] == 0 && group_off[groups] == n, "group offsets must cover [0, n)");
     if (n == 0) return CIS_OK;
     CIS_TRY(cis_lazy_init());
