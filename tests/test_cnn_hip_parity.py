@@ -1,6 +1,8 @@
 """GPU parity of the DeepSentibank forward against the CPU restatement (oracle/cnn_oracle.py), seeded synthetic
 weights.  float32 everywhere; the MFMA accumulates k-ascending in float32 like caffe's sgemm would, only the
-order differs => tolerance 2e-4 relative to the feature scale (parity with caffe itself is unpinned)."""
+order differs => tolerance 2e-4 relative to the feature scale (parity with caffe itself is unpinned).
+These tolerance tests cover the dense arithmetic (every weight non-zero, long float32 sums); exactness, layer by layer and route by
+route, lives in tests/test_cnn_probe_nets.py."""
 import os
 
 import numpy as np
