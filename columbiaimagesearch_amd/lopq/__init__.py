@@ -1,10 +1,10 @@
 """Drop-in for the reference's vendored ``lopq`` package (lopq/lopq/__init__.py)."""
-from . import model, search, utils
+from . import eval, model, search, utils
 from .model import LOPQCode, LOPQModel, LOPQModelPCA
 from .search import LOPQSearcher, LOPQSearcherHIP, LOPQSearcherLMDB, multisequence
 
 __all__ = ["LOPQModel", "LOPQModelPCA", "LOPQSearcher", "LOPQSearcherHIP", "LOPQSearcherLMDB", "LOPQCode", "multisequence", "model", "search",
-           "utils"]
+           "utils", "eval"]
 
 
 def install_as_lopq():
@@ -16,3 +16,4 @@ def install_as_lopq():
     sys.modules["lopq.model"] = model
     sys.modules["lopq.search"] = search
     sys.modules["lopq.utils"] = utils
+    sys.modules["lopq.eval"] = eval

@@ -24,7 +24,8 @@ class ResidentFeatures(object):
         if not (feats.is_cuda and feats.is_contiguous() and feats.dim() == 2 and feats.dtype in (torch.float32, torch.float64)):
             raise ValueError("feats must be a contiguous float32/float64 [n, D] tensor on the GPU")
         self.feats = feats
-        self._row = None if ids is None else {k: i for i, k in enumerate(ids)}
+        self._ids = None if ids is None else list(ids)
+        self._row = None if ids is None else {k: i for i, k in enumerate(self._ids)}
 
     def rows_of(self, ids):
         """Feature row of every id ([nq, L] array-like; -1 where the id is unknown or negative)."""
@@ -49,6 +50,31 @@ class ResidentFeatures(object):
                                              q.data_ptr(), nq, rows.data_ptr(), L, out.data_ptr(),
                                              torch.cuda.current_stream(q.device).cuda_stream))
         return out
+
+    def search_exact(self, q, k):
+        """The exact k nearest resident features of every query (include/cis_hip.h:cis_exact_knn_dev): (ids, dists) [nq, k] numpy
+        arrays, ranked by (distance, row); dists float64, NOT squared (the convention of `rerank`).  With more than n features asked
+        for, the tail holds id -1 (None for non-numeric ids) and NaN.  This is what the ADC search approximates."""
+        import torch
+        if not (q.is_cuda and q.is_contiguous() and q.dim() == 2 and q.dtype in (torch.float32, torch.float64)
+                and q.shape[1] == self.feats.shape[1]):
+            raise ValueError("q must be a contiguous float32/float64 [nq, D] tensor on the GPU with the features' width")
+        nq, k = int(q.shape[0]), int(k)
+        rows = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=q.device)
+        dists = torch.empty((nq, max(k, 0)), dtype=torch.float64, device=q.device)
+        code = lambda t: _lib.CIS_F32 if t.dtype == torch.float32 else _lib.CIS_F64
+        _lib.check(_lib.lib().cis_exact_knn_dev(self.feats.data_ptr(), code(self.feats), int(self.feats.shape[0]), int(self.feats.shape[1]),
+                                                q.data_ptr(), code(q), nq, k, 0, 0, rows.data_ptr(), dists.data_ptr(),
+                                                torch.cuda.current_stream(q.device).cuda_stream))
+        rows, dists = rows.cpu().numpy(), dists.cpu().numpy()
+        if self._ids is None:
+            return rows, dists
+        table = np.asarray(self._ids)
+        if table.dtype.kind in "iu":
+            ids = np.where(rows >= 0, table[np.maximum(rows, 0)], -1)
+        else:
+            ids = np.where(rows >= 0, table.astype(object)[np.maximum(rows, 0)], None)
+        return ids, dists
 
     def rerank(self, q, ids, adc_dists, rerank_nb=None, max_returned=None, near_dup_th=None):
         """Re-rank the results of a batch: ids / adc_dists [nq, L] (ids < 0 or NaN distance = no result).

@@ -278,6 +278,25 @@ int cis_exchange_offsets_dev(const int32_t* d_cnt_all, int world, int nq, int64_
 int cis_rerank_dev(const void* d_feats, int f_dtype, int64_t n_feats, int D, const void* d_q, int nq,
                    const int64_t* d_rows, int L, double* d_dists, void* stream);
 
+/* Exact k nearest neighbours (csrc/lopq_eval.hip): the ground truth of lopq.eval (lopq/lopq/eval.py:7-38: scipy's cdist + argmin /
+ * argsort per row).  data [m2][d] and q [m1][d], each float32 or float64 (mixed allowed: the reference promotes both to float64).
+ * dist = sqrt(s), s the float64 chain s = s + (x[i] - y[i])^2 for i ascending, every operation rounded on its own -- scipy's value
+ * bit for bit.  For every query the min(k, rows seen) rows with the smallest (dist, base + row) in ascending order: idx [m1][k]
+ * (-1 padded), dist [m1][k] (NaN padded); equal distances order by index, so k = 1 is np.argmin.  accumulate != 0: the current
+ * contents of idx / dist are candidates too (padded entries are empty), so a caller streams data in chunks, in any order, with
+ * base = first row of the chunk.  k <= 1024 (CIS_EUNSUPPORTED above).  m1 == 0 or m2 == 0 is CIS_OK.  A NaN distance ranks after
+ * every number.  The calls share one process-wide workspace: they must not overlap on two streams or threads.
+ * cis_exact_knn_set_mode: 0 = float32 matrix-core prefilter with exact re-check (default), 1 = the exact-only path for every query
+ * (tests; both give the same answer). */
+int cis_exact_knn_dev(const void* d_data, int data_dtype, int64_t m2, int d, const void* d_q, int q_dtype, int m1, int k,
+                      int64_t base, int accumulate, int64_t* d_idx, double* d_dist, void* stream);
+int cis_exact_knn(const void* data, int data_dtype, int64_t m2, int d, const void* q, int q_dtype, int m1, int k, int64_t base,
+                  int accumulate, int64_t* idx, double* dist);
+int cis_exact_knn_set_mode(int mode);
+/* Counters of the last internal pass of the last call (at most 8192 queries x 2^24 rows; waits for the device):
+ * stats[0] its queries, stats[1] those the exact-only kernel answered, stats[2] rows the prefilter left to re-score for the others. */
+int cis_exact_knn_stats(int64_t stats[3]);
+
 /* Lloyd iterations for training the coarse and fine codebooks (lopq/lopq/model.py:339-437 uses scikit-learn k-means;
  * k-means is not bit-reproducible across libraries, so this is judged by distortion).  X [n][d] float32 (host),
  * centroids [k][d] float32: initial centroids in, trained centroids out; k * d <= 7680.  assign [n] (or NULL) and *inertia
