@@ -1474,6 +1474,20 @@ static __device__ __forceinline__ void wave_bitonic_lds(uint64_t* ka, uint64_t* 
     }
 }
 
+// What the merge uses of a work item.  Every lane holds the fields of the query's list (lane & 3), and a lane that needs list l
+// fetches them from lane l with a cross-lane read: four lists of wave-uniform fields in scalar registers, beside the kernel's
+// nineteen operands, overflow the scalar file, and the scheduler then serialises the table loads to save registers.
+struct MergeList {
+    int64_t start;
+    int tab0, tab1, rank, pos0, len, cell;
+    float slack, ub;  // item_slack: (slack, scale)
+};
+static __device__ __forceinline__ int from_lane(int v, int l) { return __builtin_amdgcn_ds_bpermute(l << 2, v); }
+static __device__ __forceinline__ float from_lane(float v, int l) { return __int_as_float(from_lane(__float_as_int(v), l)); }
+static __device__ __forceinline__ int64_t from_lane(int64_t v, int l) {
+    return (int64_t)(((uint64_t)(uint32_t)from_lane((int)((uint64_t)v >> 32), l) << 32) | (uint32_t)from_lane((int)v, l));
+}
+
 template <int CAPM, int MT /* 4, 8, 16, or 0 = any M */, int NEMAX /* 4 or 8: survivors per lane the fast path may hold */>
 #ifndef CIS_MERGE_WPE
 #define CIS_MERGE_WPE 4
@@ -1492,7 +1506,8 @@ void k_merge_survivors(const uint64_t* __restrict__ surv /* [n_items][S] */,
                                                          distances within eps of the exact ones (k_adc_scan2); else they are upper bounds of
                                                          the exact distances, at most item_slack[item] above them (k_adc_scan3) */) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lane = threadIdx.x & 63, wq = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
+    const int wq = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // wave-uniform: the query's offsets and counts are scalar loads
     const int q = blockIdx.x * 4 + wq;
     if (q >= nq) return;  // whole wave; nothing below synchronises across waves
     if (lane == 0 && out_visited) out_visited[q] = plan[q].visited;
@@ -1503,29 +1518,35 @@ void k_merge_survivors(const uint64_t* __restrict__ surv /* [n_items][S] */,
     const int nf = M / 2;
     int have = 0, l = 0, e = 0, total = 0;
     bool done_fast = false;
+    // Everything the query needs to know about its first four lists is read in one round trip behind item_off: none of it
+    // depends on the survivors.  The output phase finds a hit's work item here again, not in global memory.
+    MergeList mine{};
+    int cntl[4] = {0, 0, 0, 0};
+    if (n_lists >= 1) {
+        const int64_t j = first + min(lane & 3, n_lists - 1);  // lists past the query's last repeat it: valid addresses, never selected
+        const WorkItem it = items[j];
+        const int cnt = item_n[j];
+        if (item_slack) { mine.slack = item_slack[2 * j]; mine.ub = item_slack[2 * j + 1]; }
+        mine.start = it.start; mine.tab0 = it.tab0; mine.tab1 = it.tab1; mine.rank = it.rank;
+        mine.pos0 = it.pos0; mine.len = it.len; mine.cell = it.cell;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) cntl[i] = i < n_lists ? __builtin_amdgcn_readlane(cnt, i) : 0;
+    }
     if constexpr (MT != 0) {
         // Usual case: <= 4 lists, <= 256 survivors in all.  The survivors carry their float32 distances: find the value v
         // that `limit` of them do not exceed (ballot bisection in registers) and drop everything above v*(1+3eps) BEFORE
         // the exact re-scoring -- strictly worse, in exact arithmetic, than the `limit` entries below v (the scan's own
         // argument).  ~limit/130 of the table reads, and the sort runs on 128 keys instead of 256.
-        int cntl[4] = {0, 0, 0, 0}, n_total = 0;
-        if (n_lists <= 4) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                if (i < n_lists) cntl[i] = item_n[first + i];
-                n_total += cntl[i];
-            }
-        }
+        const int n_total = cntl[0] + cntl[1] + cntl[2] + cntl[3];
         auto fast = [&](auto ne_tag) -> bool {
             constexpr int NE = decltype(ne_tag)::value;  // survivors per lane
             uint32_t hi[NE], pp[NE];
             int li[NE];
             bool valid[NE];
             uint32_t mn = 0xffffffffu, mx = 0u;
-            // (the lane's NE survivors and their lists' scales are read together, from clamped addresses: as `valid ? surv[..] : ~0`
-            // they were NE round trips one after the other at the head of every query's chain of dependent loads)
+            // (the lane's NE survivors are read together, from clamped addresses: as `valid ? surv[..] : ~0` they were NE round
+            // trips one after the other at the head of every query's chain of dependent loads)
             uint64_t ent[NE];
-            float ubv[NE];
 #pragma unroll
             for (int i = 0; i < NE; ++i) {
                 const int x = lane + 64 * i;
@@ -1537,22 +1558,18 @@ void k_merge_survivors(const uint64_t* __restrict__ surv /* [n_items][S] */,
                 li[i] = lst;
                 ent[i] = surv[valid[i] ? (first + lst) * (int64_t)S + off : first * (int64_t)S];
             }
-            if (item_slack) {
-#pragma unroll
-                for (int i = 0; i < NE; ++i) ubv[i] = item_slack[2 * (first + (valid[i] ? li[i] : 0)) + 1];
-            }
 #pragma unroll
             for (int i = 0; i < NE; ++i) {
                 hi[i] = valid[i] ? (uint32_t)(ent[i] >> 32) : 0xffffffffu;
                 pp[i] = valid[i] ? (uint32_t)ent[i] : 0xffffffffu;
+                const float ub_i = from_lane(mine.ub, li[i]);  // (every lane takes part in a cross-lane read: outside the condition)
                 if (item_slack && valid[i])  // k_adc_scan3 hands over the 16-bit sum: (sum + M) * ub >= the exact distance
-                    hi[i] = __float_as_uint(__double2float_ru((double)(hi[i] + (uint32_t)MT) * (double)ubv[i]));
+                    hi[i] = __float_as_uint(__double2float_ru((double)(hi[i] + (uint32_t)MT) * (double)ub_i));
                 mn = (valid[i] && hi[i] < mn) ? hi[i] : mn;
                 mx = (valid[i] && hi[i] > mx) ? hi[i] : mx;
             }
             uint32_t thr = 0xffffffffu;
             float vub = __int_as_float(0x7f800000);  // scan3 survivors: a distance that `limit` of them do not exceed
-            float sl[4] = {0.f, 0.f, 0.f, 0.f};
             if (n_total > limit) {
                 wave_minmax_step<1>(mn, mx); wave_minmax_step<2>(mn, mx); wave_minmax_step<4>(mn, mx);
                 wave_minmax_step<8>(mn, mx); wave_minmax_step<16>(mn, mx); wave_minmax_step<32>(mn, mx);
@@ -1561,8 +1578,6 @@ void k_merge_survivors(const uint64_t* __restrict__ surv /* [n_items][S] */,
                 const uint32_t v = wave_kth_bisect<NE>(hi, valid, mn, mx, limit);
                 if (item_slack) {
                     vub = __uint_as_float(v);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) sl[i] = (i < n_lists) ? item_slack[2 * (first + i)] : 0.f;
                 } else {
                     const float margin = 1.0f + 3.0f * (2.0f * (float)MT * 5.9604645e-8f);
                     thr = __float_as_uint(__double2float_ru((double)__uint_as_float(v) * (double)margin));
@@ -1574,8 +1589,8 @@ void k_merge_survivors(const uint64_t* __restrict__ surv /* [n_items][S] */,
 #pragma unroll
             for (int i = 0; i < NE; ++i) {
                 keep[i] = valid[i] && hi[i] <= thr;
+                const float s_i = from_lane(mine.slack, li[i]);
                 if (item_slack) {  // strictly worse than `limit` others only if even its lower bound is above vub
-                    const float s_i = li[i] == 0 ? sl[0] : (li[i] == 1 ? sl[1] : (li[i] == 2 ? sl[2] : sl[3]));
                     keep[i] = valid[i] && ((double)__uint_as_float(hi[i]) - (double)s_i <= (double)vub);  // exact in float64
                 }
                 const unsigned long long m = __ballot(keep[i]);
@@ -1583,38 +1598,27 @@ void k_merge_survivors(const uint64_t* __restrict__ surv /* [n_items][S] */,
                 kept += __popcll(m);
             }
             if (kept > CAPM) return false;  // a crowd of equal float32 distances: the general rounds below
-            WorkItem its[4];
+            // Only the kept entries are re-scored, compacted: (list, position) goes to the wave's sort region at the entry's
+            // prefix index and comes back one candidate per lane, so a pass of 64 candidates holds M table entries per lane in
+            // flight and no pass is spent on entries the cut dropped.
 #pragma unroll
-            for (int i = 0; i < 4; ++i) its[i] = items[first + (i < n_lists ? i : 0)];
-            // exact re-scoring of the kept entries, four per lane at a time: codes first, then 4 x M table entries in flight
-#pragma unroll
-            for (int i0 = 0; i0 < NE; i0 += 4) {
-                int64_t startv[4];
-                const double* t0v[4];
-                const double* t1v[4];
-                uint32_t rankv[4], pos0v[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    WorkItem it = its[0];
-#pragma unroll
-                    for (int j = 1; j < 4; ++j)
-                        if (li[i0 + i] == j) it = its[j];
-                    startv[i] = it.start; rankv[i] = (uint32_t)it.rank; pos0v[i] = (uint32_t)it.pos0;
-                    t0v[i] = T + (int64_t)it.tab0 * nf * K;
-                    t1v[i] = T + (int64_t)it.tab1 * nf * K;
-                }
-                CodeWords<MT> cw[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) cw[i] = load_code<MT>(codes, startv[i] + (keep[i0 + i] ? pp[i0 + i] : 0u));
-                double dd[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) dd[i] = adc64_words<MT>(cw[i].w, K, t0v[i], t1v[i]);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    if (keep[i0 + i]) {
-                        ka[idx[i0 + i]] = (uint64_t)__double_as_longlong(dd[i]);
-                        kb[idx[i0 + i]] = ((uint64_t)rankv[i] << 32) | (uint32_t)(pos0v[i] + pp[i0 + i]);
-                    }
+            for (int i = 0; i < NE; ++i)
+                if (keep[i]) kb[idx[i]] = ((uint64_t)(uint32_t)li[i] << 32) | pp[i];
+            wave_lds_sync();
+#pragma unroll 1
+            for (int c0 = 0; c0 < kept; c0 += 64) {
+                const bool on = c0 + lane < kept;
+                const int c = on ? c0 + lane : c0;  // an idle lane re-scores the pass's first candidate and drops the result
+                const uint64_t lp = kb[c];
+                const int lst = (int)(lp >> 32);
+                const uint32_t p = (uint32_t)lp;
+                const CodeWords<MT> cw = load_code<MT>(codes, from_lane(mine.start, lst) + p);
+                const double d = adc64_words<MT>(cw.w, K, T + (int64_t)from_lane(mine.tab0, lst) * nf * K,
+                                                 T + (int64_t)from_lane(mine.tab1, lst) * nf * K);
+                const uint32_t rank = (uint32_t)from_lane(mine.rank, lst), pos0 = (uint32_t)from_lane(mine.pos0, lst);
+                if (on) {
+                    ka[c] = (uint64_t)__double_as_longlong(d);
+                    kb[c] = ((uint64_t)rank << 32) | (pos0 + p);
                 }
             }
             int ns = 64;
@@ -1693,24 +1697,50 @@ void k_merge_survivors(const uint64_t* __restrict__ surv /* [n_items][S] */,
     }
     const int nv = total < limit ? total : limit;
     const int64_t o = (int64_t)q * limit;
+    // the first four lists' fields, wave-uniform from here on: the ids gather is the only global load between the sort and the stores
+    int64_t l_start[4];
+    uint32_t l_pos0[4], l_rank[4], l_len[4];
+    int l_cell[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        l_start[i] = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)((uint64_t)mine.start >> 32), i) << 32) |
+                               (uint32_t)__builtin_amdgcn_readlane((int)mine.start, i));
+        l_pos0[i] = (uint32_t)__builtin_amdgcn_readlane(mine.pos0, i);
+        l_rank[i] = (uint32_t)__builtin_amdgcn_readlane(mine.rank, i);
+        l_len[i] = i < n_lists ? (uint32_t)__builtin_amdgcn_readlane(mine.len, i) : 0u;  // a list the query does not have holds nothing
+        l_cell[i] = __builtin_amdgcn_readlane(mine.cell, i);
+    }
     for (int x = lane; x < limit; x += 64) {
         cis_hit hh;
         hh.dist = __longlong_as_double(0x7ff0000000000000LL);
         hh.visit_rank = 0xffffffffu; hh.pos = 0xffffffffu; hh.id = -1; hh.cell = -1; hh.reserved = 0;
         if (x < nv) {
             const uint32_t rank = (uint32_t)(kb[x] >> 32), pos = (uint32_t)kb[x];
-            // the work item this hit came from: same cell (visit rank), chunk that contains the position
-            for (int li = 0; li < n_lists; ++li) {
+            // the work item this hit came from: same cell (visit rank), chunk that contains the position; the first such list
+            int64_t src = -1;
+            int cell = -1;
+#pragma unroll
+            for (int li = 3; li >= 0; --li) {
+                const uint32_t rel = pos - l_pos0[li];
+                if (l_rank[li] == rank && rel < l_len[li]) {
+                    src = l_start[li] + rel;
+                    cell = l_cell[li];
+                }
+            }
+            for (int li = 4; li < n_lists && src < 0; ++li) {
                 const WorkItem it = items[first + li];
                 const uint32_t rel = pos - (uint32_t)it.pos0;
                 if ((uint32_t)it.rank == rank && rel < (uint32_t)it.len) {
-                    hh.dist = __longlong_as_double((long long)ka[x]);
-                    hh.visit_rank = rank;
-                    hh.pos = pos;
-                    hh.id = ids[it.start + rel];
-                    hh.cell = it.cell;
-                    break;
+                    src = it.start + rel;
+                    cell = it.cell;
                 }
+            }
+            if (src >= 0) {
+                hh.dist = __longlong_as_double((long long)ka[x]);
+                hh.visit_rank = rank;
+                hh.pos = pos;
+                hh.id = ids[src];
+                hh.cell = cell;
             }
         }
         if (out_hits) out_hits[o + x] = hh;
