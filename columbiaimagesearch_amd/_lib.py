@@ -95,6 +95,11 @@ _PROTOS = {
     "cis_extract_chips_dev": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "cis_exchange_offsets_dev": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cis_rerank_dev": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "cis_idmap_build_dev": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+    "cis_idmap_lookup_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    "cis_rerank_select_dev": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p,
+                                      c_void_p, c_int, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p]),
     "cis_exact_knn_dev": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_int, c_int64, c_int, c_void_p, c_void_p,
                                   c_void_p]),
     "cis_exact_knn": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_int, c_int64, c_int, c_void_p, c_void_p]),

@@ -242,6 +242,20 @@ class LOPQSearcherHIP(LOPQSearcherBase):
         dev_id = int(dev_id)
         return self._id_of[dev_id - _SLOT_BASE] if dev_id >= _SLOT_BASE else dev_id
 
+    def device_ids_of(self, ids):
+        """The device id (what search_batch returns in ``ids``) of every caller id, as an int64 array: an integer id is its own,
+        another id is 2^62 + its slot, and -1 stands for an id this searcher has never been given.  A pure look-up: unlike an
+        insert it creates no slot.  This is what ResidentFeatures.device_map needs for ids such as the reference's sha1_bbox."""
+        ids = list(ids)
+        out = np.empty(len(ids), dtype=np.int64)
+        for k, item_id in enumerate(ids):
+            if _is_int(item_id):
+                out[k] = int(item_id) if int(item_id) >= 0 else -1
+            else:
+                slot = self._slot_of.get(item_id)
+                out[k] = -1 if slot is None else _SLOT_BASE + slot
+        return out
+
     # -- insert ----------------------------------------------------------------------------------
     def add_codes_array(self, coarse, fine, ids=None, dedup=True):
         """Insert n codes given as arrays (coarse [n,2], fine [n,M]).  Same semantics as add_codes:
@@ -439,6 +453,15 @@ class LOPQSearcherHIP(LOPQSearcherBase):
                                                    -1 if limit is None else int(limit), out["ids"].data_ptr(),
                                                    out["dists"].data_ptr(), out["n_found"].data_ptr(),
                                                    out["visited"].data_ptr(), cells, pos, stream))
+        return out
+
+    def search_rerank_dev(self, q, feats, quota=10, limit=None, rerank_nb=None, max_returned=None, near_dup_th=None):
+        """search_batch_dev followed by feats.rerank_dev (feats: a rerank.ResidentFeatures of the queries' width and dtype) on the
+        current stream, with nothing copied to the host in between: the reference's answer to a query batch
+        (searcher_lopqhbase.py:849-912).  Returns rerank_dev's dict (ids, dists, src, n_kept) plus ``visited``."""
+        r = self.search_batch_dev(q, quota=quota, limit=limit)
+        out = feats.rerank_dev(q, r["ids"], r["dists"], rerank_nb=rerank_nb, max_returned=max_returned, near_dup_th=near_dup_th)
+        out["visited"] = r["visited"]
         return out
 
     def search_partial_dev(self, q, quota=10, limit=None):

@@ -26,6 +26,7 @@ class ResidentFeatures(object):
         self.feats = feats
         self._ids = None if ids is None else list(ids)
         self._row = None if ids is None else {k: i for i, k in enumerate(self._ids)}
+        self._dmap = None  # (keys, rows, event of the build): device_map
 
     def rows_of(self, ids):
         """Feature row of every id ([nq, L] array-like; -1 where the id is unknown or negative)."""
@@ -75,6 +76,102 @@ class ResidentFeatures(object):
         else:
             ids = np.where(rows >= 0, table.astype(object)[np.maximum(rows, 0)], None)
         return ids, dists
+
+    # -- the same on the device: id -> row map, look-up and the fused re-rank (csrc/lopq_rerank.hip) ---------------------------
+    def device_map(self, dev_ids=None):
+        """Builds the device id -> feature row map on the current stream and caches it; returns (keys, rows) int64 tensors, or
+        None for the identity (no ids were given: id = row, no table is built).  Integer ids are their own device ids; with
+        other ids pass dev_ids, one int64 per row (LOPQSearcherHIP.device_ids_of(ids)).  A repeated id maps to its last row, a
+        negative one to nothing.  Later calls on other streams wait for the build."""
+        import torch
+        if dev_ids is None:
+            if self._ids is None:
+                return None
+            if self._dmap is not None:
+                return self._dmap[:2]
+            table = np.asarray(self._ids)
+            if table.dtype.kind not in "iu" or table.ndim != 1 or (table.dtype.kind == "u" and table.size and int(table.max()) >= 1 << 63):
+                raise ValueError("the ids are not int64 integers: pass dev_ids, one int64 device id per feature row "
+                                 "(LOPQSearcherHIP.device_ids_of)")
+            dev_ids = torch.as_tensor(np.ascontiguousarray(table, dtype=np.int64))
+        elif not torch.is_tensor(dev_ids):
+            dev_ids = torch.as_tensor(np.ascontiguousarray(dev_ids, dtype=np.int64))
+        dev = self.feats.device
+        dev_ids = dev_ids.to(dev).contiguous()
+        n = int(self.feats.shape[0])
+        if dev_ids.dtype != torch.int64 or tuple(dev_ids.shape) != (n,):
+            raise ValueError("dev_ids must be int64, one per feature row (%d)" % n)
+        cap = 2
+        while cap < 2 * n:
+            cap *= 2
+        keys = torch.empty(cap, dtype=torch.int64, device=dev)
+        rows = torch.empty(cap, dtype=torch.int64, device=dev)
+        _lib.check(_lib.lib().cis_idmap_build_dev(dev_ids.data_ptr(), n, keys.data_ptr(), rows.data_ptr(), cap,
+                                                  torch.cuda.current_stream(dev).cuda_stream))
+        built = torch.cuda.Event()
+        built.record(torch.cuda.current_stream(dev))
+        self._dmap = (keys, rows, built)
+        return keys, rows
+
+    def _map_args(self, stream):
+        """(keys pointer, rows pointer, cap) of the cached map, built on first use; `stream` is made to wait for the build."""
+        if self._ids is None and self._dmap is None:
+            return None, None, 0
+        if self._dmap is None:
+            self.device_map()
+        keys, rows, built = self._dmap
+        stream.wait_event(built)
+        return keys.data_ptr(), rows.data_ptr(), int(keys.shape[0])
+
+    def rows_of_dev(self, ids):
+        """rows_of on the device: int64 tensor of ids' shape, -1 where the (device) id is unknown or negative.  No synchronise."""
+        import torch
+        if not (torch.is_tensor(ids) and ids.is_cuda and ids.is_contiguous() and ids.dtype == torch.int64):
+            raise ValueError("ids must be a contiguous int64 tensor on the GPU")
+        st = torch.cuda.current_stream(ids.device)
+        keys, rows, cap = self._map_args(st)
+        out = torch.empty_like(ids)
+        _lib.check(_lib.lib().cis_idmap_lookup_dev(keys, rows, cap, int(self.feats.shape[0]), ids.data_ptr(), ids.numel(),
+                                                   out.data_ptr(), st.cuda_stream))
+        return out
+
+    def rerank_dev(self, q, ids, adc, rerank_nb=None, max_returned=None, near_dup_th=None, out=None):
+        """`rerank` with everything on the device and one kernel: q [nq, D] of the features' dtype, ids int64 [nq, L] device ids
+        (< 0: no result), adc float64 [nq, L].  Returns a dict of tensors [nq, nb], nb = min(rerank_nb, L): ``ids`` (-1 padded),
+        ``dists`` float64 (NaN padded; bit for bit the distances of `rerank`), ``src`` int32 (the place of a result in `ids`
+        before the re-order) and ``n_kept`` int32 [nq].  Runs on the current stream; no synchronise, no host copy.  `out`: such
+        a dict to write into.  nb > 1024 is a ValueError: the host `rerank` serves those."""
+        import torch
+        if not (q.is_cuda and q.is_contiguous() and q.dim() == 2 and q.dtype == self.feats.dtype and q.shape[1] == self.feats.shape[1]):
+            raise ValueError("q must be a contiguous [nq, D] tensor on the GPU with the features' dtype and width")
+        nq = int(q.shape[0])
+        for t, dt, what in ((ids, torch.int64, "ids"), (adc, torch.float64, "adc")):
+            if not (torch.is_tensor(t) and t.is_cuda and t.is_contiguous() and t.dim() == 2 and t.dtype == dt and t.shape[0] == nq):
+                raise ValueError("%s must be a contiguous %s [nq, L] tensor on the GPU" % (what, str(dt).split(".")[-1]))
+        if ids.shape != adc.shape:
+            raise ValueError("ids and adc must have the same shape")
+        L = int(ids.shape[1])
+        nb = L if rerank_nb is None else min(int(rerank_nb), L)
+        if nb < 0 or (max_returned or 0) < 0:
+            raise ValueError("rerank_nb and max_returned must be >= 0")
+        dev = q.device
+        shapes = (("ids", torch.int64, (nq, nb)), ("dists", torch.float64, (nq, nb)), ("src", torch.int32, (nq, nb)),
+                  ("n_kept", torch.int32, (nq,)))
+        if out is None:
+            out = {k: torch.empty(shp, dtype=dt, device=dev) for k, dt, shp in shapes}
+        for k, dt, shp in shapes:
+            t = out[k]
+            if not (t.is_cuda and t.is_contiguous() and t.dtype == dt and tuple(t.shape) == shp):
+                raise ValueError("out[%r] must be a contiguous %s tensor of shape %r on the GPU" % (k, str(dt).split(".")[-1], shp))
+        st = torch.cuda.current_stream(dev)
+        keys, rows, cap = self._map_args(st)
+        code = _lib.CIS_F32 if q.dtype == torch.float32 else _lib.CIS_F64
+        _lib.check(_lib.lib().cis_rerank_select_dev(
+            self.feats.data_ptr(), code, int(self.feats.shape[0]), int(self.feats.shape[1]), keys, rows, cap, q.data_ptr(), nq,
+            ids.data_ptr(), adc.data_ptr(), L, nb, int(max_returned or 0), 0 if near_dup_th is None else 1,
+            0.0 if near_dup_th is None else float(near_dup_th), out["ids"].data_ptr(), out["dists"].data_ptr(),
+            out["src"].data_ptr(), out["n_kept"].data_ptr(), st.cuda_stream))
+        return out
 
     def rerank(self, q, ids, adc_dists, rerank_nb=None, max_returned=None, near_dup_th=None):
         """Re-rank the results of a batch: ids / adc_dists [nq, L] (ids < 0 or NaN distance = no result).

@@ -278,6 +278,27 @@ int cis_exchange_offsets_dev(const int32_t* d_cnt_all, int world, int nq, int64_
 int cis_rerank_dev(const void* d_feats, int f_dtype, int64_t n_feats, int D, const void* d_q, int nq,
                    const int64_t* d_rows, int L, double* d_dists, void* stream);
 
+/* Device id -> feature row map (csrc/lopq_rerank.hip): an open-addressing table in memory the caller owns, d_keys [cap] and
+ * d_rows [cap] int64, cap a power of two >= 2 n (anything else: CIS_EINVAL).  The build fills both with -1 and inserts
+ * d_ids [n] by kernels on `stream` (linear probing from a 64-bit mixed hash); a negative id is skipped and a repeated id maps
+ * to its LAST row, like {k: i for i, k in enumerate(ids)}.  The look-up writes d_out[i] = row of d_ids[i] (m of them), -1 for an
+ * unknown or negative id or a row >= n_feats; d_keys = d_rows = NULL is the identity map: row = id when 0 <= id < n_feats. */
+int cis_idmap_build_dev(const int64_t* d_ids, int64_t n, int64_t* d_keys, int64_t* d_rows, int64_t cap, void* stream);
+int cis_idmap_lookup_dev(const int64_t* d_keys, const int64_t* d_rows, int64_t cap, int64_t n_feats, const int64_t* d_ids, int64_t m,
+                         int64_t* d_out, void* stream);
+
+/* Search results -> the reference's final answer in one kernel, nothing through the host (searcher_lopqhbase.py:864-912,
+ * :975-1017).  For each of nq queries the first nb <= min(L, 1024) of its results d_ids / d_adc [nq][L] (id < 0: no result) are
+ * looked up in the id map (NULL, NULL: the identity), measured against d_feats [n_feats][D] (the distance of cis_rerank_dev
+ * bit for bit; a result whose feature is not resident keeps its ADC distance), kept if their place BEFORE the re-order is below
+ * max_returned (0: no cut) and their distance <= near_dup_th (when use_th != 0; compared as float64), and ranked by
+ * (distance, place): np.argsort(kind="stable").  Outputs [nq][nb]: d_out_ids (-1 padded), d_out_dists (NaN padded), d_out_src
+ * (the place a result had in d_ids, -1 padded); d_n_kept [nq].  nb > 1024 is CIS_EINVAL: such calls stay with the host path. */
+int cis_rerank_select_dev(const void* d_feats, int f_dtype, int64_t n_feats, int D, const int64_t* d_map_keys,
+                          const int64_t* d_map_rows, int64_t map_cap, const void* d_q, int nq, const int64_t* d_ids,
+                          const double* d_adc, int L, int nb, int max_returned, int use_th, double near_dup_th,
+                          int64_t* d_out_ids, double* d_out_dists, int32_t* d_out_src, int32_t* d_n_kept, void* stream);
+
 /* Exact k nearest neighbours (csrc/lopq_eval.hip): the ground truth of lopq.eval (lopq/lopq/eval.py:7-38: scipy's cdist + argmin /
  * argsort per row).  data [m2][d] and q [m1][d], each float32 or float64 (mixed allowed: the reference promotes both to float64).
  * dist = sqrt(s), s the float64 chain s = s + (x[i] - y[i])^2 for i ascending, every operation rounded on its own -- scipy's value
