@@ -78,28 +78,6 @@ struct Scan3Shared {  // one per query handled by the workgroup
     int pad;
 };
 
-static __device__ __forceinline__ uint32_t lds_ld(const uint32_t* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-static __device__ __forceinline__ void lds_st(uint32_t* p, uint32_t v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-template <int NW>
-static __device__ __forceinline__ uint64_t block_bound3(const Scan3Shared* sh) {
-    uint64_t t = lds_ld(&sh->wt[0]);
-    uint64_t l = lds_ld(&sh->wl[0]);
-#pragma unroll
-    for (int i = 1; i < NW; ++i) {
-        const uint64_t a = lds_ld(&sh->wt[i]), b = lds_ld(&sh->wl[i]);
-        t = a > t ? a : t;
-        l = b < l ? b : l;
-    }
-    const uint64_t e = lds_ld(&sh->ext);
-    l = e < l ? e : l;
-    return t < l ? t : l;
-}
-
 struct QScale { double inv_up, ub; };  // a query's scales (Scan3Shared), read where a compaction needs them
 static __device__ __forceinline__ QScale load_scale(const Scan3Shared* sh) {
     QScale q;
@@ -135,88 +113,43 @@ __device__ __forceinline__ int wave_compact3(uint32_t* rk, int cnt, int L, int L
         mn = (keep[r] && s[r] < mn) ? s[r] : mn;
         mx = (keep[r] && s[r] > mx) ? s[r] : mx;
     }
-    wave_minmax_step<1>(mn, mx); wave_minmax_step<2>(mn, mx); wave_minmax_step<4>(mn, mx);
-    wave_minmax_step<8>(mn, mx); wave_minmax_step<16>(mn, mx); wave_minmax_step<32>(mn, mx);
-    mn = (uint32_t)__builtin_amdgcn_readfirstlane((int)mn);
-    mx = (uint32_t)__builtin_amdgcn_readfirstlane((int)mx);
-    const uint64_t INF64 = 0x7ff0000000000000ull;
+    wave_minmax_all(mn, mx);
     // (1) v2 with #{s <= v2} in [Lw, Lw + W2] -> this wave's share of the block bound
+    // (the bracket is empty when the wave holds fewer than Lw entries: no probe, no bound)
     const int W2 = Lw >= 16 ? (Lw >> 3) : 1;
-    uint32_t lo2 = mn, v2 = mx;
-    while (cnt >= Lw && lo2 < v2) {  // wave-uniform
-        const uint32_t p = lo2 + ((v2 - lo2) >> 1);
-        int c = 0;
-#pragma unroll
-        for (int r = 0; r < NR; ++r) c += __popcll(__ballot(keep[r] && s[r] <= p));
-        if (c >= Lw) {
-            v2 = p;
-            if (c <= Lw + W2) break;
-        } else {
-            lo2 = p + 1;
-        }
-    }
-    const uint64_t boundW = cnt >= Lw ? val_to_bound(v2, M, qs.ub) : INF64;
+    const uint32_t v2 = wave_bisect_window<NR>(keep, s, cnt >= Lw ? mn : mx, mx, Lw, W2);
+    const uint64_t boundW = cnt >= Lw ? val_to_bound(v2, M, qs.ub) : 0x7ff0000000000000ull;
     if (lane == 0) {
         if (boundW < lds_ld(&sh->wt[w])) lds_st(&sh->wt[w], boundW);
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    uint32_t thr = bound_to_thr(block_bound3<NW>(sh), qs.inv_up);
+    uint32_t thr = bound_to_thr(block_bound<NW>(sh), qs.inv_up);
     uint32_t cut = thr;
-    int c_thr = 0;
-#pragma unroll
-    for (int r = 0; r < NR; ++r) c_thr += __popcll(__ballot(keep[r] && s[r] <= cut));
     int W = cap - L;
     W = W > 24 ? 24 : (W < 0 ? 0 : W);
-    if (c_thr > L + W) {
+    if (wave_count_le<NR>(keep, s, cut) > L + W) {
         // (2) the block bound does not thin this wave out: cut to the wave's own top L.  v with #{s <= v} in [L, L+W],
         // or the L-th smallest sum when ties prevent that; everything up to v + M stays (an entry above that is
         // strictly worse, in exact arithmetic, than the L entries that do not exceed v).
-        uint32_t lo_ = mn, v = mx;
-        while (lo_ < v) {
-            const uint32_t p = lo_ + ((v - lo_) >> 1);
-            int c = 0;
-#pragma unroll
-            for (int r = 0; r < NR; ++r) c += __popcll(__ballot(keep[r] && s[r] <= p));
-            if (c >= L) {
-                v = p;
-                if (c <= L + W) break;
-            } else {
-                lo_ = p + 1;
-            }
-        }
+        const uint32_t v = wave_bisect_window<NR>(keep, s, mn, mx, L, W);
         const uint32_t vm = v + (uint32_t)M;
-        int c_keep = 0;
-#pragma unroll
-        for (int r = 0; r < NR; ++r) c_keep += __popcll(__ballot(keep[r] && s[r] <= vm));
-        if (c_keep > cap) return -1;  // a crowd of (nearly) equal sums, e.g. duplicate codes: resolve exactly
+        if (wave_count_le<NR>(keep, s, vm) > cap) return -1;  // a crowd of (nearly) equal sums, e.g. duplicate codes: resolve exactly
         const uint64_t boundL = val_to_bound(v, M, qs.ub);
         if (lane == 0) {
             if (boundL < lds_ld(&sh->wl[w])) lds_st(&sh->wl[w], boundL);
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        thr = bound_to_thr(block_bound3<NW>(sh), qs.inv_up);
+        thr = bound_to_thr(block_bound<NW>(sh), qs.inv_up);
         cut = vm < thr ? vm : thr;
     }
     if (lane == 0) {
         if (thr < lds_ld(&sh->thr)) lds_st(&sh->thr, thr);
     }
-    int ncnt = 0;
-#pragma unroll
-    for (int r = 0; r < NR; ++r) {
-        const bool kp = keep[r] && s[r] <= cut;
-        const unsigned long long m = __ballot(kp);
-        const int idx = ncnt + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
-        if (kp) rk[idx] = ent[r];
-        ncnt += __popcll(m);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    return ncnt;
+    return wave_stable_keep<NR>([&](int r) { return keep[r] && s[r] <= cut; }, [&](int r, int idx) { rk[idx] = ent[r]; });
 }
 
 // Exact compaction (crowds of equal sums): every entry is re-scored in float64 -- code from the index, table entries
-// from global memory summed left to right (search.py:173) -- the cut is exact on (dist, pos), ties by region order
-// (= position order: appends are in increasing position and the compactions are stable).  Survivors keep their
+// from global memory summed left to right (search.py:173) -- and cut by wave_exact_cut.  Survivors keep their
 // 16-bit sums.  Returns the new count (<= L).  dup_pos: a member of a tie group the cut went through (its later
 // copies lose against all L entries kept here), or 0xffffffff.
 template <int M, int NR, int NW>
@@ -224,7 +157,6 @@ __device__ __forceinline__ int wave_compact3_exact(uint32_t* rk, int cnt, int L,
                                                    const uint8_t* __restrict__ codes, int64_t start, int K,
                                                    const double* __restrict__ t0, const double* __restrict__ t1, uint32_t& dup_pos) {
     const int lane = threadIdx.x & 63;
-    const uint64_t INF64 = 0x7ff0000000000000ull;
     uint32_t hi[NR], lo[NR], ent[NR];
     bool keep[NR];
     uint32_t mn = 0xffffffffu, mx = 0u;
@@ -246,129 +178,37 @@ __device__ __forceinline__ int wave_compact3_exact(uint32_t* rk, int cnt, int L,
         mn = (keep[r] && hi[r] < mn) ? hi[r] : mn;
         mx = (keep[r] && hi[r] > mx) ? hi[r] : mx;
     }
-    wave_minmax_step<1>(mn, mx); wave_minmax_step<2>(mn, mx); wave_minmax_step<4>(mn, mx);
-    wave_minmax_step<8>(mn, mx); wave_minmax_step<16>(mn, mx); wave_minmax_step<32>(mn, mx);
-    mn = (uint32_t)__builtin_amdgcn_readfirstlane((int)mn);
-    mx = (uint32_t)__builtin_amdgcn_readfirstlane((int)mx);
-    uint32_t vhiL = mx;
-    uint64_t boundL = INF64;
-    if (cnt >= L) {  // cut to this wave's own exact top-L
-        const uint32_t vhi = wave_kth_bisect<NR>(hi, keep, mn, mx, L);
-        vhiL = vhi;
-        boundL = hi_to_bound(vhi);
-        int c_less = 0, g = 0;
-#pragma unroll
-        for (int r = 0; r < NR; ++r) {
-            c_less += __popcll(__ballot(keep[r] && hi[r] < vhi));
-            g += __popcll(__ballot(keep[r] && hi[r] == vhi));
-        }
-        int need = L - c_less;  // members of the group {hi == vhi} to keep, 1 <= need <= g
-        if (need >= g) {
-#pragma unroll
-            for (int r = 0; r < NR; ++r) keep[r] = keep[r] && hi[r] <= vhi;
-        } else {
-            uint32_t lo_first = 0;
-            bool found = false, uniform = true;
-#pragma unroll
-            for (int r = 0; r < NR; ++r) {
-                const bool in_g = keep[r] && hi[r] == vhi;
-                const unsigned long long m = __ballot(in_g);
-                if (!found && m) {
-                    lo_first = (uint32_t)__builtin_amdgcn_readlane((int)lo[r], __ffsll((long long)m) - 1);
-                    found = true;
-                }
-                if (found) uniform = uniform && (__ballot(in_g && lo[r] != lo_first) == 0ull);
-            }
-            uint32_t vlo = lo_first;
-            if (!uniform) {
-                uint32_t t2[NR];
-#pragma unroll
-                for (int r = 0; r < NR; ++r) t2[r] = (keep[r] && hi[r] == vhi) ? lo[r] : 0xffffffffu;
-                wave_bitonic_sort<NR>(t2);
-                vlo = wave_kth<NR>(t2, need - 1);
-#pragma unroll
-                for (int r = 0; r < NR; ++r) need -= __popcll(__ballot(keep[r] && hi[r] == vhi && lo[r] < vlo));
-            }
-            int seen = 0;
-#pragma unroll
-            for (int r = 0; r < NR; ++r) {
-                const bool tie = keep[r] && hi[r] == vhi && lo[r] == vlo;
-                const unsigned long long m = __ballot(tie);
-                const int rank = seen + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
-                keep[r] = keep[r] && (hi[r] < vhi || (hi[r] == vhi && (lo[r] < vlo || (tie && rank < need))));
-                if (seen == 0 && m) dup_pos = (uint32_t)__builtin_amdgcn_readlane((int)(ent[r] & 0xffffu), __ffsll((long long)m) - 1);
-                seen += __popcll(m);
-            }
-        }
-    }
-    const uint64_t boundW = (cnt >= Lw) ? hi_to_bound(wave_kth_bisect<NR>(hi, keep, mn, vhiL, Lw)) : INF64;
+    wave_minmax_all(mn, mx);
+    uint32_t vhiL;
+    uint64_t boundL;
+    wave_exact_cut<NR>(hi, lo, keep, [&](int r) { return ent[r] & 0xffffu; }, mn, mx, cnt, L, vhiL, boundL, dup_pos);
+    const uint64_t boundW = (cnt >= Lw) ? hi_to_bound(wave_kth_bisect<NR>(hi, keep, mn, vhiL, Lw)) : 0x7ff0000000000000ull;
     if (lane == 0) {
         if (boundW < lds_ld(&sh->wt[w])) lds_st(&sh->wt[w], boundW);
         if (boundL < lds_ld(&sh->wl[w])) lds_st(&sh->wl[w], boundL);
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    const uint64_t bound = block_bound3<NW>(sh);
+    const uint64_t bound = block_bound<NW>(sh);
     if (lane == 0) {
         const uint32_t thr = bound_to_thr(bound, qs.inv_up);
         if (thr < lds_ld(&sh->thr)) lds_st(&sh->thr, thr);
     }
-    int ncnt = 0;
-#pragma unroll
-    for (int r = 0; r < NR; ++r) {
-        const uint64_t k = ((uint64_t)hi[r] << 32) | lo[r];
-        const bool kp = keep[r] && (k <= bound);
-        const unsigned long long m = __ballot(kp);
-        const int idx = ncnt + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
-        if (kp) rk[idx] = ent[r];
-        ncnt += __popcll(m);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    return ncnt;
+    return wave_stable_keep<NR>([&](int r) { return keep[r] && (((uint64_t)hi[r] << 32) | lo[r]) <= bound; },
+                                [&](int r, int idx) { rk[idx] = ent[r]; });
 }
 
 // Drop entries above the block bound (hot loop's test).  Stable.
 template <int NR, int NW>
 __device__ __forceinline__ int wave_filter3(uint32_t* rk, int cnt, const QScale& qs, const Scan3Shared* sh) {
     const int lane = threadIdx.x & 63;
-    const uint32_t thr = bound_to_thr(block_bound3<NW>(sh), qs.inv_up);
+    const uint32_t thr = bound_to_thr(block_bound<NW>(sh), qs.inv_up);
     uint32_t k[NR];
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
         const int e = r * 64 + lane;
         k[r] = e < cnt ? rk[e] : 0xffffffffu;
     }
-    int ncnt = 0;
-#pragma unroll
-    for (int r = 0; r < NR; ++r) {
-        const bool kp = (r * 64 + lane < cnt) && ((k[r] >> 16) <= thr);
-        const unsigned long long m = __ballot(kp);
-        const int idx = ncnt + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
-        if (kp) rk[idx] = k[r];
-        ncnt += __popcll(m);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    return ncnt;
-}
-
-// one candidate's code words in this lane's rotated order (make_rot): D[t >> 2] holds the byte used at step t
-template <int M>
-__device__ __forceinline__ void rot_words(const CodeWords<M>& c, const RotConsts<M>& rc, uint32_t (&D)[(M + 3) / 4]) {
-    if constexpr (M == 4) {
-        D[0] = c.w[0];
-    } else if constexpr (M == 8) {
-        D[0] = rc.hsel ? c.w[1] : c.w[0];
-        D[1] = rc.hsel ? c.w[0] : c.w[1];
-    } else {
-        const bool b0 = rc.hsel & 1, b1 = rc.hsel & 2;
-        const uint32_t x01 = b0 ? c.w[1] : c.w[0], y01 = b0 ? c.w[0] : c.w[1];
-        const uint32_t x23 = b0 ? c.w[3] : c.w[2], y23 = b0 ? c.w[2] : c.w[3];
-        D[0] = b1 ? x23 : x01;
-        D[1] = b1 ? y23 : y01;
-        D[2] = b1 ? x01 : x23;
-        D[3] = b1 ? y01 : y23;
-    }
+    return wave_stable_keep<NR>([&](int r) { return (r * 64 + lane < cnt) && ((k[r] >> 16) <= thr); }, [&](int r, int idx) { rk[idx] = k[r]; });
 }
 
 // The pipeline unit of the hot loop: OCT table reads (ds_read_b64, four queries each) of one candidate -- steps
@@ -934,7 +774,7 @@ __device__ __forceinline__ void scan3_group(const WorkItem* __restrict__ items, 
         if constexpr (NW > 1) cnt[g] = wave_filter3<NR, NW>(rk, cnt[g], qsg, &sh[g]);  // one wave: its own cut was the block bound
         if (lane == 0) sh[g].wcnt[w] = cnt[g];
         if (tid == 0) {
-            const uint64_t b = block_bound3<NW>(&sh[g]);
+            const uint64_t b = block_bound<NW>(&sh[g]);
             if (b < sh[g].ext) atomicMin(&qbound[items[item_idx[g]].q], (unsigned long long)b);
         }
     }
@@ -1948,9 +1788,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                                     mn = (val[r] && s < mn) ? s : mn;
                                     mx = (val[r] && s > mx) ? s : mx;
                                 }
-                                wave_minmax_step<1>(mn, mx); wave_minmax_step<2>(mn, mx); wave_minmax_step<4>(mn, mx);
-                                wave_minmax_step<8>(mn, mx); wave_minmax_step<16>(mn, mx); wave_minmax_step<32>(mn, mx);
-                                uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)mn), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)mx);
+                                wave_minmax_all(mn, mx);
+                                uint32_t lo = mn, hi = mx;
                                 // hi always has >= L sums at or below it (it starts at the largest collected sum and tot >= L); the search stops
                                 // as soon as that count is within L + 16: any such value serves as v (a step costs NRV ballots, the exact L-th
                                 // smallest ~12 steps, this ~5; the merge cuts the few extra survivors before re-scoring)
@@ -2420,10 +2259,7 @@ __global__ __launch_bounds__(256) void k_scan5_tau(const uint32_t* __restrict__ 
         int k = (int)(((int64_t)P * ns + ncand - 1) / ncand);
         k = k < 4 ? 4 : k;
         if (k <= fin && k <= B / 2) {
-            wave_minmax_step<1>(lo, hi); wave_minmax_step<2>(lo, hi); wave_minmax_step<4>(lo, hi);
-            wave_minmax_step<8>(lo, hi); wave_minmax_step<16>(lo, hi); wave_minmax_step<32>(lo, hi);
-            lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)lo);
-            hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)hi);
+            wave_minmax_all(lo, hi);
             t = __uint_as_float(wave_kth_bisect<PER>(v, ok, lo, hi, k));
         }
     }

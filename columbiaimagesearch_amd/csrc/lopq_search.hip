@@ -573,20 +573,6 @@ struct ScanShared {  // one per query handled by the workgroup
 
 
 static __device__ __forceinline__ float block_bound_f32(const ScanShared* sh) { return lds_ld(&sh->bound_f); }
-template <int NW>
-static __device__ __forceinline__ uint64_t block_bound_u64(const ScanShared* sh) {
-    uint64_t t = lds_ld(&sh->wt[0]);
-    uint64_t l = lds_ld(&sh->wl[0]);
-#pragma unroll
-    for (int i = 1; i < NW; ++i) {
-        const uint64_t a = lds_ld(&sh->wt[i]), b = lds_ld(&sh->wl[i]);
-        t = a > t ? a : t;
-        l = b < l ? b : l;
-    }
-    const uint64_t e = lds_ld(&sh->ext);
-    l = e < l ? e : l;
-    return t < l ? t : l;
-}
 
 // exact float64 distance of one candidate: table entries from global memory, summed left to right
 static __device__ __forceinline__ double adc64_global(const uint8_t* __restrict__ codes, int64_t p, int M, int K,
@@ -629,86 +615,41 @@ __device__ __forceinline__ int wave_compact_approx(uint64_t* rk, int cnt, int L,
         mn = (keep[r] && hi[r] < mn) ? hi[r] : mn;
         mx = (keep[r] && hi[r] > mx) ? hi[r] : mx;
     }
-    wave_minmax_step<1>(mn, mx); wave_minmax_step<2>(mn, mx); wave_minmax_step<4>(mn, mx);
-    wave_minmax_step<8>(mn, mx); wave_minmax_step<16>(mn, mx); wave_minmax_step<32>(mn, mx);
-    mn = (uint32_t)__builtin_amdgcn_readfirstlane((int)mn);
-    mx = (uint32_t)__builtin_amdgcn_readfirstlane((int)mx);
-    const uint64_t INF64 = 0x7ff0000000000000ull;
+    wave_minmax_all(mn, mx);
     // (1) v2 with #{d32 <= v2} in [Lw, Lw + W2] -> this wave's share of the block bound
+    // (the bracket is empty when the wave holds fewer than Lw entries: no probe, no bound)
     const int W2 = Lw >= 16 ? (Lw >> 3) : 1;
-    uint32_t lo2 = mn, v2 = mx;
-    while (cnt >= Lw && lo2 < v2) {  // wave-uniform
-        const uint32_t p = lo2 + ((v2 - lo2) >> 1);
-        int c = 0;
-#pragma unroll
-        for (int r = 0; r < NR; ++r) c += __popcll(__ballot(keep[r] && hi[r] <= p));
-        if (c >= Lw) {
-            v2 = p;
-            if (c <= Lw + W2) break;
-        } else {
-            lo2 = p + 1;
-        }
-    }
-    const uint64_t boundW = cnt >= Lw ? (uint64_t)__double_as_longlong((double)__uint_as_float(v2) * infl) : INF64;
+    const uint32_t v2 = wave_bisect_window<NR>(keep, hi, cnt >= Lw ? mn : mx, mx, Lw, W2);
+    const uint64_t boundW = cnt >= Lw ? (uint64_t)__double_as_longlong((double)__uint_as_float(v2) * infl) : 0x7ff0000000000000ull;
     if (lane == 0) {
         if (boundW < lds_ld(&sh->wt[w])) lds_st(&sh->wt[w], boundW);
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    uint64_t bound = block_bound_u64<NW>(sh);
-    float bf = __double2float_ru(__longlong_as_double((long long)bound));
+    float bf = __double2float_ru(__longlong_as_double((long long)block_bound<NW>(sh)));
     uint32_t cut = __float_as_uint(bf * margin);  // the hot loop's test
-    int c_thr = 0;
-#pragma unroll
-    for (int r = 0; r < NR; ++r) c_thr += __popcll(__ballot(keep[r] && hi[r] <= cut));
     int W = cap - L;
     W = W > 24 ? 24 : (W < 0 ? 0 : W);
-    if (c_thr > L + W) {
+    if (wave_count_le<NR>(keep, hi, cut) > L + W) {
         // (2) the block bound does not thin this wave out (the other waves lag, the good candidates sit in this
         // wave's stripes, or many distances are equal): cut to the wave's own top L.
         // v with #{d32 <= v} in [L, L+W], or the exact L-th smallest when ties prevent that
-        uint32_t lo_ = mn, v = mx;
-        while (lo_ < v) {
-            const uint32_t p = lo_ + ((v - lo_) >> 1);
-            int c = 0;
-#pragma unroll
-            for (int r = 0; r < NR; ++r) c += __popcll(__ballot(keep[r] && hi[r] <= p));
-            if (c >= L) {
-                v = p;
-                if (c <= L + W) break;
-            } else {
-                lo_ = p + 1;
-            }
-        }
+        const uint32_t v = wave_bisect_window<NR>(keep, hi, mn, mx, L, W);
         const uint32_t vm = __float_as_uint(__double2float_ru((double)__uint_as_float(v) * (double)margin));
-        int c_keep = 0;
-#pragma unroll
-        for (int r = 0; r < NR; ++r) c_keep += __popcll(__ballot(keep[r] && hi[r] <= vm));
-        if (c_keep > cap) return -1;  // a crowd of (nearly) equal distances, e.g. duplicate codes: resolve exactly
+        if (wave_count_le<NR>(keep, hi, vm) > cap) return -1;  // a crowd of (nearly) equal distances, e.g. duplicate codes: resolve exactly
         const uint64_t boundL = (uint64_t)__double_as_longlong((double)__uint_as_float(v) * infl);
         if (lane == 0) {
             if (boundL < lds_ld(&sh->wl[w])) lds_st(&sh->wl[w], boundL);
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        bound = block_bound_u64<NW>(sh);
-        bf = __double2float_ru(__longlong_as_double((long long)bound));
+        bf = __double2float_ru(__longlong_as_double((long long)block_bound<NW>(sh)));
         const uint32_t thr = __float_as_uint(bf * margin);
         cut = vm < thr ? vm : thr;
     }
     if (lane == 0) {
         if (bf < lds_ld(&sh->bound_f)) lds_st(&sh->bound_f, bf);
     }
-    int ncnt = 0;
-#pragma unroll
-    for (int r = 0; r < NR; ++r) {
-        const bool kp = keep[r] && hi[r] <= cut;
-        const unsigned long long m = __ballot(kp);
-        const int idx = ncnt + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
-        if (kp) rk[idx] = ((uint64_t)hi[r] << 32) | pp[r];
-        ncnt += __popcll(m);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    return ncnt;
+    return wave_stable_keep<NR>([&](int r) { return keep[r] && hi[r] <= cut; },
+                                [&](int r, int idx) { rk[idx] = ((uint64_t)hi[r] << 32) | pp[r]; });
 }
 
 // FINAL: leaves exact float64 keys in rk and positions in rp (the output format); otherwise the survivors go back
@@ -719,7 +660,6 @@ __device__ __forceinline__ int wave_compact_exact(uint64_t* rk, uint32_t* rp, in
                                                   int K, const double* __restrict__ t0, const double* __restrict__ t1,
                                                   uint32_t& dup_pos) {
     const int lane = threadIdx.x & 63;
-    const uint64_t INF64 = 0x7ff0000000000000ull;
     CIS_CTR(1, 1);
     uint32_t hi[NR], lo[NR], pp[NR];
     bool keep[NR];
@@ -745,104 +685,62 @@ __device__ __forceinline__ int wave_compact_exact(uint64_t* rk, uint32_t* rp, in
             mx = (keep[r] && hi[r] > mx) ? hi[r] : mx;
         }
     }
-    wave_minmax_step<1>(mn, mx); wave_minmax_step<2>(mn, mx); wave_minmax_step<4>(mn, mx);
-    wave_minmax_step<8>(mn, mx); wave_minmax_step<16>(mn, mx); wave_minmax_step<32>(mn, mx);
-    mn = (uint32_t)__builtin_amdgcn_readfirstlane((int)mn);
-    mx = (uint32_t)__builtin_amdgcn_readfirstlane((int)mx);
-    uint32_t vhiL = mx;
-    uint64_t boundL = INF64;
-    if (cnt >= L) {  // cut to this wave's own exact top-L
-        const uint32_t vhi = wave_kth_bisect<NR>(hi, keep, mn, mx, L);
-        vhiL = vhi;
-        boundL = hi_to_bound(vhi);
-        int c_less = 0, g = 0;
-#pragma unroll
-        for (int r = 0; r < NR; ++r) {
-            c_less += __popcll(__ballot(keep[r] && hi[r] < vhi));
-            g += __popcll(__ballot(keep[r] && hi[r] == vhi));
-        }
-        int need = L - c_less;  // members of the group {hi == vhi} to keep, 1 <= need <= g
-        if (need >= g) {
-#pragma unroll
-            for (int r = 0; r < NR; ++r) keep[r] = keep[r] && hi[r] <= vhi;
-        } else {
-            // low word of the first group member in region order; are all members equal to it?
-            uint32_t lo_first = 0;
-            bool found = false, uniform = true;
-#pragma unroll
-            for (int r = 0; r < NR; ++r) {
-                const bool in_g = keep[r] && hi[r] == vhi;
-                const unsigned long long m = __ballot(in_g);
-                if (!found && m) {
-                    lo_first = (uint32_t)__builtin_amdgcn_readlane((int)lo[r], __ffsll((long long)m) - 1);
-                    found = true;
-                }
-                if (found) uniform = uniform && (__ballot(in_g && lo[r] != lo_first) == 0ull);
-            }
-            uint32_t vlo = lo_first;
-            if (!uniform) {
-                uint32_t t2[NR];
-#pragma unroll
-                for (int r = 0; r < NR; ++r) t2[r] = (keep[r] && hi[r] == vhi) ? lo[r] : 0xffffffffu;
-                wave_bitonic_sort<NR>(t2);
-                vlo = wave_kth<NR>(t2, need - 1);
-#pragma unroll
-                for (int r = 0; r < NR; ++r) need -= __popcll(__ballot(keep[r] && hi[r] == vhi && lo[r] < vlo));
-            }
-            // exact ties (hi, lo) == (vhi, vlo): the first `need` in region order have the smallest positions
-            int seen = 0;
-#pragma unroll
-            for (int r = 0; r < NR; ++r) {
-                const bool tie = keep[r] && hi[r] == vhi && lo[r] == vlo;
-                const unsigned long long m = __ballot(tie);
-                const int rank = seen + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
-                keep[r] = keep[r] && (hi[r] < vhi || (hi[r] == vhi && (lo[r] < vlo || (tie && rank < need))));
-                // The cut fell inside a group of exactly equal distances.  Remember one member: every LATER
-                // candidate with the same code has the same distance and a larger position, so it loses
-                // against all L entries kept here and the hot loop may skip it (duplicate codes are common).
-                if (seen == 0 && m) dup_pos = (uint32_t)__builtin_amdgcn_readlane((int)pp[r], __ffsll((long long)m) - 1);
-                seen += __popcll(m);
-            }
-        }
-    }
-    const uint64_t boundW = (cnt >= Lw) ? hi_to_bound(wave_kth_bisect<NR>(hi, keep, mn, vhiL, Lw)) : INF64;
+    wave_minmax_all(mn, mx);
+    uint32_t vhiL;
+    uint64_t boundL;
+    wave_exact_cut<NR>(hi, lo, keep, [&](int r) { return pp[r]; }, mn, mx, cnt, L, vhiL, boundL, dup_pos);
+    const uint64_t boundW = (cnt >= Lw) ? hi_to_bound(wave_kth_bisect<NR>(hi, keep, mn, vhiL, Lw)) : 0x7ff0000000000000ull;
     if (lane == 0) {
         if (boundW < lds_ld(&sh->wt[w])) lds_st(&sh->wt[w], boundW);
         if (boundL < lds_ld(&sh->wl[w])) lds_st(&sh->wl[w], boundL);
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    const uint64_t bound = block_bound_u64<NW>(sh);
+    const uint64_t bound = block_bound<NW>(sh);
     if (lane == 0) {
         const float bf = __double2float_ru(__longlong_as_double((long long)bound));
         if (bf < lds_ld(&sh->bound_f)) lds_st(&sh->bound_f, bf);
     }
-    int ncnt = 0;
-#pragma unroll
-    for (int r = 0; r < NR; ++r) {
-        const uint64_t k = ((uint64_t)hi[r] << 32) | lo[r];
-        const bool kp = keep[r] && (k <= bound);
-        const unsigned long long m = __ballot(kp);
-        const int idx = ncnt + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
-        if (kp) {
+    if constexpr (NR < 16) {
+        return wave_stable_keep<NR>([&](int r) { return keep[r] && (((uint64_t)hi[r] << 32) | lo[r]) <= bound; }, [&](int r, int idx) {
+            const uint64_t k = ((uint64_t)hi[r] << 32) | lo[r];
             if constexpr (FINAL) {
                 rk[idx] = k;
                 rp[idx] = pp[r];
             } else {
                 rk[idx] = ((uint64_t)__float_as_uint(__double2float_ru(__longlong_as_double((long long)k))) << 32) | pp[r];
             }
+        });
+    } else {
+        // wave_stable_keep spelled out: through the helper the NR = 16 instantiations spill three times the scalars and the 8192-query
+        // batch at limit 500 takes 3.03 ms instead of 1.80 (profiles/scan_cut_ab.txt)
+        int ncnt = 0;
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+            const uint64_t k = ((uint64_t)hi[r] << 32) | lo[r];
+            const bool kp = keep[r] && (k <= bound);
+            const unsigned long long m = __ballot(kp);
+            const int idx = ncnt + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
+            if (kp) {
+                if constexpr (FINAL) {
+                    rk[idx] = k;
+                    rp[idx] = pp[r];
+                } else {
+                    rk[idx] = ((uint64_t)__float_as_uint(__double2float_ru(__longlong_as_double((long long)k))) << 32) | pp[r];
+                }
+            }
+            ncnt += __popcll(m);
         }
-        ncnt += __popcll(m);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        return ncnt;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    return ncnt;
 }
 
 // Drop (float32 distance, position) entries above the block bound, with the hot loop's test.  Stable.
 template <int NR, int NW>
 __device__ __forceinline__ int wave_filter_approx(uint64_t* rk, int cnt, float margin, const ScanShared* sh) {
     const int lane = threadIdx.x & 63;
-    const uint64_t bound = block_bound_u64<NW>(sh);
+    const uint64_t bound = block_bound<NW>(sh);
     const uint32_t thr = __float_as_uint(__double2float_ru(__longlong_as_double((long long)bound)) * margin);
     uint64_t k[NR];
 #pragma unroll
@@ -850,85 +748,10 @@ __device__ __forceinline__ int wave_filter_approx(uint64_t* rk, int cnt, float m
         const int e = r * 64 + lane;
         k[r] = e < cnt ? rk[e] : ~0ull;
     }
-    int ncnt = 0;
-#pragma unroll
-    for (int r = 0; r < NR; ++r) {
-        const bool kp = (r * 64 + lane < cnt) && ((uint32_t)(k[r] >> 32) <= thr);
-        const unsigned long long m = __ballot(kp);
-        const int idx = ncnt + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
-        if (kp) rk[idx] = k[r];
-        ncnt += __popcll(m);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    return ncnt;
+    return wave_stable_keep<NR>([&](int r) { return (r * 64 + lane < cnt) && ((uint32_t)(k[r] >> 32) <= thr); },
+                                [&](int r, int idx) { rk[idx] = k[r]; });
 }
 
-// Drop entries above the (final) block bound; entries already carry exact keys.  Stable.
-template <int NR, int NW>
-__device__ __forceinline__ int wave_filter(uint64_t* rk, uint32_t* rp, int cnt, const ScanShared* sh) {
-    const int lane = threadIdx.x & 63;
-    const uint64_t bound = block_bound_u64<NW>(sh);
-    uint64_t k[NR];
-    uint32_t pp[NR];
-#pragma unroll
-    for (int r = 0; r < NR; ++r) {
-        const int e = r * 64 + lane;
-        k[r] = e < cnt ? rk[e] : ~0ull;
-        pp[r] = e < cnt ? rp[e] : 0u;
-    }
-    int ncnt = 0;
-#pragma unroll
-    for (int r = 0; r < NR; ++r) {
-        const bool kp = (r * 64 + lane < cnt) && (k[r] <= bound);
-        const unsigned long long m = __ballot(kp);
-        const int idx = ncnt + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
-        if (kp) { rk[idx] = k[r]; rp[idx] = pp[r]; }
-        ncnt += __popcll(m);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    return ncnt;
-}
-
-
-// float32 ADC sum of one candidate with the lane-rotated table order (see header comment)
-template <int M>
-__device__ __forceinline__ float adc32(const CodeWords<M>& c, const char* __restrict__ tab, const RotConsts<M>& rc) {
-    constexpr int SH = (M == 4) ? 4 : (M == 8 ? 5 : 6);  // log2(M * 4 bytes)
-    uint32_t D[(M + 3) / 4];
-    if constexpr (M == 4) {
-        D[0] = c.w[0];
-    } else if constexpr (M == 8) {
-        D[0] = rc.hsel ? c.w[1] : c.w[0];
-        D[1] = rc.hsel ? c.w[0] : c.w[1];
-    } else {
-        const bool b0 = rc.hsel & 1, b1 = rc.hsel & 2;
-        const uint32_t x01 = b0 ? c.w[1] : c.w[0], y01 = b0 ? c.w[0] : c.w[1];
-        const uint32_t x23 = b0 ? c.w[3] : c.w[2], y23 = b0 ? c.w[2] : c.w[3];
-        D[0] = b1 ? x23 : x01;
-        D[1] = b1 ? y23 : y01;
-        D[2] = b1 ? x01 : x23;
-        D[3] = b1 ? y01 : y23;
-    }
-    float f[M];
-#pragma unroll
-    for (int t = 0; t < M; ++t) {
-        const uint32_t k = __builtin_amdgcn_ubfe(D[t >> 2], rc.sh[t & 3], 8);
-        const uint32_t addr = (k << SH) | rc.cj[t];
-        f[t] = *reinterpret_cast<const float*>(tab + addr);
-    }
-    float acc;
-    if constexpr (M == 4) {
-        acc = (f[0] + f[1]) + (f[2] + f[3]);
-    } else if constexpr (M == 8) {
-        acc = ((f[0] + f[1]) + (f[2] + f[3])) + ((f[4] + f[5]) + (f[6] + f[7]));
-    } else {
-        acc = (((f[0] + f[1]) + (f[2] + f[3])) + ((f[4] + f[5]) + (f[6] + f[7]))) +
-              (((f[8] + f[9]) + (f[10] + f[11])) + ((f[12] + f[13]) + (f[14] + f[15])));
-    }
-    return acc;
-}
 
 // float32 ADC sums of one candidate for G queries at once: the LDS table interleaves the queries,
 // tab[k][j][g], so ONE ds_read (b32 for G=1, b64 for G=2) serves all G queries of the workgroup.
@@ -937,20 +760,7 @@ __device__ __forceinline__ void adc32g(const CodeWords<M>& c, const char* __rest
                                        float (&out)[G]) {
     constexpr int SH = ((M == 4) ? 4 : (M == 8 ? 5 : 6)) + (G == 2 ? 1 : 0);  // log2(M * G * 4 bytes)
     uint32_t D[(M + 3) / 4];
-    if constexpr (M == 4) {
-        D[0] = c.w[0];
-    } else if constexpr (M == 8) {
-        D[0] = rc.hsel ? c.w[1] : c.w[0];
-        D[1] = rc.hsel ? c.w[0] : c.w[1];
-    } else {
-        const bool b0 = rc.hsel & 1, b1 = rc.hsel & 2;
-        const uint32_t x01 = b0 ? c.w[1] : c.w[0], y01 = b0 ? c.w[0] : c.w[1];
-        const uint32_t x23 = b0 ? c.w[3] : c.w[2], y23 = b0 ? c.w[2] : c.w[3];
-        D[0] = b1 ? x23 : x01;
-        D[1] = b1 ? y23 : y01;
-        D[2] = b1 ? x01 : x23;
-        D[3] = b1 ? y01 : y23;
-    }
+    rot_words<M>(c, rc, D);
     if constexpr (G == 1) {
         float f[M];
 #pragma unroll
@@ -995,20 +805,7 @@ __device__ __forceinline__ void adc32_issue(const CodeWords<M>& c, const char* _
     constexpr int LG = (G == 2) ? 1 : 2;
     constexpr int SH = ((M == 4) ? 4 : (M == 8 ? 5 : 6)) + LG;  // log2(M * G * 4 bytes)
     uint32_t D[(M + 3) / 4];
-    if constexpr (M == 4) {
-        D[0] = c.w[0];
-    } else if constexpr (M == 8) {
-        D[0] = rc.hsel ? c.w[1] : c.w[0];
-        D[1] = rc.hsel ? c.w[0] : c.w[1];
-    } else {
-        const bool b0 = rc.hsel & 1, b1 = rc.hsel & 2;
-        const uint32_t x01 = b0 ? c.w[1] : c.w[0], y01 = b0 ? c.w[0] : c.w[1];
-        const uint32_t x23 = b0 ? c.w[3] : c.w[2], y23 = b0 ? c.w[2] : c.w[3];
-        D[0] = b1 ? x23 : x01;
-        D[1] = b1 ? y23 : y01;
-        D[2] = b1 ? x01 : x23;
-        D[3] = b1 ? y01 : y23;
-    }
+    rot_words<M>(c, rc, D);
 #pragma unroll
     for (int t = 0; t < M; ++t) {
         const uint32_t k = __builtin_amdgcn_ubfe(D[t >> 2], rc.sh[t & 3], 8);
@@ -1327,7 +1124,7 @@ __device__ __forceinline__ void scan2_group(const WorkItem* __restrict__ items_a
         if (lane == 0) sh[g].wcnt[w] = cnt[g];
 #ifndef CIS_SCAN_NO_QBOUND
         if (tid == 0) {
-            const uint64_t b = block_bound_u64<NW>(&sh[g]);
+            const uint64_t b = block_bound<NW>(&sh[g]);
             if (b < sh[g].ext) atomicMin(&qbound[it_q[g]], (unsigned long long)b);
         }
 #endif
@@ -1571,10 +1368,7 @@ void k_merge_survivors(const uint64_t* __restrict__ surv /* [n_items][S] */,
             uint32_t thr = 0xffffffffu;
             float vub = __int_as_float(0x7f800000);  // scan3 survivors: a distance that `limit` of them do not exceed
             if (n_total > limit) {
-                wave_minmax_step<1>(mn, mx); wave_minmax_step<2>(mn, mx); wave_minmax_step<4>(mn, mx);
-                wave_minmax_step<8>(mn, mx); wave_minmax_step<16>(mn, mx); wave_minmax_step<32>(mn, mx);
-                mn = (uint32_t)__builtin_amdgcn_readfirstlane((int)mn);
-                mx = (uint32_t)__builtin_amdgcn_readfirstlane((int)mx);
+                wave_minmax_all(mn, mx);
                 const uint32_t v = wave_kth_bisect<NE>(hi, valid, mn, mx, limit);
                 if (item_slack) {
                     vub = __uint_as_float(v);
@@ -1805,11 +1599,108 @@ __device__ int selftest_sort(uint32_t seed) {
     return bad;
 }
 
+static __device__ uint32_t selftest_hash(uint32_t x) {
+    x *= 2654435761u; x ^= x >> 15; x *= 2246822519u; x ^= x >> 13;
+    return x;
+}
+
+// The selection primitives of scan_common.h: one wave against a serial reference that lane 0 computes from the same keys in LDS.
+// Entry e = r * 64 + lane, as in a hit region; its candidate position is 7 * e + 3.  Case c picks the keys and the cut:
+//   0  cnt < L: nothing cut, no bound; the bisection behind its callers' guard, and at its edge n == cnt
+//   1  cnt == L                                       2  distinct hi: the cut falls between groups; W = 0
+//   3  three values of hi, fifty of lo: the cut goes through a group of equal hi with different lo (sort of the low words), the
+//      counts of the bisection jump over the window
+//   4  three values of hi, lo follows hi: the cut goes through a group of equal keys (first `need` in region order, dup_pos)
+//   5  two values of hi, distinct lo                  6  all keys equal                  7  a thousand values of hi, random lo
+template <int NR>
+__device__ int selftest_cut(int c, uint32_t seed) {
+    __shared__ uint32_t s_hi[NR * 64], s_lo[NR * 64], s_out[NR * 64];
+    const int lane = threadIdx.x & 63;
+    const int cnt = NR * 64 - 8 - (int)seed * 5 - c;  // never a multiple of 64: the last row is partial
+    const int L = c == 0 ? cnt + 3 : (c == 1 ? cnt : (c == 7 ? cnt / 3 : (c == 2 ? cnt * 2 / 3 : cnt / 2 - (int)seed)));
+    uint32_t hi[NR], lo[NR], mn = 0xffffffffu, mx = 0u;
+    bool keep[NR];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+        const uint32_t e = (uint32_t)(r * 64 + lane), h = selftest_hash(seed * 4099u + e), h2 = selftest_hash(h + 1u);
+        const uint32_t distinct = (e * 167u + seed) % 1021u;
+        keep[r] = (int)e < cnt;
+        hi[r] = c == 2 ? distinct : (c == 3 || c == 4 ? h % 3u : (c == 5 ? h % 2u : (c == 6 ? 5u : h % 1000u)));
+        lo[r] = c == 3 ? h2 % 50u : (c == 4 ? hi[r] * 7u + 1u : (c == 5 ? distinct : (c == 6 ? 9u : h2)));
+        s_hi[e] = hi[r]; s_lo[e] = lo[r];
+        mn = (keep[r] && hi[r] < mn) ? hi[r] : mn;
+        mx = (keep[r] && hi[r] > mx) ? hi[r] : mx;
+    }
+    wave_minmax_all(mn, mx);
+    // wave_bisect_window / wave_count_le on the hi words
+    const int n = L <= cnt ? L : cnt, W = c == 0 ? 3 : (c == 3 || c == 4 ? 2 : (c == 7 ? n >> 3 : 0));
+    const uint32_t v = wave_bisect_window<NR>(keep, hi, mn, mx, n, W);
+    const uint32_t v_guard = wave_bisect_window<NR>(keep, hi, cnt >= L ? mn : mx, mx, L, W);  // as wave_compact_approx calls it
+    const int c_v = wave_count_le<NR>(keep, hi, v);
+    // wave_stable_keep: nothing, everything, or about half of the entries
+    const auto pred = [&](uint32_t key) { return (c & 3) == 0 ? false : ((c & 3) == 1 ? true : ((key >> 3) & 1u) != 0u); };
+    const int n_kept = wave_stable_keep<NR>([&](int r) { return keep[r] && pred(lo[r]); }, [&](int r, int idx) { s_out[idx] = lo[r]; });
+    wave_lds_sync();
+    int bad = 0;
+    if (lane == 0) {
+        int c_ref = 0, j = 0;
+        uint32_t nth = 0xffffffffu, k_min = 0xffffffffu, k_max = 0u;
+        for (int e = 0; e < cnt; ++e) {
+            int c_e = 0;
+            for (int f = 0; f < cnt; ++f) c_e += s_hi[f] <= s_hi[e];
+            if (c_e >= n && s_hi[e] < nth) nth = s_hi[e];  // the n-th smallest key
+            c_ref += s_hi[e] <= v;
+            k_min = s_hi[e] < k_min ? s_hi[e] : k_min;
+            k_max = s_hi[e] > k_max ? s_hi[e] : k_max;
+            if (pred(s_lo[e])) { bad += s_out[j] != s_lo[e]; ++j; }
+        }
+        bad += (mn != k_min) + (mx != k_max) + (c_v != c_ref) + (c_ref < n) + (c_ref > n + W && v != nth) + (j != n_kept);
+        bad += (c == 3 || c == 6) && v != nth;      // ties: no value has its count inside the window
+        bad += (cnt >= L ? v_guard != v : v_guard != mx);
+    }
+    wave_lds_sync();
+    // wave_exact_cut
+    uint32_t vhiL = 0u, dup_pos = 0xffffffffu;
+    uint64_t boundL = 0ull;
+    wave_exact_cut<NR>(hi, lo, keep, [&](int r) { return 7u * (uint32_t)(r * 64 + lane) + 3u; }, mn, mx, cnt, L, vhiL, boundL, dup_pos);
+#pragma unroll
+    for (int r = 0; r < NR; ++r) s_out[r * 64 + lane] = keep[r] ? 1u : 0u;
+    wave_lds_sync();
+    if (lane == 0) {
+        // the reference's stable sorted(): entry e survives when fewer than L entries come before it by (hi, lo, e)
+        int kth = -1;
+        for (int e = 0; e < NR * 64; ++e) {
+            int before = 0;
+            for (int f = 0; f < cnt; ++f)
+                before += s_hi[f] < s_hi[e] || (s_hi[f] == s_hi[e] && (s_lo[f] < s_lo[e] || (s_lo[f] == s_lo[e] && f < e)));
+            bad += s_out[e] != ((e < cnt && before < L) ? 1u : 0u);
+            if (e < cnt && before == L - 1) kth = e;
+        }
+        uint32_t dup_ref = 0xffffffffu;
+        if (kth >= 0) {
+            int c_less = 0, g = 0, first = -1;
+            for (int e = cnt - 1; e >= 0; --e) {
+                c_less += s_hi[e] < s_hi[kth];
+                g += s_hi[e] == s_hi[kth];
+                if (s_hi[e] == s_hi[kth] && s_lo[e] == s_lo[kth]) first = e;
+            }
+            if (L - c_less < g) dup_ref = 7u * (uint32_t)first + 3u;  // the cut went through the group of the L-th entry's hi word
+        }
+        bad += (kth >= 0) != (cnt >= L);
+        bad += vhiL != (kth >= 0 ? s_hi[kth] : mx);
+        bad += boundL != (kth >= 0 ? hi_to_bound(s_hi[kth]) : 0x7ff0000000000000ull);
+        bad += dup_pos != dup_ref;
+        bad += (c == 4 || c == 6) && dup_ref == 0xffffffffu;  // these cases are built to reach the tie rule
+    }
+    return bad;
+}
+
 __global__ void k_selftest(int* __restrict__ errors) {
     const uint32_t v = (uint32_t)threadIdx.x * 7919u + blockIdx.x * 104729u + 17u;
     int bad = selftest_xor<1>(v) + selftest_xor<2>(v) + selftest_xor<4>(v) + selftest_xor<8>(v) + selftest_xor<16>(v) +
               selftest_xor<32>(v);
     bad += selftest_sort<4>(blockIdx.x * 977u + 1u) + selftest_sort<8>(blockIdx.x * 31u + 5u);
+    bad += selftest_cut<4>(blockIdx.x & 7, blockIdx.x >> 3) + selftest_cut<8>(blockIdx.x & 7, blockIdx.x >> 3);
     if (bad) atomicAdd(errors, bad);
 }
 
@@ -1977,11 +1868,6 @@ static void launch_scan2(int M, const Scan2Geom& g, const ScanArgs& a) {  // (sc
 // ranking = the reference's stable sorted() over the retrieved list (search.py:210).
 int cis_seg_sort_u64(void* temp, size_t* temp_bytes, const uint64_t* keys_in, uint64_t* keys_out, const uint64_t* vals_in,
                      uint64_t* vals_out, int64_t n, int nseg, const int64_t* seg_begin, const int64_t* seg_end, hipStream_t st);
-
-__global__ void k_item_lens(const WorkItem* __restrict__ items, int64_t n, int64_t* __restrict__ lens) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) lens[i] = items[i].len;
-}
 
 __global__ void k_seg_begin(const int64_t* __restrict__ cand_start, const int64_t* __restrict__ item_off, int nq, int64_t n_items,
                             int64_t n_cand, int64_t* __restrict__ seg, unsigned long long* __restrict__ qmin,
@@ -3656,11 +3542,10 @@ static int run_all_candidates(Batch& b, const Route& r) {
     if (!sp.sort_lds)
         CIS_TRY(cis_seg_sort_u64(nullptr, &sort_tmp, nullptr, nullptr, nullptr, nullptr, sp.select ? n_sel : n_cand, nq, nullptr, nullptr, st));
     const size_t tmp_bytes = (sort_tmp + 255) & ~(size_t)255;
-    const size_t n_i64 = (size_t)2 * (n_items + 1) + (size_t)6 * (nq + 2);
+    const size_t n_i64 = (size_t)(n_items + 1) + (size_t)6 * (nq + 2);
     const size_t n_pairs = sp.select ? (size_t)(n_cand + 1) + (size_t)(sp.sort_lds ? 2 : 4) * (n_sel + 1) : (size_t)4 * (n_cand + 1);
     CIS_TRY(ix->w_hits.reserve(n_i64 * 8 + n_pairs * 8 + tmp_bytes + 256));
-    int64_t* lens = ix->w_hits.as<int64_t>();
-    int64_t* cand_start = lens + (n_items + 1);
+    int64_t* cand_start = ix->w_hits.as<int64_t>();
     int64_t* seg = cand_start + (n_items + 1);
     int64_t* seg_b = seg + (nq + 2);
     int64_t* seg_e = seg_b + (nq + 2);

@@ -105,6 +105,13 @@ __device__ __forceinline__ void wave_minmax_step(uint32_t& mn, uint32_t& mx) {
     mn = a < mn ? a : mn;
     mx = b > mx ? b : mx;
 }
+// min and max of the lanes' values over the wave, as wave-uniform (scalar) values
+static __device__ __forceinline__ void wave_minmax_all(uint32_t& mn, uint32_t& mx) {
+    wave_minmax_step<1>(mn, mx); wave_minmax_step<2>(mn, mx); wave_minmax_step<4>(mn, mx);
+    wave_minmax_step<8>(mn, mx); wave_minmax_step<16>(mn, mx); wave_minmax_step<32>(mn, mx);
+    mn = (uint32_t)__builtin_amdgcn_readfirstlane((int)mn);
+    mx = (uint32_t)__builtin_amdgcn_readfirstlane((int)mx);
+}
 
 // Smallest v with  #{valid keys <= v} >= target  == the target-th smallest key (1-based), found by
 // bisection on the value range with ballots: ~4 VALU compares per probe instead of a ~650-instruction
@@ -123,6 +130,52 @@ __device__ __forceinline__ uint32_t wave_kth_bisect(const uint32_t (&key)[NR], c
     return lo;
 }
 
+// #{kept keys <= p} over the wave
+template <int NR>
+__device__ __forceinline__ int wave_count_le(const bool (&keep)[NR], const uint32_t (&key)[NR], uint32_t p) {
+    int c = 0;
+#pragma unroll
+    for (int r = 0; r < NR; ++r) c += __popcll(__ballot(keep[r] && key[r] <= p));
+    return c;
+}
+
+// A value v with #{kept keys <= v} in [n, n + W]: the bisection of wave_kth_bisect, stopped at the first probe whose count falls
+// inside the window.  When ties make the count jump over the window, v is the n-th smallest key.  Needs n <= #kept; [lo, hi]
+// brackets the keys.
+template <int NR>
+__device__ __forceinline__ uint32_t wave_bisect_window(const bool (&keep)[NR], const uint32_t (&key)[NR], uint32_t lo, uint32_t hi,
+                                                       int n, int W) {
+    while (lo < hi) {  // wave-uniform
+        const uint32_t p = lo + ((hi - lo) >> 1);
+        const int c = wave_count_le<NR>(keep, key, p);
+        if (c >= n) {
+            hi = p;
+            if (c <= n + W) break;
+        } else {
+            lo = p + 1;
+        }
+    }
+    return hi;
+}
+
+// Stable compaction of a wave's NR * 64 entries (entry e = r * 64 + lane): store(r, idx) for every entry with pred(r), idx = its
+// index among the kept ones.  Returns their number.  Wave-synchronous: the stores are visible to the wave on return.
+template <int NR, typename P, typename S>
+__device__ __forceinline__ int wave_stable_keep(P&& pred, S&& store) {
+    int n = 0;
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+        const bool kp = pred(r);
+        const unsigned long long m = __ballot(kp);
+        const int idx = n + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
+        if (kp) store(r, idx);
+        n += __popcll(m);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    return n;
+}
+
 template <int NR>
 __device__ __forceinline__ uint32_t wave_kth(const uint32_t (&k)[NR], int i) {  // i-th smallest after the sort
     uint32_t v = k[0];
@@ -138,10 +191,16 @@ static __device__ __forceinline__ float lds_ld(const float* p) {
 static __device__ __forceinline__ uint64_t lds_ld(const uint64_t* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
+static __device__ __forceinline__ uint32_t lds_ld(const uint32_t* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
 static __device__ __forceinline__ void lds_st(float* p, float v) {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 static __device__ __forceinline__ void lds_st(uint64_t* p, uint64_t v) {
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+static __device__ __forceinline__ void lds_st(uint32_t* p, uint32_t v) {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
@@ -166,6 +225,92 @@ static __device__ __forceinline__ double adc64_words(const uint32_t (&cw)[(M + 3
 // distance whose bits start with `vhi`); infinities stay infinite
 static __device__ __forceinline__ uint64_t hi_to_bound(uint32_t vhi) {
     return vhi >= 0x7ff00000u ? 0x7ff0000000000000ull : (((uint64_t)vhi << 32) | 0xffffffffull);
+}
+
+// The exact cut of both scan families (wave_compact_exact, wave_compact3_exact): of the wave's cnt entries with exact float64 keys
+// (hi, lo), entry e = r * 64 + lane in region order, keep[] narrows to the top L by (key, region order).  Region entries are always
+// in increasing candidate position (appends are, and the compactions are stable), so among exactly equal distances "first in the
+// region" == "smallest pos": the order of the reference's stable sorted().  mn / mx: wave_minmax_all of the hi words.  Out: vhiL,
+// the hi word of the L-th entry (mx when cnt < L, nothing cut), and boundL, a distance no smaller than the L kept ones (infinite
+// when cnt < L).  pos_of(r): the candidate position of entry r of this lane.
+template <int NR, typename POS>
+__device__ __forceinline__ void wave_exact_cut(const uint32_t (&hi)[NR], const uint32_t (&lo)[NR], bool (&keep)[NR], POS&& pos_of,
+                                               uint32_t mn, uint32_t mx, int cnt, int L, uint32_t& vhiL, uint64_t& boundL,
+                                               uint32_t& dup_pos) {
+    vhiL = mx;
+    boundL = 0x7ff0000000000000ull;
+    if (cnt >= L) {  // cut to this wave's own exact top-L
+        const uint32_t vhi = wave_kth_bisect<NR>(hi, keep, mn, mx, L);
+        vhiL = vhi;
+        boundL = hi_to_bound(vhi);
+        int c_less = 0, g = 0;
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+            c_less += __popcll(__ballot(keep[r] && hi[r] < vhi));
+            g += __popcll(__ballot(keep[r] && hi[r] == vhi));
+        }
+        int need = L - c_less;  // members of the group {hi == vhi} to keep, 1 <= need <= g
+        if (need >= g) {
+#pragma unroll
+            for (int r = 0; r < NR; ++r) keep[r] = keep[r] && hi[r] <= vhi;
+        } else {
+            // low word of the first group member in region order; are all members equal to it?
+            uint32_t lo_first = 0;
+            bool found = false, uniform = true;
+#pragma unroll
+            for (int r = 0; r < NR; ++r) {
+                const bool in_g = keep[r] && hi[r] == vhi;
+                const unsigned long long m = __ballot(in_g);
+                if (!found && m) {
+                    lo_first = (uint32_t)__builtin_amdgcn_readlane((int)lo[r], __ffsll((long long)m) - 1);
+                    found = true;
+                }
+                if (found) uniform = uniform && (__ballot(in_g && lo[r] != lo_first) == 0ull);
+            }
+            uint32_t vlo = lo_first;
+            if (!uniform) {
+                uint32_t t2[NR];
+#pragma unroll
+                for (int r = 0; r < NR; ++r) t2[r] = (keep[r] && hi[r] == vhi) ? lo[r] : 0xffffffffu;
+                wave_bitonic_sort<NR>(t2);
+                vlo = wave_kth<NR>(t2, need - 1);
+#pragma unroll
+                for (int r = 0; r < NR; ++r) need -= __popcll(__ballot(keep[r] && hi[r] == vhi && lo[r] < vlo));
+            }
+            // exact ties (hi, lo) == (vhi, vlo): the first `need` in region order have the smallest positions
+            int seen = 0;
+#pragma unroll
+            for (int r = 0; r < NR; ++r) {
+                const bool tie = keep[r] && hi[r] == vhi && lo[r] == vlo;
+                const unsigned long long m = __ballot(tie);
+                const int rank = seen + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
+                keep[r] = keep[r] && (hi[r] < vhi || (hi[r] == vhi && (lo[r] < vlo || (tie && rank < need))));
+                // The cut fell inside a group of exactly equal distances.  Remember one member: every LATER
+                // candidate with the same code has the same distance and a larger position, so it loses
+                // against all L entries kept here and the hot loop may skip it (duplicate codes are common).
+                if (seen == 0 && m) dup_pos = (uint32_t)__builtin_amdgcn_readlane((int)pos_of(r), __ffsll((long long)m) - 1);
+                seen += __popcll(m);
+            }
+        }
+    }
+}
+
+// The bound of a query's workgroup from what its waves published (ScanShared, Scan3Shared): every wt[w] is a distance that
+// ceil(limit / NW) candidates of wave w do not exceed, so `limit` candidates do not exceed their maximum; every wl[w], and ext from
+// the query's other cells, is one that `limit` candidates do not exceed.  Exact float64 bits.
+template <int NW, typename SH>
+static __device__ __forceinline__ uint64_t block_bound(const SH* sh) {
+    uint64_t t = lds_ld(&sh->wt[0]);
+    uint64_t l = lds_ld(&sh->wl[0]);
+#pragma unroll
+    for (int i = 1; i < NW; ++i) {
+        const uint64_t a = lds_ld(&sh->wt[i]), b = lds_ld(&sh->wl[i]);
+        t = a > t ? a : t;
+        l = b < l ? b : l;
+    }
+    const uint64_t e = lds_ld(&sh->ext);
+    l = e < l ? e : l;
+    return t < l ? t : l;
 }
 
 // one candidate's code as 32-bit words (little-endian bytes = fine codes 0..M-1)
@@ -212,6 +357,25 @@ __device__ __forceinline__ RotConsts<M> make_rot(int lane) {
 #endif
     }
     return rc;
+}
+
+// one candidate's code words in this lane's rotated order (make_rot): D[t >> 2] holds the byte used at step t
+template <int M>
+__device__ __forceinline__ void rot_words(const CodeWords<M>& c, const RotConsts<M>& rc, uint32_t (&D)[(M + 3) / 4]) {
+    if constexpr (M == 4) {
+        D[0] = c.w[0];
+    } else if constexpr (M == 8) {
+        D[0] = rc.hsel ? c.w[1] : c.w[0];
+        D[1] = rc.hsel ? c.w[0] : c.w[1];
+    } else {
+        const bool b0 = rc.hsel & 1, b1 = rc.hsel & 2;
+        const uint32_t x01 = b0 ? c.w[1] : c.w[0], y01 = b0 ? c.w[0] : c.w[1];
+        const uint32_t x23 = b0 ? c.w[3] : c.w[2], y23 = b0 ? c.w[2] : c.w[3];
+        D[0] = b1 ? x23 : x01;
+        D[1] = b1 ? y23 : y01;
+        D[2] = b1 ? x01 : x23;
+        D[3] = b1 ? y01 : y23;
+    }
 }
 
 // the same through a buffer descriptor that covers exactly the chunk being scanned: one 32-bit offset per

@@ -505,7 +505,10 @@ def test_many_exact_ties_fall_back_to_exact_kernel():
 
 
 def test_device_selftest_of_wave_primitives():
-    """DPP / permlane lane exchanges == __shfl_xor, and the in-register bitonic sort sorts."""
+    """DPP / permlane lane exchanges == __shfl_xor, the in-register bitonic sort sorts, and the selection primitives both scan
+    families cut through (wave_bisect_window, wave_stable_keep, wave_exact_cut) agree with a serial reference computed on the device
+    from the same keys: cuts between groups, through a group of equal high words with different low words (the sort of the low
+    words, which no search test reaches) and through a group of equal keys (first in region order, dup_pos)."""
     import ctypes
     from columbiaimagesearch_amd import _lib
     n = ctypes.c_int(-1)
