@@ -1009,6 +1009,10 @@ static size_t scan4_lds(int M, int K, int lcap, int nw) {
     return (size_t)K * M * S3G * 2 + (lists > samp ? lists : samp) + S3G * sizeof(Scan4Shared) + 32 + (size_t)S3G * nw * 4 + (S4_DS + 1) * sizeof(Slot4);
 }
 
+// row of sample t of ns over a chunk of nrows rows: t * nrows / ns.  t < ns <= nrows <= 1024 (a chunk is at most 65536 candidates), so the
+// product fits 32 bits: the 64-bit division this once was is a few hundred scalar instructions, several times per wave and slot.
+static __device__ __forceinline__ int sample_row(int t, int nrows, int ns) { return (int)(((uint32_t)t * (uint32_t)nrows) / (uint32_t)ns); }
+
 template <int M, int U, int NW, int WPE, int LCAPT>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void k_adc_scan4(
     const WorkItem* __restrict__ items, const TabDesc* __restrict__ tabs, const int* __restrict__ slots,
@@ -1111,7 +1115,9 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
         __syncthreads();             // the previous round's descriptors and lists are dead
         if (tid < S4_DS) {           // one lane per slot walks the chain slot -> items -> table descriptors
             Slot4 d;
-            const int j = (LCAPT > 504 && dyn) ? (tid == 0 ? dyn_j : -1) : slot_of(kb + tid);
+            int dyn_s = dyn;  // (laundered: the hoisted test of `dyn` sat in a vector register as 0 / 1, the long M = 8 form's one spill)
+            asm volatile("" : "+s"(dyn_s));
+            const int j = (LCAPT > 504 && dyn_s) ? (tid == 0 ? dyn_j : -1) : slot_of(kb + tid);
             d.ng = 0; d.len = 0; d.start_lo = d.start_hi = 0;
 #pragma unroll
             for (int g = 0; g < G; ++g) { d.item[g] = 0; d.tab0[g] = 0; d.tab1[g] = 0; d.q[g] = 0; d.qinv[g] = 0.f; d.ist_lo[g] = d.ist_hi[g] = d.ilen[g] = 0; }
@@ -1142,7 +1148,11 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                 d.start_lo = (int)(uint32_t)st0; d.start_hi = (int)(st0 >> 32); d.len = len0;
                 d.ng = same ? ng : -ng;
             }
-            sd[tid] = d;
+            // (laundered like tid_st below: the descriptor's address is an invariant of the round loop and, hoisted, was the one register
+            // the M = 8 forms still kept in private memory)
+            int tid_d = tid;
+            asm volatile("" : "+v"(tid_d));
+            sd[tid_d] = d;
         }
         __syncthreads();
         for (int kk = 0; kk < S4_DS; ++kk) {
@@ -1323,7 +1333,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
 #pragma unroll
                     for (int i = 0; i < SPW; ++i) {
                         const int t = SPW * w + i;
-                        srow[i] = t < ns ? (int)(((int64_t)t * nrows) / ns) : nrows;
+                        srow[i] = t < ns ? sample_row(t, nrows, ns) : nrows;
                         sc[i] = load_code_buf<M>(rs, srow[i] * 64 + lane);  // rows past the chunk read zeros (masked below)
                     }
                     S3_CTR(11, S3_CLK() - c0);
@@ -1369,7 +1379,9 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                         int ksv = L;
                         if (!exact) {
                             const float need = (float)L * (float)nsam / (float)len;
-                            const float hz = 0.5f * zq;
+                            float zq_s = zq;  // (laundered: 0.5 zq is an invariant of the kernel and, hoisted, sat in a spilled vector register)
+                            asm volatile("" : "+s"(zq_s));
+                            const float hz = 0.5f * zq_s;
                             const float rt = hz + sqrtf(hz * hz + need);  // root of k - z sqrt(k) = need
                             ksv = (int)(rt * rt) + 1;
                         }
@@ -1427,7 +1439,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
 #pragma unroll
                     for (int i = 0; i < SPW; ++i) {
                         const int t = SPW * w + i;
-                        srow[i] = t < ns ? (int)(((int64_t)t * nrows) / ns) : nrows;
+                        srow[i] = t < ns ? sample_row(t, nrows, ns) : nrows;
                         sc[i] = load_code_buf<M>(rs, srow[i] * 64 + lane);  // rows past the chunk read zeros (masked below)
                     }
                     S3_CTR(11, S3_CLK() - c0);
@@ -1445,7 +1457,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
 #pragma unroll
                                     for (int i = 0; i < SPW; ++i) {
                                         const int t = ((r + 1) * NW + w) * SPW + i;
-                                        nrow[i] = t < ns ? (int)(((int64_t)t * nrows) / ns) : nrows;
+                                        nrow[i] = t < ns ? sample_row(t, nrows, ns) : nrows;
                                         nsc[i] = load_code_buf<M>(rs, nrow[i] * 64 + lane);
                                     }
                                 }
@@ -1481,8 +1493,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                         uint32_t sv[NW];
 #pragma unroll
                         for (int r = 0; r < NW; ++r) {
-                            const u32x2_t x = reinterpret_cast<const volatile u32x2_t*>(samp)[r * 64 + lane];
-                            const uint32_t xw = (g >> 1) ? x[1] : x[0];
+                            const uint32_t xw = lds_ld(reinterpret_cast<const uint32_t*>(samp) + 2 * (r * 64 + lane) + (g >> 1));  // query g's half of the pair
                             sv[r] = (g & 1) ? (xw >> 16) : (xw & 0xffffu);
                         }
                         // every sampled row is full but the chunk's last one, which is sampled only when all rows are
@@ -1536,7 +1547,9 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                 S3_CTR(4, S3_CLK() - c0);
                 // ---- main pass: every candidate once ------------------------------------------------------------------------------------
                 {
-                    const u32x2_t tpk = *reinterpret_cast<const volatile u32x2_t*>(thr1);
+                    const uint64_t tp64 = lds_ld(reinterpret_cast<const uint64_t*>(thr1));  // (an LDS read: a volatile generic one waits for every load in flight)
+                    u32x2_t tpk;
+                    tpk[0] = (uint32_t)tp64; tpk[1] = (uint32_t)(tp64 >> 32);
                     const uint32_t s01 = (uint32_t)__builtin_amdgcn_readfirstlane((int)tpk[0]);
                     const uint32_t s23 = (uint32_t)__builtin_amdgcn_readfirstlane((int)tpk[1]);
 #if defined(CIS_S4_PROBE) && CIS_S4_PROBE >= 2
@@ -1663,40 +1676,51 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                         // the recorded positions move to registers (two per register), then the list memory becomes the per-query lists
                         const bool pover = pcur > PCAP;  // more passing candidates than the position list holds: the slot falls back
                         const int pn = pover ? 0 : pcur;
+                        // (all NRP reads are in flight at once: the first register is waited for alone, its rows are requested in front of the
+                        // barrier, whose lgkmcnt(0) is the wait of the rest; registers past pn hold stale positions of the wave's own list
+                        // memory, which on_of() below masks)
+                        static_assert(NRP * 128 <= PCAP_LDS, "the NRP registers are read from the wave's own position list");
                         uint32_t pp[NRP];
 #pragma unroll
-                        for (int r = 0; r < NRP; ++r)
-                            pp[r] = (2 * (r * 64) < pn) ? reinterpret_cast<const volatile uint32_t*>(plist)[r * 64 + lane] : 0u;
+                        for (int r = 0; r < NRP; ++r) pp[r] = lds_ld(reinterpret_cast<const uint32_t*>(plist) + r * 64 + lane);
+                        // The second gather takes the registers in turn, two iterations each: iteration it = half (it & 1) of register it >> 1.
+                        // pp[] is ROTATED by one register per trip, so the loop stays rolled and still indexes pp[] by constants only (a
+                        // run-time index put the array in private memory; unrolled sixteen times the loop's many uses of the rotation
+                        // constants drew the M = 16 form's spill reloads into the main pass).  The code rows travel in a ring of two: the row
+                        // of iteration it + 1 is in flight during the gathers of iteration it, a row's wait is vmcnt(1), not vmcnt(0), and the
+                        // first two rows travel across the barrier.  The requests are unconditional -- lanes and iterations past pn ask for
+                        // position `len`, where the descriptor returns zeros without a memory access -- so that every path has the same
+                        // number of loads in flight.  (M = 16 at three waves per SIMD: a spill reload in the preheader still costs that form a
+                        // vmcnt(0) per trip, profiles/scan4_phases_ab.txt.)
+                        auto on_of = [&](int it) -> bool { return 2 * (((it >> 1) * 64) + lane) + (it & 1) < pn; };
+                        CodeWords<M> cw[2];
+                        cw[0] = load_code_buf<M>(rs, on_of(0) ? (int)(pp[0] & 0xffffu) : len);
+                        cw[1] = load_code_buf<M>(rs, on_of(1) ? (int)(pp[0] >> 16) : len);
                         lds_barrier();  // B3b: every wave holds its positions; nobody still writes a position list
                         uint32_t* grow[G];  // GLISTS: the items' survivor rows as 32-bit list memory (S 8-byte entries = 2 S list entries >= LCAP)
 #pragma unroll
                         for (int g = 0; g < G; ++g)
                             grow[g] = reinterpret_cast<uint32_t*>(item_surv + (int64_t)__builtin_amdgcn_readfirstlane(d->item[g]) * S);
                         if (pn > 0) {
-                            auto pos_of = [&](int it) -> uint32_t {  // iteration it takes half (it & 1) of register it >> 1
-                                uint32_t v = pp[0];
-#pragma unroll
-                                for (int r = 1; r < NRP; ++r) v = ((it >> 1) == r) ? pp[r] : v;
-                                return (it & 1) ? (v >> 16) : (v & 0xffffu);
-                            };
-                            auto on_of = [&](int it) -> bool { return 2 * (((it >> 1) * 64) + lane) + (it & 1) < pn; };
-                            const int nit2 = 2 * ((pn + 127) >> 7);  // iterations: halves of ceil(pn / 128) registers
-                            CodeWords<M> nxc[1];
-                            uint32_t npos = pos_of(0);
-                            nxc[0] = load_code_buf<M>(rs, on_of(0) ? (int)npos : len);  // past the chunk: zeros, masked below
+                            const int nreg = (pn + 127) >> 7;  // registers that hold a position
 #pragma unroll 1
-                            for (int it = 0; it < nit2; ++it) {
+                            for (int r = 0; r < nreg; ++r) {
+                              const uint32_t cur = pp[0];
+#pragma unroll
+                              for (int k = 0; k + 1 < NRP; ++k) pp[k] = pp[k + 1];
+                              pp[NRP - 1] = 0u;
+#pragma unroll
+                              for (int h = 0; h < 2; ++h) {
+                                const int it = 2 * r + h;
+                                const uint32_t pos = h ? (cur >> 16) : (cur & 0xffffu);
                                 CodeWords<M> cc[1];
-                                cc[0] = nxc[0];
-                                const uint32_t pos = npos;
-                                const bool on = on_of(it);
-                                if (it + 1 < nit2) {
-                                    npos = pos_of(it + 1);
-                                    nxc[0] = load_code_buf<M>(rs, on_of(it + 1) ? (int)npos : len);
-                                }
+                                cc[0] = cw[h];
                                 u32x2_t d1[1];
                                 adc16_rows<M, 1, S4_OCT>(cc, tab, rc, d1);
-                                const unsigned long long am2 = __ballot(on);
+                                // (requested once the row's words have been consumed, as in the main pass: the load targets the same registers;
+                                // requested earlier it lands in new ones, and the copy at the loop's end waits for it with vmcnt(0))
+                                cw[h] = load_code_buf<M>(rs, on_of(it + 2) ? (int)(h ? (pp[0] >> 16) : (pp[0] & 0xffffu)) : len);
+                                const unsigned long long am2 = __ballot(on_of(it));
 #pragma unroll
                                 for (int g = 0; g < G; ++g) {
                                     const uint32_t sg = (g & 1) ? (d1[0][g >> 1] >> 16) : (d1[0][g >> 1] & 0xffffu);
@@ -1710,6 +1734,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                                     }
                                     wcur[g] += __popcll(mg);
                                 }
+                              }
                             }
                         }
                         if (pover) wcur[0] = WCAP + 1;  // reported like an overflowing quarter (the verification below sends the slot to the fall-back)

@@ -2,7 +2,9 @@
 allow (make -C columbiaimagesearch_amd/csrc report-regs).  Reads the amdhsa.kernels metadata only, no instruction.  On gfx950 a SIMD
 has 512 VGPRs per lane (architectural + accumulation, handed out in blocks of 8) and holds at most 8 waves; LDS and the workgroup size
 can lower the figure further and are not looked at here.
-usage: kernel_regs.py build/x.s ..."""
+usage: kernel_regs.py [--no-scratch SUBSTRING ...] build/x.s ...
+--no-scratch: exit with status 1 when a kernel whose demangled name contains SUBSTRING has a private segment (spills to memory or a
+run-time indexed array), or when no kernel has that name."""
 import re, subprocess, sys
 
 KEYS = ("vgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size")
@@ -29,8 +31,25 @@ def report(path):
     for r, name in sorted(zip(rows, short), key=lambda t: t[1]):
         waves = min(8, 512 // max(8, (r[1] + 7) // 8 * 8))
         print("%6d %6d %6d %8d %6d  %s" % (r[1], r[2], r[3], r[4], waves, name[:120]))
+    return {name: r[4] for r, name in zip(rows, short)}
 
 
 if __name__ == "__main__":
-    for path in sys.argv[1:]:
-        report(path)
+    args, gated = sys.argv[1:], []
+    while args and args[0] == "--no-scratch":
+        gated.append(args[1])
+        args = args[2:]
+    scratch = {}
+    for path in args:
+        scratch.update(report(path))
+    status = 0
+    for want in gated:
+        hit = {n: b for n, b in scratch.items() if want in n}
+        if not hit:
+            print("kernel_regs: no kernel named %s" % want)
+            status = 1
+        for n, b in sorted(hit.items()):
+            if b:
+                print("kernel_regs: %s has a private segment of %d bytes, 0 wanted" % (n, b))
+                status = 1
+    sys.exit(status)
