@@ -69,11 +69,12 @@ def gram_hip(X, assign=None, groups=1):
     return G, S
 
 
-def local_rotations(data, C, num_buckets):
+def local_rotations(data, C, num_buckets, dev=None):
     """Per-cluster residual mean and PCA rotation with balanced variance.
-    reference: lopq/lopq/model.py:74-206.  Returns (R [V,d,d], mu [V,d], assignments, residuals)."""
+    reference: lopq/lopq/model.py:74-206.  Returns (R [V,d,d], mu [V,d], assignments, residuals).
+    dev: `data` as a float32 tensor on the GPU, if the caller has one (KMEANS_BACKEND = "device" assigns from it)."""
     V, d = C.shape
-    assign = assign_clusters(data, C)
+    assign = assign_clusters_dev(data if dev is None else dev, C) if KMEANS_BACKEND == "device" else assign_clusters(data, C)
     residuals = np.asarray(data - C[assign], dtype=np.float64)
     R = np.zeros((V, d, d))
     mu = np.zeros((V, d))
@@ -122,10 +123,19 @@ def project_to_local(residuals, assign, R, mu):
     return out
 
 
+def _is_tensor(x):
+    return type(x).__module__.split(".")[0] == "torch"
+
+
 def kmeans_pp_init(data, k, rs, sample=20000):
     """k-means++ seeding (Arthur & Vassilvitskii) on a subsample, on the host: k sequential draws."""
     n = data.shape[0]
-    x = np.asarray(data[rs.choice(n, min(n, sample), replace=False)], dtype=np.float64)
+    pick = rs.choice(n, min(n, sample), replace=False)
+    if _is_tensor(data):  # resident training set: only the subsample comes to the host
+        import torch
+        x = data[torch.as_tensor(pick, device=data.device)].cpu().numpy().astype(np.float64)
+    else:
+        x = np.asarray(data[pick], dtype=np.float64)
     C = np.empty((k, x.shape[1]))
     C[0] = x[rs.randint(len(x))]
     d2 = ((x - C[0]) ** 2).sum(axis=1)
@@ -153,10 +163,63 @@ def kmeans_hip(data, k, iters, n_init=1, random_state=None):
     return best.astype(np.float64), best_inertia
 
 
-KMEANS_BACKEND = "sklearn"  # "hip": Lloyd iterations on the GPU where the codebook fits the kernel (k * d <= 7680)
+def _resident(data):
+    """`data` as a contiguous float32 [n, d] tensor on the GPU: a numpy array is uploaded, a tensor must already be one."""
+    import torch
+    if _is_tensor(data):
+        if not (data.is_cuda and data.dim() == 2 and data.dtype == torch.float32):
+            raise ValueError("expected a float32 [n, d] tensor on the GPU, got %s %s on %s" % (data.dtype, tuple(data.shape), data.device))
+        return data.contiguous()
+    x = np.ascontiguousarray(data, dtype=np.float32)
+    if x.ndim != 2:
+        raise ValueError("expected an [n, d] matrix, got shape %r" % (x.shape,))
+    return torch.from_numpy(x).to(torch.device("cuda", torch.cuda.current_device()))
 
 
-def _kmeans(data, k, iters, n_init, random_state):
+def kmeans_dev(data, k, iters, n_init=1, random_state=None):
+    """kmeans_hip for codebooks of any size, on data that stays on the GPU (cis_kmeans_dev, csrc/kmeans_mfma.hip): k-means++ seeds
+    from the host, best of n_init by reported inertia; (float64 centroids, inertia).  data: a numpy array (uploaded once, reused by
+    every run) or a float32 tensor on the GPU."""
+    import torch
+    from .. import _lib
+    x = _resident(data)
+    n, d = int(x.shape[0]), int(x.shape[1])
+    rs = np.random.RandomState(random_state)
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    inertia = torch.empty(1, dtype=torch.float64, device=x.device)
+    best, best_inertia = None, np.inf
+    for _ in range(max(int(n_init), 1)):
+        C = torch.from_numpy(np.ascontiguousarray(kmeans_pp_init(x, k, rs), dtype=np.float32)).to(x.device)
+        _lib.check(_lib.lib().cis_kmeans_dev(x.data_ptr(), n, d, int(k), int(iters), C.data_ptr(), None, inertia.data_ptr(), stream))
+        got = float(inertia.cpu()[0])
+        if got < best_inertia:
+            best, best_inertia = C.cpu().numpy(), got
+    return best.astype(np.float64), best_inertia
+
+
+def assign_clusters_dev(data, C):
+    """assign_clusters on the GPU: one assignment pass of cis_kmeans_dev (iters = 0) in float32, int64 assignments on the host.
+    The kernel minimises |c|^2 - 2 x.c, so a point between two almost equally near centroids may go to either."""
+    import torch
+    from .. import _lib
+    x = _resident(data)
+    Cd = torch.from_numpy(np.ascontiguousarray(C, dtype=np.float32)).to(x.device)
+    if Cd.dim() != 2 or Cd.shape[1] != x.shape[1]:
+        raise ValueError("centroids %r do not match data %r" % (tuple(Cd.shape), tuple(x.shape)))
+    assign = torch.empty(int(x.shape[0]), dtype=torch.int32, device=x.device)
+    _lib.check(_lib.lib().cis_kmeans_dev(x.data_ptr(), int(x.shape[0]), int(x.shape[1]), int(Cd.shape[0]), 0, Cd.data_ptr(),
+                                         assign.data_ptr(), None, torch.cuda.current_stream(x.device).cuda_stream))
+    return assign.cpu().numpy().astype(np.int64)
+
+
+# "hip": Lloyd iterations on the GPU where the codebook fits the LDS kernel (k * d <= 7680), scikit-learn beyond.
+# "device": every codebook, and every assignment of the training set, on the GPU (kmeans_dev / assign_clusters_dev).
+KMEANS_BACKEND = "sklearn"
+
+
+def _kmeans(data, k, iters, n_init, random_state, dev=None):
+    if KMEANS_BACKEND == "device":
+        return kmeans_dev(data if dev is None else dev, k, iters, n_init, random_state)[0]
     if KMEANS_BACKEND == "hip" and k * data.shape[1] <= 7680:
         return kmeans_hip(data, k, iters, n_init, random_state)[0]
     from sklearn.cluster import MiniBatchKMeans
@@ -203,13 +266,17 @@ def train(data, V=8, M=4, subquantizer_clusters=256, parameters=None, kmeans_coa
     if Rs is None or mus is None:
         Rs = mus = None
     halves = np.split(data, 2, axis=1)
+    devs = [None, None]
+    if KMEANS_BACKEND == "device" and (Cs is None or Rs is None):  # one upload per half: the coarse k-means and the assignment share it
+        devs = [_resident(h) for h in halves]
     if Cs is None:
-        Cs = tuple(_kmeans(h, V, kmeans_coarse_iters, n_init, random_state) for h in halves)
+        Cs = tuple(_kmeans(h, V, kmeans_coarse_iters, n_init, random_state, dev) for h, dev in zip(halves, devs))
     fitted = None
     if Rs is None:
-        fitted = [local_rotations(h, C, M // 2) for h, C in zip(halves, Cs)]
+        fitted = [local_rotations(h, C, M // 2, dev) for h, C, dev in zip(halves, Cs, devs)]
         Rs = tuple(f[0] for f in fitted)
         mus = tuple(f[1] for f in fitted)
+    del devs
     if subs is not None:
         return tuple(Cs), tuple(Rs), tuple(mus), subs
     N = data.shape[0]
@@ -221,7 +288,7 @@ def train(data, V=8, M=4, subquantizer_clusters=256, parameters=None, kmeans_coa
             assign, residuals = fitted[s][2][sample], fitted[s][3][sample]
         else:
             hs = h[sample]
-            assign = assign_clusters(hs, C)
+            assign = assign_clusters_dev(hs, C) if KMEANS_BACKEND == "device" else assign_clusters(hs, C)
             residuals = np.asarray(hs - C[assign], dtype=np.float64)
         projected = project_to_local(residuals, assign, Rs[s], mus[s])
         subs.append([_kmeans(p, subquantizer_clusters, kmeans_local_iters, n_init, random_state)

@@ -324,6 +324,21 @@ int cis_exact_knn_stats(int64_t stats[3]);
  * (sum of squared distances, or NULL) refer to the returned centroids. */
 int cis_kmeans(const float* X, int64_t n, int d, int k, int iters, float* centroids, int32_t* assign, double* inertia);
 
+/* The same Lloyd iterations on data that is already on the device, for codebooks of any size (csrc/kmeans_mfma.hip).  Every pointer is
+ * a device pointer: d_X [n][d] float32 (never written), d_centroids [k][d] float32 (initial centroids in, trained centroids out),
+ * d_assign [n] int32 (or NULL) and d_inertia (one double, or NULL).  `iters` updates are followed by one more assignment pass, so
+ * d_assign and *d_inertia describe the returned centroids; iters = 0 only assigns and leaves the centroids' bytes alone.  An empty
+ * cluster keeps its centroid's bytes; of equally near centroids the lowest index wins.  The call only enqueues kernels on `stream`
+ * and returns without waiting for the device; its grow-only workspace is allocated on the first use of a size.
+ * The assignment minimises fl32(|c|^2 - 2 x.c) computed on the float32 matrix cores: with u = 2^-24 and r = |x| + max_c |c| the
+ * chosen centroid's true squared distance is at most the minimum + 2 (d + 4) u r^2 (exact on small-integer data).  The inertia is
+ * the direct form for the chosen centroid, acc = fmaf(x[i] - c[i], x[i] - c[i], acc) for i ascending, summed in double.  The sums of
+ * an update are float32 atomics: centroids may differ in their last bits from run to run, as those of cis_kmeans may.
+ * Limits (CIS_EINVAL beyond): 1 <= n <= 2^31 - 256 (int32 assignments), k >= 1, d >= 1, k * d <= 2^30 (32-bit element indices).
+ * The calls share one process-wide workspace: they must not overlap on two streams or threads. */
+int cis_kmeans_dev(const float* d_X, int64_t n, int d, int k, int iters, float* d_centroids, int32_t* d_assign, double* d_inertia,
+                   void* stream);
+
 /* Training accumulations on the GPU (csrc/lopq_train.hip), float64, host pointers.  Rows of X [n][d] are sorted by group;
  * group_off [groups+1] are the row offsets (group_off[0] = 0, group_off[groups] = n).
  * cis_train_gram:    G[g] = sum_{r in g} x_r x_r^T [groups][d][d] and S[g] = sum x_r [groups][d] (S may be NULL): the np.outer
