@@ -214,15 +214,19 @@ __device__ __forceinline__ int wave_filter3(uint32_t* rk, int cnt, const QScale&
 // The pipeline unit of the hot loop: OCT table reads (ds_read_b64, four queries each) of one candidate -- steps
 // [o*OCT, (o+1)*OCT) of the lane-rotated sub-quantizer order -- and their sum.  M = 16 is two units per candidate, so
 // that the register footprint of the reads in flight is the same for every M.
-template <int M, int OCT>
+// TWO (k_adc_scan4's long-chunk M = 8 form): two interleaved copies of the table, a k-row is 2 M * 8 bytes and rc.cj carries the
+// lane's copy (two_copy_rot) -- the same two VALU per entry.
+template <int M, int OCT, bool TWO = false>
 __device__ __forceinline__ void adc16_issue(const uint32_t (&D)[(M + 3) / 4], int o, const char* __restrict__ tab,
                                             const RotConsts<M>& rc, u32x2_t (&f)[OCT]) {
-    constexpr int SH = ((M == 4) ? 2 : (M == 8 ? 3 : 4)) + 3;  // log2(M * 8 bytes): one k-row of the table
+    constexpr int SH = ((M == 4) ? 2 : (M == 8 ? 3 : 4)) + 3 + (TWO ? 1 : 0);  // log2(M * 8 bytes): one k-row of the table
 #pragma unroll
     for (int i = 0; i < OCT; ++i) {
         const int t = o * OCT + i;
         const uint32_t k = __builtin_amdgcn_ubfe(D[t >> 2], rc.sh[t & 3], 8);
-        f[i] = *reinterpret_cast<const u32x2_t*>(tab + ((k << SH) | (rc.cj[t] << 1)));
+        // (TWO: written as a sum, so that every entry is one shift-add onto a constant that holds the table's base)
+        if constexpr (TWO) f[i] = *reinterpret_cast<const u32x2_t*>(tab + ((k << SH) + (rc.cj[t] << 1)));
+        else f[i] = *reinterpret_cast<const u32x2_t*>(tab + ((k << SH) | (rc.cj[t] << 1)));
     }
 }
 
@@ -919,21 +923,21 @@ struct Scan4Shared {  // per query
 };
 
 // sums of UU rows of 64 candidates (software pipelined: the table reads of unit q+1 are issued before the adds of unit q)
-template <int M, int UU, int OCT = (M >= 8 ? 8 : 4)>
+template <int M, int UU, int OCT = (M >= 8 ? 8 : 4), bool TWO = false>
 __device__ __forceinline__ void adc16_rows(const CodeWords<M> (&cur)[UU], const char* __restrict__ tab, const RotConsts<M>& rc,
                                            u32x2_t (&d)[UU]) {
     constexpr int NU = M / OCT;
     u32x2_t fbuf[2][OCT];
     uint32_t D[2][(M + 3) / 4];
     rot_words<M>(cur[0], rc, D[0]);
-    adc16_issue<M, OCT>(D[0], 0, tab, rc, fbuf[0]);
+    adc16_issue<M, OCT, TWO>(D[0], 0, tab, rc, fbuf[0]);
 #pragma unroll
     for (int q = 0; q < UU * NU; ++q) {
         const int u = q / NU, o = q % NU;
         if (q + 1 < UU * NU) {
             const int u1 = (q + 1) / NU, o1 = (q + 1) % NU;
             if (o1 == 0) rot_words<M>(cur[u1], rc, D[u1 & 1]);
-            adc16_issue<M, OCT>(D[u1 & 1], o1, tab, rc, fbuf[(q + 1) & 1]);
+            adc16_issue<M, OCT, TWO>(D[u1 & 1], o1, tab, rc, fbuf[(q + 1) & 1]);
         }
         __builtin_amdgcn_sched_barrier(0);
         const u32x2_t part = adc16_sum<OCT>(fbuf[q & 1]);
@@ -1003,7 +1007,35 @@ static const int S4_NS = CIS_S4_NS;      // sample rows per chunk (64 sums per q
 
 static const int S4_LCAP_LONG = 1016;    // list entries per query for long chunks (sixteen registers per lane in the verification)
 
+// The long-chunk M = 8 form keeps TWO interleaved copies of the table: entry (k, j, copy c) at byte
+// k << 7 | (2 j + c) << 3, copy 0 in the even 8-byte slots and copy 1 in the odd ones.  A lane's copy is bit 3 of its number, which
+// splits the four lanes of a 32-lane read group that share a sub-quantizer: each (sub-quantizer, copy) owns two bank pairs for two
+// lanes instead of four bank pairs for the four lanes of ALL sub-quantizers of a residue.  The second copy costs no LDS: after the
+// main pass (barrier B3b) its slots hold the per-query lists, and the recorded positions move to the sample's region.
+static const int S4_TWO_NRP = 24;  // registers of packed positions per slot (all waves): 768 positions per wave of four
+static constexpr bool scan4_two(int M, int lcap) { return M == 8 && lcap > 504 && CIS_S4_DEFER != 0 && CIS_S4_GLISTS == 0; }
+// bytes of the table region of the two-copy form: both copies, and room for G lists of lcap words in the odd slots
+static constexpr size_t scan4_two_tab(int K, int lcap) {
+    const size_t t = (size_t)K * 8 * S3G * 4, l = (((size_t)S3G * lcap + 1) / 2) * 16;
+    return t > l ? t : l;
+}
+// table region (lists inside it), recorded positions (the sample's bucket minima before them), shared records
+static constexpr size_t scan4_two_lds(int K, int lcap, int nw) {
+    return scan4_two_tab(K, lcap) + (size_t)S4_TWO_NRP * 128 * 2 + S3G * sizeof(Scan4Shared) + 32 + (size_t)S3G * nw * 4 + (S4_DS + 1) * sizeof(Slot4);
+}
+static_assert(4 * scan4_two_lds(256, S4_LCAP_LONG, 4) <= 163840, "the two-copy form keeps four workgroups of four waves per CU");
+static __device__ __forceinline__ RotConsts<8> two_copy_rot(const RotConsts<8>& rc, uint32_t copy) {
+    RotConsts<8> r2 = rc;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) r2.cj[t] = (rc.cj[t] << 1) | (copy << 2);  // (adc16_issue shifts by one more: (2 j + c) << 3)
+    return r2;
+}
+// byte of list word i in the odd slots of the table region
+// ((i >> 1) << 4 | 8 | (i & 1) << 2, written as a sum: the 8 folds into the instruction's offset)
+static __device__ __forceinline__ int two_list_byte(int i) { return ((i >> 1) << 4) + ((i & 1) << 2) + 8; }
+
 static size_t scan4_lds(int M, int K, int lcap, int nw) {
+    if (scan4_two(M, lcap)) return scan4_two_lds(K, lcap, nw);
     const bool glists = lcap > 504 && CIS_S4_DEFER != 0 && CIS_S4_GLISTS != 0;
     const size_t lists = glists ? (size_t)nw * ((32 / nw) * 128) * 2 : (size_t)S3G * lcap * 4, samp = glists ? 0 : (size_t)S3G * S4_NS * 64 * 2;
     return (size_t)K * M * S3G * 2 + (lists > samp ? lists : samp) + S3G * sizeof(Scan4Shared) + 32 + (size_t)S3G * nw * 4 + (S4_DS + 1) * sizeof(Slot4);
@@ -1043,9 +1075,13 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
     // more (48 / 71 spilled registers) than the extra workgroups bring.  Off by default; results identical either way.
     constexpr bool GLISTS = (LCAPT > 504) && (CIS_S4_DEFER != 0) && (CIS_S4_GLISTS != 0);
     constexpr size_t LIST_B_FULL = (size_t)G * LCAP * 4 > (size_t)G * NS * 64 * 2 ? (size_t)G * LCAP * 4 : (size_t)G * NS * 64 * 2;
-    constexpr size_t LIST_B = GLISTS ? (size_t)NW * (((LCAPT > 504 ? 32 : 16) / NW) * 128) * 2 : LIST_B_FULL;
-    char* tab = smem;                                                            // [K][M][G] uint16
-    uint32_t* lists = reinterpret_cast<uint32_t*>(smem + (size_t)K * M * G * 2);  // [G][LCAP] (sum << 16 | position)
+    // TWO: two interleaved table copies (scan4_two above).  `lists` is then the region of the recorded positions and of the sample's bucket
+    // minima only; the per-query lists live in the odd slots of the table region from B3b on (list_at below)
+    constexpr bool TWO = scan4_two(M, LCAPT);
+    constexpr size_t LIST_B = TWO ? (size_t)S4_TWO_NRP * 128 * 2 : (GLISTS ? (size_t)NW * (((LCAPT > 504 ? 32 : 16) / NW) * 128) * 2 : LIST_B_FULL);
+    static_assert(!TWO || LIST_B >= (size_t)NW * 64 * 8, "the bucket minima of the sample fit the position lists' region");
+    char* tab = smem;                                                            // [K][M][G] uint16 (TWO: [K][M][2][G])
+    uint32_t* lists = reinterpret_cast<uint32_t*>(smem + (TWO ? scan4_two_tab(K, LCAPT) : (size_t)K * M * G * 2));  // [G][LCAP] (sum << 16 | position)
     uint16_t* samp = reinterpret_cast<uint16_t*>(lists);                         // [G][NS * 64] the sample's sums (before the main pass)
     Scan4Shared* sh = reinterpret_cast<Scan4Shared*>(reinterpret_cast<char*>(lists) + LIST_B);
     uint16_t* thr1 = reinterpret_cast<uint16_t*>(sh + G);  // [G] collection thresholds + 1, packed like the sums
@@ -1061,7 +1097,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
     constexpr int WCAP = LCAPT / NW;
     // deferred split: 16-bit positions per wave in the list memory (PCAP_LDS of them fit), of which NRP registers' worth are used
     constexpr int PCAP_LDS = (int)(LIST_B / (NW * 2));
-    constexpr int NRP = (LCAPT > 504 ? 32 : 16) / NW;      // registers of packed positions per lane in the second gather
+    constexpr int NRP = (TWO ? S4_TWO_NRP : (LCAPT > 504 ? 32 : 16)) / NW;  // registers of packed positions per lane in the second gather
     constexpr int PCAP = NRP * 128 < PCAP_LDS ? NRP * 128 : PCAP_LDS;
     static_assert(PCAP % 2 == 0 && (PCAP_LDS * 2) % 4 == 0, "position lists are read back as 32-bit pairs");
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1078,7 +1114,10 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
         const int j = (((li >> 5) * 8 + xcd) << 5) | (li & 31);
         return j < total ? j : -1;
     };
-    const RotConsts<M> rc = make_rot<M>(lane);
+    RotConsts<M> rc = make_rot<M>(lane);
+    if constexpr (TWO) rc = two_copy_rot(rc, ((uint32_t)lane >> 3) & 1u);
+    // word i of the per-query lists [(g * NW + w) * WCAP + idx]
+    auto list_at = [&](int i) -> uint32_t* { return reinterpret_cast<uint32_t*>(tab + two_list_byte(i)); };  // (TWO)
     const int nvec = (nf * K) >> 2;  // float4 per half table (<= 256 = threads)
     const long long k0 = S3_CLK();
     (void)k0;
@@ -1288,7 +1327,13 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                             u32x2_t pk;
                             pk[0] = qv[0] | (qv[1] << 16);
                             pk[1] = qv[2] | (qv[3] << 16);
-                            *reinterpret_cast<u32x2_t*>(tw + (((k0 + c) * M + s2 * nf + j) << 1)) = pk;
+                            if constexpr (TWO) {  // both copies of the entry with one 16-byte store
+                                u32x4_t pk2;
+                                pk2[0] = pk[0]; pk2[1] = pk[1]; pk2[2] = pk[0]; pk2[3] = pk[1];
+                                *reinterpret_cast<u32x4_t*>(tw + (((k0 + c) * M + s2 * nf + j) << 2)) = pk2;
+                            } else {
+                                *reinterpret_cast<u32x2_t*>(tw + (((k0 + c) * M + s2 * nf + j) << 1)) = pk;
+                            }
                         }
                     }
                 }
@@ -1466,7 +1511,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
 #if defined(CIS_S4_PROBE) && CIS_S4_PROBE >= 3
                             for (int u = 0; u < SPW; ++u) { dd[u][0] = 0xffffffffu; dd[u][1] = 0xffffffffu; }  // probe: no sample pass
 #else
-                            adc16_rows<M, SPW, S4_OCT>(sc, tab, rc, dd);
+                            adc16_rows<M, SPW, S4_OCT, TWO>(sc, tab, rc, dd);
 #endif
 #pragma unroll
                             for (int u = 0; u < SPW; ++u) {
@@ -1591,7 +1636,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                         const int iter = iter0 + k * NW;
                         const int base = iter * 64 * U;
                         u32x2_t dd[U];
-                        adc16_rows<M, U, S4_OCT>(ring[k], tab, rc, dd);
+                        adc16_rows<M, U, S4_OCT, TWO>(ring[k], tab, rc, dd);
                         // the set's next rows are requested as soon as its words have been consumed (the loads target the same registers:
                         // no copies).  Unconditional -- past the chunk the descriptor returns zeros -- so that every path through the
                         // loop has the same number of loads in flight and the wait before a set's use is vmcnt((PF - 1) * U), not vmcnt(0)
@@ -1600,8 +1645,22 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
 #pragma unroll
                         for (int u = 0; u < U; ++u) {
                             const uint32_t xx = pk_subsat_u16(tpk[0], dd[u][0]) | pk_subsat_u16(tpk[1], dd[u][1]);
-                            unsigned long long am = __ballot(xx != 0u);
                             const int n = len - base - u * 64;
+#if CIS_S4_DEFER
+                            if constexpr (TWO) {
+                                // The chunk's end as a lane compare: the passing lanes are ONE condition mask, which is the ballot and the
+                                // append's predicate (the scalar mask below is built with eight scalar instructions per row and tested by
+                                // the append with two ANDs and a 64-bit compare)
+                                const bool pass = xx != 0u && lane < n;
+                                const unsigned long long am = __builtin_amdgcn_ballot_w64(xx != 0u) & __builtin_amdgcn_ballot_w64(lane < n);
+                                if (am == 0ull) continue;  // scalar branch
+                                const int idx = __builtin_amdgcn_mbcnt_hi((unsigned)(am >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)am, pcur));
+                                if (pass && idx < PCAP) plist[idx] = (uint16_t)(base + u * 64 + lane);
+                                pcur += __popcll(am);
+                                continue;
+                            }
+#endif
+                            unsigned long long am = __ballot(xx != 0u);
                             if (n < 64) am &= n <= 0 ? 0ull : ((1ull << n) - 1ull);
                             if (am == 0ull) continue;  // scalar branch
 #if CIS_S4_DEFER
@@ -1697,6 +1756,17 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                         cw[0] = load_code_buf<M>(rs, on_of(0) ? (int)(pp[0] & 0xffffu) : len);
                         cw[1] = load_code_buf<M>(rs, on_of(1) ? (int)(pp[0] >> 16) : len);
                         lds_barrier();  // B3b: every wave holds its positions; nobody still writes a position list
+                        // TWO: B3b is also behind the last gather of every wave's main pass, so copy 1 ends here -- its slots take the
+                        // per-query lists, and this gather reads copy 0 alone.  Its constants are derived here (the mask is laundered: hoisted,
+                        // they would be eight more registers across the main pass)
+                        RotConsts<M> rc0;
+                        if constexpr (TWO) {
+                            rc0 = rc;
+                            uint32_t keep0 = ~4u;
+                            asm volatile("" : "+v"(keep0));
+#pragma unroll
+                            for (int t = 0; t < M; ++t) rc0.cj[t] = rc.cj[t] & keep0;
+                        }
                         uint32_t* grow[G];  // GLISTS: the items' survivor rows as 32-bit list memory (S 8-byte entries = 2 S list entries >= LCAP)
 #pragma unroll
                         for (int g = 0; g < G; ++g)
@@ -1716,7 +1786,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                                 CodeWords<M> cc[1];
                                 cc[0] = cw[h];
                                 u32x2_t d1[1];
-                                adc16_rows<M, 1, S4_OCT>(cc, tab, rc, d1);
+                                if constexpr (TWO) adc16_rows<M, 1, S4_OCT, true>(cc, tab, rc0, d1);
+                                else adc16_rows<M, 1, S4_OCT>(cc, tab, rc, d1);
                                 // (requested once the row's words have been consumed, as in the main pass: the load targets the same registers;
                                 // requested earlier it lands in new ones, and the copy at the loop's end waits for it with vmcnt(0))
                                 cw[h] = load_code_buf<M>(rs, on_of(it + 2) ? (int)(h ? (pp[0] >> 16) : (pp[0] & 0xffffu)) : len);
@@ -1730,6 +1801,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                                     const int idx = __builtin_amdgcn_mbcnt_hi((unsigned)(mg >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mg, wcur[g]));
                                     if (((mg >> lane) & 1ull) && idx < WCAP) {
                                         if constexpr (GLISTS) grow[g][w * WCAP + idx] = (sg << 16) | pos;
+                                        else if constexpr (TWO) *list_at((g * NW + w) * WCAP + idx) = (sg << 16) | pos;
                                         else lists[(g * NW + w) * WCAP + idx] = (sg << 16) | pos;
                                     }
                                     wcur[g] += __popcll(mg);
@@ -1786,7 +1858,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                                     const uint32_t* gr = reinterpret_cast<const uint32_t*>(item_surv + (int64_t)__builtin_amdgcn_readfirstlane(d->item[g]) * S);
                                     ent[r] = val[r] ? __hip_atomic_load(gr + (r / RW) * WCAP + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0xffffffffu;
                                 } else {
-                                    ent[r] = val[r] ? lists[(g * NW + r / RW) * WCAP + e] : 0xffffffffu;
+                                    if constexpr (TWO) ent[r] = val[r] ? *list_at((g * NW + r / RW) * WCAP + e) : 0xffffffffu;
+                                    else ent[r] = val[r] ? lists[(g * NW + r / RW) * WCAP + e] : 0xffffffffu;
                                 }
                             } else {
                                 val[r] = r * 64 + lane_v < tot;
