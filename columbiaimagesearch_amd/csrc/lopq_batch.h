@@ -44,7 +44,6 @@ struct Route {
     // route_decide: with the plan totals, or their bounds
     bool direct;        // tiny cells on the all-candidates path: entries computed per candidate from px (k_adc_direct), no tables
     bool stream;
-    bool use5;          // k_adc_scan5 where the sampled form k_adc_scan4 would run
     bool drop_t32;
     Scan3Geom geom3;
     int S;              // hit slots per work item (fast kernels: a full region per wave)

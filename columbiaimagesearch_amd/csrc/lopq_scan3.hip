@@ -244,7 +244,6 @@ __device__ __forceinline__ u32x2_t adc16_sum(const u32x2_t (&f)[OCT]) {
     return r;
 }
 
-static __device__ __forceinline__ uint32_t ld16(const uint16_t* p) { return *reinterpret_cast<const volatile uint16_t*>(p); }
 static __device__ __forceinline__ void st16(uint16_t* p, uint32_t v) { *reinterpret_cast<volatile uint16_t*>(p) = (uint16_t)v; }
 
 // One workgroup (NW waves) scans one cell chunk (<= 65536 candidates) for `ng` <= 4 queries that all visit it.
@@ -300,12 +299,8 @@ __device__ __forceinline__ void scan3_group(const WorkItem* __restrict__ items, 
                                                   : 0x7ff0000000000000ull;
             sh[g].ext = e;
             // an absent query: threshold 0 (thr1 = 0: the saturated difference is never non-zero) and maximal table entries
-            uint32_t thr = (g < ng) ? bound_to_thr(e, inv_up) : 0u;
-#ifdef CIS_S3_PROBE_NOPASS
-            thr = 0u;  // probe: nothing passes, only the fixed-point scan runs
-            if (true) { sh[g].thr = 0u; thr1[g] = 0; } else
-#endif
-            { sh[g].thr = thr; thr1[g] = (uint16_t)((g < ng) ? thr + 1u : 0u); }
+            const uint32_t thr = (g < ng) ? bound_to_thr(e, inv_up) : 0u;
+            sh[g].thr = thr; thr1[g] = (uint16_t)((g < ng) ? thr + 1u : 0u);
             // what the merge may assume about a survivor: exact distance >= (its float32 upper bound) - slack
             if (g < ng) {
                 item_slack[2 * (int64_t)item_idx[g] + 0] = __double2float_ru(ub * ((double)M + 0.1));
@@ -358,11 +353,7 @@ __device__ __forceinline__ void scan3_group(const WorkItem* __restrict__ items, 
     const int len = __builtin_amdgcn_readfirstlane(it0.len);
     const int64_t start = ((int64_t)__builtin_amdgcn_readfirstlane((int)(it0.start >> 32)) << 32) |
                           (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)it0.start);
-#ifdef CIS_S3_PROBE_NOLOOP
-    const int nit = 0;  // probe: prologue + epilogue only
-#else
     const int nit = (len + 64 * U - 1) / (64 * U);
-#endif
     int cnt[G];
     CodeWords<M> dup[G];  // per query: a code whose later copies cannot enter this wave's top-L any more
     bool has_dup[G];
@@ -497,9 +488,6 @@ __device__ __forceinline__ void scan3_group(const WorkItem* __restrict__ items, 
                     const uint32_t nb = (thr + 1u) >> BSH;  // the bin right after the edge
                     if (nb < (uint32_t)NB) n_keep += hist[g * NB + nb];
                 }
-#ifdef CIS_S3_OLD_EDGE  // test-sensitivity builds only: the collection threshold before the fix
-                keep = thr;
-#endif
                 const uint32_t t_ext = lds_ld(&sh[g].thr);  // from the query's other cells (or 0 for an absent query)
                 const uint32_t t = keep < t_ext ? keep : t_ext;
                 sh[g].thr = t;
@@ -971,24 +959,6 @@ static __device__ __forceinline__ void lds_barrier() {
 #define CIS_S4_WPE 6
 #endif
 static const int S4_OCT = CIS_S4_OCT;  // table reads per pipeline unit of the main pass (4: 16 registers of reads in flight)
-#ifndef CIS_S4_DEFER
-#define CIS_S4_DEFER 1  // the main pass records positions only; the per-query split runs on a second gather of the recorded candidates
-#endif
-#ifndef CIS_S4_NW_LONG
-#define CIS_S4_NW_LONG 4   // waves per slot, long chunks (8: measured slower on C4, 0.275 - 0.32 against 0.243 ms: profiles/r04f_ab.txt)
-#endif
-#ifndef CIS_S4_NW_SHORT
-#define CIS_S4_NW_SHORT 4  // waves per slot, short chunks
-#endif
-#ifndef CIS_S4_WPE8
-#define CIS_S4_WPE8 6      // waves per SIMD the 8-wave long-chunk variant is compiled for (80 registers: three workgroups per CU)
-#endif
-#ifndef CIS_S4_GLISTS
-#define CIS_S4_GLISTS 0    // 1: long chunks keep their per-query lists in global memory (26 KB of LDS per workgroup) -- measured and lost, see GLISTS below
-#endif
-#ifndef CIS_S4_WPE_LONG
-#define CIS_S4_WPE_LONG 6  // waves per SIMD the long-chunk variant is compiled for (80 registers) when its lists are in global memory
-#endif
 #ifndef CIS_S4_PF
 #define CIS_S4_PF 2  // iterations of a wave that its code rows travel ahead
 #endif
@@ -1013,7 +983,7 @@ static const int S4_LCAP_LONG = 1016;    // list entries per query for long chun
 // lanes instead of four bank pairs for the four lanes of ALL sub-quantizers of a residue.  The second copy costs no LDS: after the
 // main pass (barrier B3b) its slots hold the per-query lists, and the recorded positions move to the sample's region.
 static const int S4_TWO_NRP = 24;  // registers of packed positions per slot (all waves): 768 positions per wave of four
-static constexpr bool scan4_two(int M, int lcap) { return M == 8 && lcap > 504 && CIS_S4_DEFER != 0 && CIS_S4_GLISTS == 0; }
+static constexpr bool scan4_two(int M, int lcap) { return M == 8 && lcap > 504; }
 // bytes of the table region of the two-copy form: both copies, and room for G lists of lcap words in the odd slots
 static constexpr size_t scan4_two_tab(int K, int lcap) {
     const size_t t = (size_t)K * 8 * S3G * 4, l = (((size_t)S3G * lcap + 1) / 2) * 16;
@@ -1036,8 +1006,7 @@ static __device__ __forceinline__ int two_list_byte(int i) { return ((i >> 1) <<
 
 static size_t scan4_lds(int M, int K, int lcap, int nw) {
     if (scan4_two(M, lcap)) return scan4_two_lds(K, lcap, nw);
-    const bool glists = lcap > 504 && CIS_S4_DEFER != 0 && CIS_S4_GLISTS != 0;
-    const size_t lists = glists ? (size_t)nw * ((32 / nw) * 128) * 2 : (size_t)S3G * lcap * 4, samp = glists ? 0 : (size_t)S3G * S4_NS * 64 * 2;
+    const size_t lists = (size_t)S3G * lcap * 4, samp = (size_t)S3G * S4_NS * 64 * 2;
     return (size_t)K * M * S3G * 2 + (lists > samp ? lists : samp) + S3G * sizeof(Scan4Shared) + 32 + (size_t)S3G * nw * 4 + (S4_DS + 1) * sizeof(Slot4);
 }
 
@@ -1058,27 +1027,18 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int G = S3G;
     // NW waves gather (sample, main pass, second gather); waves 0 .. G-1 also serve one query each in the threshold and verification
-    // phases.  NW = 8 (round 4): a slot's latency, not the chip's throughput, bounds the launch -- a slot alone on the chip takes as long
-    // as one among 1024 (tools/nq_sweep.py) -- so twice the waves per slot halve the main pass, and three such workgroups per CU are
-    // 24 waves against 16
+    // phases.  Only NW = 4 is launched: a slot's latency, not the chip's throughput, bounds the launch -- a slot alone on the chip takes
+    // as long as one among 1024 (tools/nq_sweep.py) -- but eight waves per slot measured slower (profiles/archive/r04/r04_scan4_nw8_ab.txt)
     static_assert(NW >= G && NW % G == 0 && NW <= 8, "waves 0 .. G-1 serve one query each in the threshold and verification phases");
     static_assert(M == 4 || M == 8 || M == 16, "float4s of the half tables are dealt to the threads in rounds of 256");
     constexpr int nf = M / 2;
     constexpr uint32_t CAP = 65535u / M;
     constexpr int LCAP = LCAPT, NS = S4_NS, NRV = (LCAP + 63) / 64;
-    // GLISTS (round 4, long chunks with the deferred split): the per-query lists live in the items' survivor rows in GLOBAL memory
-    // (written by the second gather, read back from L2 by the verification: ~1600 entries per slot), so LDS holds the tables and the
-    // 16-bit position lists only -- 26 KB per workgroup, six workgroups per CU instead of four: a slot is bound by latency, and 46 % of
-    // it is serial per-query work during which only other workgroups can use the SIMDs.
-    // MEASURED (profiles/r04_scan4_glists_ab.txt, C4, one batch at a time): 128 registers / 4 workgroups per CU 0.237 ms (= the LDS lists,
-    // 0.232-0.238), 96 registers / 5 per CU 0.256, 80 registers / 6 per CU 0.310 -- the register budget of the higher occupancies costs
-    // more (48 / 71 spilled registers) than the extra workgroups bring.  Off by default; results identical either way.
-    constexpr bool GLISTS = (LCAPT > 504) && (CIS_S4_DEFER != 0) && (CIS_S4_GLISTS != 0);
     constexpr size_t LIST_B_FULL = (size_t)G * LCAP * 4 > (size_t)G * NS * 64 * 2 ? (size_t)G * LCAP * 4 : (size_t)G * NS * 64 * 2;
     // TWO: two interleaved table copies (scan4_two above).  `lists` is then the region of the recorded positions and of the sample's bucket
     // minima only; the per-query lists live in the odd slots of the table region from B3b on (list_at below)
     constexpr bool TWO = scan4_two(M, LCAPT);
-    constexpr size_t LIST_B = TWO ? (size_t)S4_TWO_NRP * 128 * 2 : (GLISTS ? (size_t)NW * (((LCAPT > 504 ? 32 : 16) / NW) * 128) * 2 : LIST_B_FULL);
+    constexpr size_t LIST_B = TWO ? (size_t)S4_TWO_NRP * 128 * 2 : LIST_B_FULL;
     static_assert(!TWO || LIST_B >= (size_t)NW * 64 * 8, "the bucket minima of the sample fit the position lists' region");
     char* tab = smem;                                                            // [K][M][G] uint16 (TWO: [K][M][2][G])
     uint32_t* lists = reinterpret_cast<uint32_t*>(smem + (TWO ? scan4_two_tab(K, LCAPT) : (size_t)K * M * G * 2));  // [G][LCAP] (sum << 16 | position)
@@ -1086,15 +1046,10 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
     Scan4Shared* sh = reinterpret_cast<Scan4Shared*>(reinterpret_cast<char*>(lists) + LIST_B);
     uint16_t* thr1 = reinterpret_cast<uint16_t*>(sh + G);  // [G] collection thresholds + 1, packed like the sums
     int* s_flag = reinterpret_cast<int*>(thr1 + 4);
-    int* s_cnt = s_flag + 1;                               // [G] list cursors (the 4-lane atomic of the main pass)
-    int* wcnt = reinterpret_cast<int*>(reinterpret_cast<char*>(thr1) + 32);  // [G][NW] entries of the wave-private lists (long chunks)
+    int* s_cnt = s_flag + 1;                               // [G] zeroed per slot, read by nobody: to go with the next change of this kernel's code
+    int* wcnt = reinterpret_cast<int*>(reinterpret_cast<char*>(thr1) + 32);  // [G][NW] entries of the wave-private lists
     Slot4* sd = reinterpret_cast<Slot4*>(reinterpret_cast<char*>(thr1) + 32 + G * NW * 4);
-#ifdef CIS_S4_SHARED_LISTS  // short chunks with one list per query and an LDS atomic per row: 0.176 against 0.172 ms on C2
-    constexpr bool WLISTS = LCAPT > 504;
-#else
-    constexpr bool WLISTS = true;  // every wave appends to its own quarter of a query's list (no LDS atomic in the loop)
-#endif
-    constexpr int WCAP = LCAPT / NW;
+    constexpr int WCAP = LCAPT / NW;  // every wave appends to its own quarter of a query's list (no LDS atomic in the loop)
     // deferred split: 16-bit positions per wave in the list memory (PCAP_LDS of them fit), of which NRP registers' worth are used
     constexpr int PCAP_LDS = (int)(LIST_B / (NW * 2));
     constexpr int NRP = (TWO ? S4_TWO_NRP : (LCAPT > 504 ? 32 : 16)) / NW;  // registers of packed positions per lane in the second gather
@@ -1387,11 +1342,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                     // ---- sample pass: wave w computes sample rows 2w, 2w+1; an absent sample leaves 0xffff -------------------------------
                     {
                         u32x2_t dd[SPW];
-#if defined(CIS_S4_PROBE) && CIS_S4_PROBE >= 3
-                        for (int u = 0; u < SPW; ++u) { dd[u][0] = 0xffffffffu; dd[u][1] = 0xffffffffu; }  // probe: no sample pass
-#else
                         adc16_rows<M, SPW, S4_OCT>(sc, tab, rc, dd);
-#endif
 #pragma unroll
                         for (int u = 0; u < SPW; ++u) {
                             const int t = SPW * w + u;
@@ -1399,11 +1350,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
 #pragma unroll
                             for (int g = 0; g < G; ++g) {
                                 const uint32_t sg = (g & 1) ? (dd[u][g >> 1] >> 16) : (dd[u][g >> 1] & 0xffffu);
-#if defined(CIS_S4_PROBE) && CIS_S4_PROBE >= 3
-                                samp[g * (NS * 64) + t * 64 + lane] = (uint16_t)0xffffu;
-#else
                                 samp[g * (NS * 64) + t * 64 + lane] = (uint16_t)(ok ? sg : 0xffffu);
-#endif
                             }
                         }
                     }
@@ -1454,15 +1401,9 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                             const uint32_t t_ext = (g < ng) ? bound_to_thr(sh[g].ext, sh[g].inv_up) : 0u;
                             const uint32_t t = keep < t_ext ? keep : t_ext;
                             thr1[g] = (uint16_t)((g < ng) ? t + 1u : 0u);
-#if defined(CIS_S4_PROBE) && CIS_S4_PROBE == 1
-                            thr1[g] = 0;  // probe: nothing passes
-#endif
                             sh[g].tau = tau;
                             // keep < t_ext: the threshold rests on the sample (exact when every row was sampled, else to be verified)
                             sh[g].verify = (have_bound && keep < t_ext && !exact) ? 1 : 0;
-#if defined(CIS_S4_PROBE)
-                            sh[g].verify = 0;
-#endif
                         }
                     }
                 } else {
@@ -1508,11 +1449,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                                 }
                             }
                             u32x2_t dd[SPW];
-#if defined(CIS_S4_PROBE) && CIS_S4_PROBE >= 3
-                            for (int u = 0; u < SPW; ++u) { dd[u][0] = 0xffffffffu; dd[u][1] = 0xffffffffu; }  // probe: no sample pass
-#else
                             adc16_rows<M, SPW, S4_OCT, TWO>(sc, tab, rc, dd);
-#endif
 #pragma unroll
                             for (int u = 0; u < SPW; ++u) {
                                 const bool ok = srow[u] < nrows && (srow[u] * 64 + lane < len);
@@ -1576,15 +1513,9 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                             const uint32_t t_ext = (g < ng) ? bound_to_thr(sh[g].ext, sh[g].inv_up) : 0u;
                             const uint32_t t = keep < t_ext ? keep : t_ext;
                             thr1[g] = (uint16_t)((g < ng) ? t + 1u : 0u);
-#if defined(CIS_S4_PROBE) && CIS_S4_PROBE == 1
-                            thr1[g] = 0;  // probe: nothing passes
-#endif
                             sh[g].tau = tau;
                             // keep < t_ext: the threshold rests on the sample (valid by itself when every row was sampled, else to be verified)
                             sh[g].verify = (have_bound && keep < t_ext && !all) ? 1 : 0;
-#if defined(CIS_S4_PROBE)
-                            sh[g].verify = 0;
-#endif
                         }
                     }
                 }
@@ -1597,11 +1528,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                     tpk[0] = (uint32_t)tp64; tpk[1] = (uint32_t)(tp64 >> 32);
                     const uint32_t s01 = (uint32_t)__builtin_amdgcn_readfirstlane((int)tpk[0]);
                     const uint32_t s23 = (uint32_t)__builtin_amdgcn_readfirstlane((int)tpk[1]);
-#if defined(CIS_S4_PROBE) && CIS_S4_PROBE >= 2
-                    const int nit = 0;  // probe: no main pass
-#else
                     const int nit = (len + 64 * U - 1) / (64 * U);
-#endif
                     // code rows travel PF iterations of this wave ahead of their use (a ring of PF register sets, the loop unrolled PF
                     // times so that the sets are static): one iteration ahead left the wave waiting at the end of most iterations --
                     // an iteration is ~100 instructions, a code row comes from L2 / Infinity Cache / HBM
@@ -1618,7 +1545,6 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                     int wcur[G];
 #pragma unroll
                     for (int g = 0; g < G; ++g) wcur[g] = 0;
-#if CIS_S4_DEFER
                     // Deferred split (round 4).  ~94 % of the rows of a long chunk carry a lane that passes for SOME query (four queries x 64
                     // lanes against a threshold that lets ~1 % through), and the per-query ballots / prefix counts / stores of such a row cost
                     // about as many instructions as its gathers (profiles/r03zz_c4_sq_pmc.csv: 1.8x the bare loop).  The loop now only
@@ -1627,7 +1553,6 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                     // in LDS), where the per-query split runs on 64 passing lanes per row instead of one or two.
                     uint16_t* plist = reinterpret_cast<uint16_t*>(lists) + (size_t)w * PCAP_LDS;
                     int pcur = 0;
-#endif
                     for (int iter0 = w; iter0 < nit; iter0 += NW * PF) {
 #pragma unroll
                       for (int k = 0; k < PF; ++k) {
@@ -1646,7 +1571,6 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                         for (int u = 0; u < U; ++u) {
                             const uint32_t xx = pk_subsat_u16(tpk[0], dd[u][0]) | pk_subsat_u16(tpk[1], dd[u][1]);
                             const int n = len - base - u * 64;
-#if CIS_S4_DEFER
                             if constexpr (TWO) {
                                 // The chunk's end as a lane compare: the passing lanes are ONE condition mask, which is the ballot and the
                                 // append's predicate (the scalar mask below is built with eight scalar instructions per row and tested by
@@ -1659,171 +1583,98 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                                 pcur += __popcll(am);
                                 continue;
                             }
-#endif
                             unsigned long long am = __ballot(xx != 0u);
                             if (n < 64) am &= n <= 0 ? 0ull : ((1ull << n) - 1ull);
                             if (am == 0ull) continue;  // scalar branch
-#if CIS_S4_DEFER
-                            if constexpr (WLISTS) {
-                                const int idx = __builtin_amdgcn_mbcnt_hi((unsigned)(am >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)am, pcur));
-                                if (((am >> lane) & 1ull) && idx < PCAP) plist[idx] = (uint16_t)(base + u * 64 + lane);
-                                pcur += __popcll(am);
-                                continue;
-                            }
-#endif
-                            if constexpr (WLISTS) {
-#ifdef CIS_S4_SCALAR_APPEND  // measured on C4: 0.341 ms against 0.307 ms for the ballot form below (the scalar chain serialises)
-                                // A row that gets here carries one passing lane as a rule (the threshold lets ~1 % through): the lanes
-                                // are taken one by one on the scalar unit -- two readlanes, four scalar compares, a uniform LDS store per
-                                // pass -- instead of four ballots and prefix counts over the whole wave.
-                                while (am != 0ull) {
-                                    const int l = __builtin_ctzll(am);
-                                    am &= am - 1ull;
-                                    const uint32_t d0 = (uint32_t)__builtin_amdgcn_readlane((int)dd[u][0], l);
-                                    const uint32_t d1 = (uint32_t)__builtin_amdgcn_readlane((int)dd[u][1], l);
-                                    const uint32_t pos = (uint32_t)(base + u * 64 + l);
-#pragma unroll
-                                    for (int g = 0; g < G; ++g) {
-                                        const uint32_t dw = (g >> 1) ? d1 : d0;
-                                        const uint32_t sg = (g & 1) ? (dw >> 16) : (dw & 0xffffu);
-                                        const uint32_t t1 = (g & 1) ? ((g >> 1) ? s23 >> 16 : s01 >> 16) : ((g >> 1) ? s23 & 0xffffu : s01 & 0xffffu);
-                                        if (sg < t1) {  // scalar
-                                            if (wcur[g] < WCAP) lists[(g * NW + w) * WCAP + wcur[g]] = (sg << 16) | pos;  // every lane stores the same word
-                                            wcur[g] += 1;
-                                        }
-                                    }
-                                }
-#else
-#pragma unroll
-                                for (int g = 0; g < G; ++g) {
-                                    const uint32_t sg = (g & 1) ? (dd[u][g >> 1] >> 16) : (dd[u][g >> 1] & 0xffffu);
-                                    const uint32_t t1 = (g & 1) ? ((g >> 1) ? s23 >> 16 : s01 >> 16) : ((g >> 1) ? s23 & 0xffffu : s01 & 0xffffu);
-                                    const unsigned long long mg = __ballot(sg < t1) & am;
-                                    if (mg == 0ull) continue;
-                                    const int idx = __builtin_amdgcn_mbcnt_hi((unsigned)(mg >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mg, wcur[g]));
-                                    if (((mg >> lane) & 1ull) && idx < WCAP) lists[(g * NW + w) * WCAP + idx] = (sg << 16) | (uint32_t)(base + u * 64 + lane);
-                                    wcur[g] += __popcll(mg);
-                                }
-#endif
-                                continue;
-                            }
-                            unsigned long long m[G];
-                            int mine = 0;  // lane g: the places query g needs
-#pragma unroll
-                            for (int g = 0; g < G; ++g) {
-                                const uint32_t sg = (g & 1) ? (dd[u][g >> 1] >> 16) : (dd[u][g >> 1] & 0xffffu);
-                                const uint32_t t1 = (g & 1) ? ((g >> 1) ? s23 >> 16 : s01 >> 16) : ((g >> 1) ? s23 & 0xffffu : s01 & 0xffffu);
-                                m[g] = __ballot(sg < t1) & am;
-                                mine = (lane == g) ? __popcll(m[g]) : mine;
-                            }
-                            int got = 0;
-                            if (lane < G) got = atomicAdd(&s_cnt[lane], mine);  // one LDS atomic reserves the places of all four queries
-#pragma unroll
-                            for (int g = 0; g < G; ++g) {
-                                if (m[g] == 0ull) continue;
-                                const int b0 = __builtin_amdgcn_readlane(got, g);
-                                const uint32_t sg = (g & 1) ? (dd[u][g >> 1] >> 16) : (dd[u][g >> 1] & 0xffffu);
-                                const int idx = __builtin_amdgcn_mbcnt_hi((unsigned)(m[g] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m[g], b0));
-                                if (((m[g] >> lane) & 1ull) && idx < LCAP) lists[g * LCAP + idx] = (sg << 16) | (uint32_t)(base + u * 64 + lane);
-                            }
+                            const int idx = __builtin_amdgcn_mbcnt_hi((unsigned)(am >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)am, pcur));
+                            if (((am >> lane) & 1ull) && idx < PCAP) plist[idx] = (uint16_t)(base + u * 64 + lane);
+                            pcur += __popcll(am);
                         }
                       }
                     }
                     S3_CTR(13, S3_CLK() - c0);
-#if CIS_S4_DEFER
-                    if constexpr (WLISTS) {
-                        // the recorded positions move to registers (two per register), then the list memory becomes the per-query lists
-                        const bool pover = pcur > PCAP;  // more passing candidates than the position list holds: the slot falls back
-                        const int pn = pover ? 0 : pcur;
-                        // (all NRP reads are in flight at once: the first register is waited for alone, its rows are requested in front of the
-                        // barrier, whose lgkmcnt(0) is the wait of the rest; registers past pn hold stale positions of the wave's own list
-                        // memory, which on_of() below masks)
-                        static_assert(NRP * 128 <= PCAP_LDS, "the NRP registers are read from the wave's own position list");
-                        uint32_t pp[NRP];
+                    // the recorded positions move to registers (two per register), then the list memory becomes the per-query lists
+                    const bool pover = pcur > PCAP;  // more passing candidates than the position list holds: the slot falls back
+                    const int pn = pover ? 0 : pcur;
+                    // (all NRP reads are in flight at once: the first register is waited for alone, its rows are requested in front of the
+                    // barrier, whose lgkmcnt(0) is the wait of the rest; registers past pn hold stale positions of the wave's own list
+                    // memory, which on_of() below masks)
+                    static_assert(NRP * 128 <= PCAP_LDS, "the NRP registers are read from the wave's own position list");
+                    uint32_t pp[NRP];
 #pragma unroll
-                        for (int r = 0; r < NRP; ++r) pp[r] = lds_ld(reinterpret_cast<const uint32_t*>(plist) + r * 64 + lane);
-                        // The second gather takes the registers in turn, two iterations each: iteration it = half (it & 1) of register it >> 1.
-                        // pp[] is ROTATED by one register per trip, so the loop stays rolled and still indexes pp[] by constants only (a
-                        // run-time index put the array in private memory; unrolled sixteen times the loop's many uses of the rotation
-                        // constants drew the M = 16 form's spill reloads into the main pass).  The code rows travel in a ring of two: the row
-                        // of iteration it + 1 is in flight during the gathers of iteration it, a row's wait is vmcnt(1), not vmcnt(0), and the
-                        // first two rows travel across the barrier.  The requests are unconditional -- lanes and iterations past pn ask for
-                        // position `len`, where the descriptor returns zeros without a memory access -- so that every path has the same
-                        // number of loads in flight.  (M = 16 at three waves per SIMD: a spill reload in the preheader still costs that form a
-                        // vmcnt(0) per trip, profiles/scan4_phases_ab.txt.)
-                        auto on_of = [&](int it) -> bool { return 2 * (((it >> 1) * 64) + lane) + (it & 1) < pn; };
-                        CodeWords<M> cw[2];
-                        cw[0] = load_code_buf<M>(rs, on_of(0) ? (int)(pp[0] & 0xffffu) : len);
-                        cw[1] = load_code_buf<M>(rs, on_of(1) ? (int)(pp[0] >> 16) : len);
-                        lds_barrier();  // B3b: every wave holds its positions; nobody still writes a position list
-                        // TWO: B3b is also behind the last gather of every wave's main pass, so copy 1 ends here -- its slots take the
-                        // per-query lists, and this gather reads copy 0 alone.  Its constants are derived here (the mask is laundered: hoisted,
-                        // they would be eight more registers across the main pass)
-                        RotConsts<M> rc0;
-                        if constexpr (TWO) {
-                            rc0 = rc;
-                            uint32_t keep0 = ~4u;
-                            asm volatile("" : "+v"(keep0));
+                    for (int r = 0; r < NRP; ++r) pp[r] = lds_ld(reinterpret_cast<const uint32_t*>(plist) + r * 64 + lane);
+                    // The second gather takes the registers in turn, two iterations each: iteration it = half (it & 1) of register it >> 1.
+                    // pp[] is ROTATED by one register per trip, so the loop stays rolled and still indexes pp[] by constants only (a
+                    // run-time index put the array in private memory; unrolled sixteen times the loop's many uses of the rotation
+                    // constants drew the M = 16 form's spill reloads into the main pass).  The code rows travel in a ring of two: the row
+                    // of iteration it + 1 is in flight during the gathers of iteration it, a row's wait is vmcnt(1), not vmcnt(0), and the
+                    // first two rows travel across the barrier.  The requests are unconditional -- lanes and iterations past pn ask for
+                    // position `len`, where the descriptor returns zeros without a memory access -- so that every path has the same
+                    // number of loads in flight.  (M = 16 at three waves per SIMD: a spill reload in the preheader still costs that form a
+                    // vmcnt(0) per trip, profiles/scan4_phases_ab.txt.)
+                    auto on_of = [&](int it) -> bool { return 2 * (((it >> 1) * 64) + lane) + (it & 1) < pn; };
+                    CodeWords<M> cw[2];
+                    cw[0] = load_code_buf<M>(rs, on_of(0) ? (int)(pp[0] & 0xffffu) : len);
+                    cw[1] = load_code_buf<M>(rs, on_of(1) ? (int)(pp[0] >> 16) : len);
+                    lds_barrier();  // B3b: every wave holds its positions; nobody still writes a position list
+                    // TWO: B3b is also behind the last gather of every wave's main pass, so copy 1 ends here -- its slots take the
+                    // per-query lists, and this gather reads copy 0 alone.  Its constants are derived here (the mask is laundered: hoisted,
+                    // they would be eight more registers across the main pass)
+                    RotConsts<M> rc0;
+                    if constexpr (TWO) {
+                        rc0 = rc;
+                        uint32_t keep0 = ~4u;
+                        asm volatile("" : "+v"(keep0));
 #pragma unroll
-                            for (int t = 0; t < M; ++t) rc0.cj[t] = rc.cj[t] & keep0;
-                        }
-                        uint32_t* grow[G];  // GLISTS: the items' survivor rows as 32-bit list memory (S 8-byte entries = 2 S list entries >= LCAP)
-#pragma unroll
-                        for (int g = 0; g < G; ++g)
-                            grow[g] = reinterpret_cast<uint32_t*>(item_surv + (int64_t)__builtin_amdgcn_readfirstlane(d->item[g]) * S);
-                        if (pn > 0) {
-                            const int nreg = (pn + 127) >> 7;  // registers that hold a position
-#pragma unroll 1
-                            for (int r = 0; r < nreg; ++r) {
-                              const uint32_t cur = pp[0];
-#pragma unroll
-                              for (int k = 0; k + 1 < NRP; ++k) pp[k] = pp[k + 1];
-                              pp[NRP - 1] = 0u;
-#pragma unroll
-                              for (int h = 0; h < 2; ++h) {
-                                const int it = 2 * r + h;
-                                const uint32_t pos = h ? (cur >> 16) : (cur & 0xffffu);
-                                CodeWords<M> cc[1];
-                                cc[0] = cw[h];
-                                u32x2_t d1[1];
-                                if constexpr (TWO) adc16_rows<M, 1, S4_OCT, true>(cc, tab, rc0, d1);
-                                else adc16_rows<M, 1, S4_OCT>(cc, tab, rc, d1);
-                                // (requested once the row's words have been consumed, as in the main pass: the load targets the same registers;
-                                // requested earlier it lands in new ones, and the copy at the loop's end waits for it with vmcnt(0))
-                                cw[h] = load_code_buf<M>(rs, on_of(it + 2) ? (int)(h ? (pp[0] >> 16) : (pp[0] & 0xffffu)) : len);
-                                const unsigned long long am2 = __ballot(on_of(it));
-#pragma unroll
-                                for (int g = 0; g < G; ++g) {
-                                    const uint32_t sg = (g & 1) ? (d1[0][g >> 1] >> 16) : (d1[0][g >> 1] & 0xffffu);
-                                    const uint32_t t1 = (g & 1) ? ((g >> 1) ? s23 >> 16 : s01 >> 16) : ((g >> 1) ? s23 & 0xffffu : s01 & 0xffffu);
-                                    const unsigned long long mg = __ballot(sg < t1) & am2;
-                                    if (mg == 0ull) continue;
-                                    const int idx = __builtin_amdgcn_mbcnt_hi((unsigned)(mg >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mg, wcur[g]));
-                                    if (((mg >> lane) & 1ull) && idx < WCAP) {
-                                        if constexpr (GLISTS) grow[g][w * WCAP + idx] = (sg << 16) | pos;
-                                        else if constexpr (TWO) *list_at((g * NW + w) * WCAP + idx) = (sg << 16) | pos;
-                                        else lists[(g * NW + w) * WCAP + idx] = (sg << 16) | pos;
-                                    }
-                                    wcur[g] += __popcll(mg);
-                                }
-                              }
-                            }
-                        }
-                        if (pover) wcur[0] = WCAP + 1;  // reported like an overflowing quarter (the verification below sends the slot to the fall-back)
+                        for (int t = 0; t < M; ++t) rc0.cj[t] = rc.cj[t] & keep0;
                     }
-#endif
-                    if constexpr (WLISTS) {
-                        if (lane < G) {
-                            int c = wcur[0];
+                    if (pn > 0) {
+                        const int nreg = (pn + 127) >> 7;  // registers that hold a position
+#pragma unroll 1
+                        for (int r = 0; r < nreg; ++r) {
+                          const uint32_t cur = pp[0];
 #pragma unroll
-                            for (int g = 1; g < G; ++g) c = (lane == g) ? wcur[g] : c;
-                            wcnt[lane * NW + w] = c;
+                          for (int k = 0; k + 1 < NRP; ++k) pp[k] = pp[k + 1];
+                          pp[NRP - 1] = 0u;
+#pragma unroll
+                          for (int h = 0; h < 2; ++h) {
+                            const int it = 2 * r + h;
+                            const uint32_t pos = h ? (cur >> 16) : (cur & 0xffffu);
+                            CodeWords<M> cc[1];
+                            cc[0] = cw[h];
+                            u32x2_t d1[1];
+                            if constexpr (TWO) adc16_rows<M, 1, S4_OCT, true>(cc, tab, rc0, d1);
+                            else adc16_rows<M, 1, S4_OCT>(cc, tab, rc, d1);
+                            // (requested once the row's words have been consumed, as in the main pass: the load targets the same registers;
+                            // requested earlier it lands in new ones, and the copy at the loop's end waits for it with vmcnt(0))
+                            cw[h] = load_code_buf<M>(rs, on_of(it + 2) ? (int)(h ? (pp[0] >> 16) : (pp[0] & 0xffffu)) : len);
+                            const unsigned long long am2 = __ballot(on_of(it));
+#pragma unroll
+                            for (int g = 0; g < G; ++g) {
+                                const uint32_t sg = (g & 1) ? (d1[0][g >> 1] >> 16) : (d1[0][g >> 1] & 0xffffu);
+                                const uint32_t t1 = (g & 1) ? ((g >> 1) ? s23 >> 16 : s01 >> 16) : ((g >> 1) ? s23 & 0xffffu : s01 & 0xffffu);
+                                const unsigned long long mg = __ballot(sg < t1) & am2;
+                                if (mg == 0ull) continue;
+                                const int idx = __builtin_amdgcn_mbcnt_hi((unsigned)(mg >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mg, wcur[g]));
+                                if (((mg >> lane) & 1ull) && idx < WCAP) {
+                                    if constexpr (TWO) *list_at((g * NW + w) * WCAP + idx) = (sg << 16) | pos;
+                                    else lists[(g * NW + w) * WCAP + idx] = (sg << 16) | pos;
+                                }
+                                wcur[g] += __popcll(mg);
+                            }
+                          }
                         }
+                    }
+                    if (pover) wcur[0] = WCAP + 1;  // reported like an overflowing quarter (the verification below sends the slot to the fall-back)
+                    if (lane < G) {
+                        int c = wcur[0];
+#pragma unroll
+                        for (int g = 1; g < G; ++g) c = (lane == g) ? wcur[g] : c;
+                        wcnt[lane * NW + w] = c;
                     }
                 }
                 S3_CTR(12, S3_CLK() - c0);
-                if constexpr (GLISTS) __syncthreads();  // B4: lists complete -- in global memory: the barrier also waits for the stores (vmcnt)
-                else lds_barrier();  // B4: lists complete
+                lds_barrier();  // B4: lists complete
                 S3_CTR(5, S3_CLK() - c0);
                 // ---- verification + cut + write-out: wave g serves query g ------------------------------------------------------------
                 bool bad = false;
@@ -1833,16 +1684,11 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                     int wtot[NW];
                     int lane_v = lane;  // laundered: the verification's per-lane offsets are not to live across the hot loop
                     asm volatile("" : "+v"(lane_v));
-                    if constexpr (WLISTS) {
 #pragma unroll
-                        for (int r = 0; r < NW; ++r) {
-                            wtot[r] = wcnt[g * NW + r];
-                            bad = bad || wtot[r] > WCAP;  // a wave's quarter overflowed
-                            tot += wtot[r];
-                        }
-                    } else {
-                        tot = s_cnt[g];
-                        bad = tot > LCAP;  // the list overflowed (a crowd of equal sums, or a threshold far too loose)
+                    for (int r = 0; r < NW; ++r) {
+                        wtot[r] = wcnt[g * NW + r];
+                        bad = bad || wtot[r] > WCAP;  // a wave's quarter overflowed
+                        tot += wtot[r];
                     }
                     if (bad && lane_v == 0) atomicAdd(&dbg[2], 1);
                     if (!bad) {
@@ -1850,21 +1696,11 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                         bool val[NRV];
 #pragma unroll
                         for (int r = 0; r < NRV; ++r) {
-                            if constexpr (WLISTS) {
-                                constexpr int RW = NRV / NW;  // registers per wave quarter
-                                const int e = (r % RW) * 64 + lane_v;
-                                val[r] = e < wtot[r / RW];
-                                if constexpr (GLISTS) {  // written by the other waves of this workgroup: read past the L1 (device scope)
-                                    const uint32_t* gr = reinterpret_cast<const uint32_t*>(item_surv + (int64_t)__builtin_amdgcn_readfirstlane(d->item[g]) * S);
-                                    ent[r] = val[r] ? __hip_atomic_load(gr + (r / RW) * WCAP + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0xffffffffu;
-                                } else {
-                                    if constexpr (TWO) ent[r] = val[r] ? *list_at((g * NW + r / RW) * WCAP + e) : 0xffffffffu;
-                                    else ent[r] = val[r] ? lists[(g * NW + r / RW) * WCAP + e] : 0xffffffffu;
-                                }
-                            } else {
-                                val[r] = r * 64 + lane_v < tot;
-                                ent[r] = val[r] ? lists[g * LCAP + r * 64 + lane_v] : 0xffffffffu;
-                            }
+                            constexpr int RW = NRV / NW;  // registers per wave quarter
+                            const int e = (r % RW) * 64 + lane_v;
+                            val[r] = e < wtot[r / RW];
+                            if constexpr (TWO) ent[r] = val[r] ? *list_at((g * NW + r / RW) * WCAP + e) : 0xffffffffu;
+                            else ent[r] = val[r] ? lists[(g * NW + r / RW) * WCAP + e] : 0xffffffffu;
                         }
                         const uint32_t tau = sh[g].tau;
                         if (sh[g].verify) {
@@ -1972,436 +1808,6 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
     S3_CTR(10, 1);
 }
 
-// ---- k_adc_scan5 (round 5): ONE threshold per query for the whole batch, eight queries per slot ------------------------------
-// k_adc_scan4 spends 46 % of a slot in serial per-query phases (sample, threshold bisection, second gather, verification: one wave per
-// query while the others idle) and issues 2.3 x the instructions of its gather loop.  The streaming route
-// (lopq_stream.hip) showed the alternative: take the threshold out of the slot.
-//   1. k_adc_scan5<SAMPLE>  every slot stages its tables and gathers one row in `ss`; a lane folds the smallest upper bound
-//                           (sum + M) * ub it saw into one of B buckets of its query (atomicMin on float bits);
-//   2. k_scan5_tau          tau[q] = the k-th smallest bucket minimum, k = P x sampled fraction: about P (~2.4 x limit) candidates of
-//                           the query lie under it (count(buckets <= v) <= count(samples <= v): never tighter than the sample's own);
-//   3. k_adc_scan5          the slot's only phases are staging and gathering: thresholds thr_g = floor(tau[q_g] * qinv_g (1 + 2^-22)) + 1
-//                           -- a candidate with d <= tau has sum <= d qinv (1 + 2^-23) < thr (truncated, saturating entries only round
-//                           sums DOWN) -- the loop records the positions where ANY of the eight queries passes (one packed compare,
-//                           one ballot), a second gather of those ~5 % splits them per query, counts, reserves room in the items'
-//                           survivor rows with one atomic per (wave, query) and writes (sum << 32 | position): k_merge_survivors'
-//                           input.  It also counts, per query, the listed candidates whose UPPER bound (sum + M) ub is <= tau;
-//   4. k_scan5_check        the proof: that count >= min(limit, candidates) -- then the limit-th smallest upper bound is <= tau, every
-//                           candidate of the true top `limit` has d <= tau and was listed (ties included) -- and no row or position list
-//                           overflowed.  Slots with a query that fails go to the fall-back list k_adc_scan3 works off (as k_adc_scan4's).
-// Eight queries per slot (ds_read_b128: 8 x 16-bit entries; four packed adds per gather): a code row is fetched, rotated and its
-// bytes extracted once for eight queries instead of four, and a 16-lane read group meets two lanes per sub-quantizer instead of four.
-static const int S5G = 8;
-typedef unsigned int u32x4v __attribute__((ext_vector_type(4)));
-
-template <int M, int OCT>
-__device__ __forceinline__ void adc16x8_issue(const uint32_t (&D)[(M + 3) / 4], int o, const char* __restrict__ tab, const RotConsts<M>& rc,
-                                              u32x4v (&f)[OCT]) {
-    constexpr int SH = ((M == 4) ? 2 : (M == 8 ? 3 : 4)) + 4;  // log2(M * 16 bytes): one k-row of the table
-#pragma unroll
-    for (int i = 0; i < OCT; ++i) {
-        const int t = o * OCT + i;
-        const uint32_t k = __builtin_amdgcn_ubfe(D[t >> 2], rc.sh[t & 3], 8);
-        f[i] = *reinterpret_cast<const u32x4v*>(tab + ((k << SH) | (rc.cj[t] << 2)));
-    }
-}
-
-template <int OCT>
-__device__ __forceinline__ u32x4v adc16x8_sum(const u32x4v (&f)[OCT]) {
-    u32x4v a = f[0];
-#pragma unroll
-    for (int i = 1; i < OCT; ++i) {
-        a[0] = pk_add_u16(a[0], f[i][0]);
-        a[1] = pk_add_u16(a[1], f[i][1]);
-        a[2] = pk_add_u16(a[2], f[i][2]);
-        a[3] = pk_add_u16(a[3], f[i][3]);
-    }
-    return a;
-}
-
-// sums of UU rows of 64 candidates for eight queries (software pipelined like adc16_rows)
-template <int M, int UU, int OCT>
-__device__ __forceinline__ void adc16x8_rows(const CodeWords<M> (&cur)[UU], const char* __restrict__ tab, const RotConsts<M>& rc, u32x4v (&d)[UU]) {
-    constexpr int NU = M / OCT;
-    u32x4v fbuf[2][OCT];
-    uint32_t D[2][(M + 3) / 4];
-    rot_words<M>(cur[0], rc, D[0]);
-    adc16x8_issue<M, OCT>(D[0], 0, tab, rc, fbuf[0]);
-#pragma unroll
-    for (int q = 0; q < UU * NU; ++q) {
-        const int u = q / NU, o = q % NU;
-        if (q + 1 < UU * NU) {
-            const int u1 = (q + 1) / NU, o1 = (q + 1) % NU;
-            if (o1 == 0) rot_words<M>(cur[u1], rc, D[u1 & 1]);
-            adc16x8_issue<M, OCT>(D[u1 & 1], o1, tab, rc, fbuf[(q + 1) & 1]);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        const u32x4v part = adc16x8_sum<OCT>(fbuf[q & 1]);
-        if (o == 0) {
-            d[u] = part;
-        } else {
-#pragma unroll
-            for (int x = 0; x < 4; ++x) d[u][x] = pk_add_u16(d[u][x], part[x]);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
-struct Slot5 {
-    int item[S5G], tab0[S5G], tab1[S5G], q[S5G];
-    float qinv[S5G];
-    uint32_t thr1[S5G], ok1[S5G];  // keep sum < thr1; sum < ok1: the candidate's upper bound is <= tau
-    float ubf[S5G];                // (1 + 2^-21) / qinv, rounded up
-    int start_lo, start_hi, len, ng, same;
-};
-
-static __device__ __forceinline__ uint32_t s5_sum_of(const u32x4v& d, int g) {  // query g's 16-bit sum
-    const uint32_t w = d[g >> 1];
-    return (g & 1) ? (w >> 16) : (w & 0xffffu);
-}
-
-static const int S5_PCAP = 1024;  // recorded positions per wave and slot
-
-static size_t scan5_lds(int M, int K) { return (size_t)K * M * S5G * 2 + (size_t)4 * S5_PCAP * 2 + sizeof(Slot5) + 64; }
-
-template <int M, bool SAMPLE, int WPE>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void k_adc_scan5(
-    const WorkItem* __restrict__ items, const TabDesc* __restrict__ tabs, const int* __restrict__ slots, const int* __restrict__ n_slots_ptr,
-    const float* __restrict__ T32 /* null: converted from T */, const double* __restrict__ T, const uint8_t* __restrict__ codes, int K, int S,
-    const float* __restrict__ tau, uint32_t* __restrict__ bmin, int B, int* __restrict__ nsamp, int ss,
-    uint64_t* __restrict__ item_surv, int* __restrict__ item_n, float* __restrict__ item_slack, int* __restrict__ cnt_ok, int* __restrict__ ovf) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int G = S5G, NW = 4, nf = M / 2, U = 2, PF = 2, OCT = 4;
-    constexpr uint32_t CAP = 65535u / M;
-    char* tab = smem;                                                                  // [K][M][G] uint16
-    uint16_t* plist_all = reinterpret_cast<uint16_t*>(smem + (size_t)K * M * G * 2);    // [NW][S5_PCAP]
-    Slot5* sd = reinterpret_cast<Slot5*>(reinterpret_cast<char*>(plist_all) + (size_t)NW * S5_PCAP * 2);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int total = n_slots_ptr[0];
-    const int xcd = blockIdx.x & 7, lb = blockIdx.x >> 3, LW = gridDim.x >> 3;
-    const RotConsts<M> rc = make_rot<M>(lane);
-    const int nvec = (nf * K) >> 2;  // float4 per half table
-    for (int kk = 0;; ++kk) {
-        // the workgroup's kk-th slot: runs of 32 consecutive slots (a few cells) stay on one XCD, as in k_adc_scan4
-        const int li = lb + kk * LW;
-        const int j = (((li >> 5) * 8 + xcd) << 5) | (li & 31);
-        if ((li >> 5) * 256 >= total + 256) break;   // past every run (uniform)
-        if (j >= total) continue;
-        __syncthreads();  // the previous slot's tables, lists and descriptor are dead
-        if (tid < G) {    // lane g resolves item g of the slot
-            const int g = tid;
-            int idx = slots[j * G + g];
-            const int idx0 = slots[j * G];
-            const bool on = idx >= 0;
-            idx = on ? idx : idx0;
-            const WorkItem it = items[idx];
-            const WorkItem it0 = items[idx0];
-            float mxT = fmaxf(__int_as_float(tabs[it.tab0].pad), __int_as_float(tabs[it.tab1].pad));
-            mxT = fmaxf(mxT, 1e-30f);
-            float qi = ((float)CAP / mxT) * (1.0f - 9.5367431640625e-7f);  // as k_adc_scan4: T32 * qinv stays below cap
-            qi = (mxT < 3.0e38f) ? qi : 0.0f;
-            qi = (qi < 3.0e38f) ? qi : 3.0e38f;
-            sd->item[g] = idx; sd->tab0[g] = it.tab0; sd->tab1[g] = it.tab1; sd->q[g] = on ? it.q : -1;
-            sd->qinv[g] = qi;
-            const double inv_up = (double)qi * (1.0 + 2.384185791015625e-7);
-            const double ub = qi > 0.0f ? (1.0 + 4.76837158203125e-7) / (double)qi : __longlong_as_double(0x7ff0000000000000LL);
-            sd->ubf[g] = __double2float_ru(ub);
-            uint32_t t1 = 0u, o1 = 0u;
-            if (on && !SAMPLE) {
-                const float tq = tau[it.q];
-                if (!(tq < 3.0e38f)) { t1 = 65535u; o1 = 65535u; }   // no threshold: everything is listed (and counts)
-                else {
-                    const double x = (double)tq * inv_up;
-                    t1 = x >= 65533.0 ? 65535u : (uint32_t)x + 2u;    // keep sum <= floor(x) + 1 (bound_to_thr), as sum < t1
-                    const double y = (double)tq / ((double)sd->ubf[g]) - (double)M - 1.0;  // (sum + M) ubf <= tau  <=  sum <= y
-                    o1 = y <= 0.0 ? 0u : (y >= 65533.0 ? 65535u : (uint32_t)y + 1u);      // counted: sum < o1
-                }
-            }
-            sd->thr1[g] = t1; sd->ok1[g] = o1;
-            if (on && !SAMPLE) {
-                item_slack[2 * (int64_t)idx + 0] = __double2float_ru(ub * ((double)M + 0.1));
-                item_slack[2 * (int64_t)idx + 1] = __double2float_ru(ub);
-            }
-            // all items of a slot are the SAME chunk of one cell (the slot key); a slot that mixes chunks (a cell of more than 16
-            // chunks) is not scanned here: its queries are flagged and take the fall-back
-            const bool same = it.start == it0.start && it.len == it0.len;
-            const unsigned long long sm = __ballot(same || !on);
-            if (g == 0) {
-                sd->start_lo = (int)(uint32_t)it0.start; sd->start_hi = (int)(it0.start >> 32); sd->len = it0.len;
-                sd->same = ((sm & 0xffull) == 0xffull) ? 1 : 0;
-            }
-            const unsigned long long om = __ballot(on);
-            if (g == 0) sd->ng = 64 - __builtin_clzll((om & 0xffull) | 0ull) ;
-        }
-        __syncthreads();
-        const int ng = __builtin_amdgcn_readfirstlane(sd->ng);
-        const int len = __builtin_amdgcn_readfirstlane(sd->len);
-        const int64_t start = ((int64_t)__builtin_amdgcn_readfirstlane(sd->start_hi) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane(sd->start_lo);
-        if (!__builtin_amdgcn_readfirstlane(sd->same)) {
-            if (!SAMPLE && tid < ng && sd->q[tid] >= 0) ovf[sd->q[tid]] = 1;
-            continue;
-        }
-        // ---- tables -> 16-bit entries -> LDS: thread -> (sub-quantizer j = vt % nf, four consecutive k), half tables one after the other
-        {
-            float qinv[G];
-#pragma unroll
-            for (int g = 0; g < G; ++g) qinv[g] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, sd->qinv[g])));
-            int tid_st = tid;
-            asm volatile("" : "+v"(tid_st));
-            for (int vt = tid_st; vt < nvec; vt += 256) {
-                const int jq = vt & (nf - 1), kq = vt / nf, k0 = 4 * kq;
-                const int vidx = jq * (K >> 2) + kq;
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) {
-                    float4 pv[G];
-#pragma unroll
-                    for (int g = 0; g < G; ++g) {
-                        const int tb = __builtin_amdgcn_readfirstlane(s2 ? sd->tab1[g] : sd->tab0[g]);
-                        pv[g] = tab_f4(T32, T, tb, nf * K, vidx);
-                    }
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        uint32_t qv[G];
-#pragma unroll
-                        for (int g = 0; g < G; ++g) {
-                            const float x = c == 0 ? pv[g].x : (c == 1 ? pv[g].y : (c == 2 ? pv[g].z : pv[g].w));
-                            qv[g] = (g < ng) ? (uint32_t)(x * qinv[g]) : CAP;  // truncation: a lower bound of x * qinv
-                            qv[g] = qv[g] > CAP ? CAP : qv[g];
-                        }
-                        u32x4v pk;
-                        pk[0] = qv[0] | (qv[1] << 16); pk[1] = qv[2] | (qv[3] << 16); pk[2] = qv[4] | (qv[5] << 16); pk[3] = qv[6] | (qv[7] << 16);
-                        *reinterpret_cast<u32x4v*>(tab + ((size_t)((k0 + c) * M + s2 * nf + jq) << 4)) = pk;
-                    }
-                }
-            }
-        }
-        __amdgpu_buffer_rsrc_t rs;
-        {
-            const uint64_t cbase = (uint64_t)(uintptr_t)(codes + start * M);
-            const uint32_t blo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)cbase);
-            const uint32_t bhi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(cbase >> 32));
-            rs = __builtin_amdgcn_make_buffer_rsrc((void*)(uintptr_t)(((uint64_t)bhi << 32) | blo), 0, len * M, 0x00020000);
-        }
-        const int nrows = (len + 63) >> 6;
-        if constexpr (SAMPLE) {
-            // every ss-th row (all rows of a chunk shorter than that: at least one row per wave where there is one)
-            lds_barrier();
-            const int step = nrows >= 4 * ss ? ss : 1;
-            u32x4v bm;
-            bm[0] = bm[1] = bm[2] = bm[3] = 0xffffffffu;
-            int nval = 0;
-            for (int r0 = w * step; r0 < nrows; r0 += 4 * step * U) {
-                CodeWords<M> sc[U];
-#pragma unroll
-                for (int u = 0; u < U; ++u) sc[u] = load_code_buf<M>(rs, (r0 + u * 4 * step) * 64 + lane);  // past the chunk: zeros, masked below
-                u32x4v dd[U];
-                adc16x8_rows<M, U, OCT>(sc, tab, rc, dd);
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const bool ok = (r0 + u * 4 * step) * 64 + lane < len;
-                    nval += __popcll(__ballot(ok));
-#pragma unroll
-                    for (int x = 0; x < 4; ++x) bm[x] = pk_min_u16(bm[x], ok ? dd[u][x] : 0xffffffffu);
-                }
-            }
-#pragma unroll
-            for (int g = 0; g < G; ++g) {
-                if (g < ng) {
-                    const int q = __builtin_amdgcn_readfirstlane(sd->q[g]);
-                    const uint32_t sg = s5_sum_of(bm, g);
-                    if (sg != 0xffffu) {
-                        const float ubv = (float)(sg + (uint32_t)M) * sd->ubf[g] * 1.0000002f;  // >= the candidate's exact distance
-                        atomicMin(&bmin[(int64_t)q * B + (((unsigned)j * 131u + (unsigned)tid) & (unsigned)(B - 1))], __float_as_uint(ubv));
-                    }
-                    if (lane == 0 && nval > 0) atomicAdd(&nsamp[q], nval);
-                }
-            }
-            continue;
-        } else {
-        lds_barrier();  // tables and the descriptor's thresholds visible
-        u32x4v tpk;  // the eight thresholds, packed like the sums
-#pragma unroll
-        for (int x = 0; x < 4; ++x) {
-            const uint32_t a = sd->thr1[2 * x], b = sd->thr1[2 * x + 1];
-            tpk[x] = (uint32_t)__builtin_amdgcn_readfirstlane((int)((a & 0xffffu) | (b << 16)));
-        }
-        // ---- main pass: every candidate once, the positions where ANY query passes are recorded ---------------------------------
-        uint16_t* plist = plist_all + (size_t)w * S5_PCAP;
-        int pcur = 0;
-        {
-            const int nit = (len + 64 * U - 1) / (64 * U);
-            CodeWords<M> ring[PF][U];
-#pragma unroll
-            for (int k = 0; k < PF; ++k) {
-#pragma unroll
-                for (int u = 0; u < U; ++u) ring[k][u] = load_code_buf<M>(rs, (w + k * NW) * 64 * U + u * 64 + lane);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            for (int iter0 = w; iter0 < nit; iter0 += NW * PF) {
-#pragma unroll
-                for (int k = 0; k < PF; ++k) {
-                    const int iter = iter0 + k * NW;
-                    const int base = iter * 64 * U;
-                    u32x4v dd[U];
-                    adc16x8_rows<M, U, OCT>(ring[k], tab, rc, dd);
-#pragma unroll
-                    for (int u = 0; u < U; ++u) ring[k][u] = load_code_buf<M>(rs, (iter + PF * NW) * 64 * U + u * 64 + lane);
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        const uint32_t xx = (pk_subsat_u16(tpk[0], dd[u][0]) | pk_subsat_u16(tpk[1], dd[u][1])) |
-                                            (pk_subsat_u16(tpk[2], dd[u][2]) | pk_subsat_u16(tpk[3], dd[u][3]));
-                        unsigned long long am = __ballot(xx != 0u);
-                        const int n = len - base - u * 64;
-                        if (n < 64) am &= n <= 0 ? 0ull : ((1ull << n) - 1ull);
-                        if (am == 0ull) continue;  // scalar branch
-                        const int idx = __builtin_amdgcn_mbcnt_hi((unsigned)(am >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)am, pcur));
-                        if (((am >> lane) & 1ull) && idx < S5_PCAP) plist[idx] = (uint16_t)(base + u * 64 + lane);
-                        pcur += __popcll(am);
-                    }
-                }
-            }
-        }
-        // ---- second gather of the recorded candidates: per-query split, counts, room, write-out --------------------------------------
-        const bool pover = pcur > S5_PCAP;
-        const int pn = pover ? 0 : pcur;
-        if (pover) {
-            if (lane < ng) ovf[sd->q[lane]] = 1;
-        }
-        if (pn > 0) {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's own position stores
-            const int nit2 = (pn + 63) >> 6;
-            int cnt[G], okc[G];
-#pragma unroll
-            for (int g = 0; g < G; ++g) { cnt[g] = 0; okc[g] = 0; }
-            uint32_t thr1[G], ok1[G];
-#pragma unroll
-            for (int g = 0; g < G; ++g) {
-                thr1[g] = (uint32_t)__builtin_amdgcn_readfirstlane((int)sd->thr1[g]);
-                ok1[g] = (uint32_t)__builtin_amdgcn_readfirstlane((int)sd->ok1[g]);
-            }
-            for (int it = 0; it < nit2; ++it) {   // pass A: counts
-                const bool on = it * 64 + lane < pn;
-                const uint32_t pos = on ? (uint32_t)ld16(&plist[it * 64 + lane]) : (uint32_t)len;
-                CodeWords<M> cc[1];
-                cc[0] = load_code_buf<M>(rs, (int)pos);
-                u32x4v d1[1];
-                adc16x8_rows<M, 1, OCT>(cc, tab, rc, d1);
-#pragma unroll
-                for (int g = 0; g < G; ++g) {
-                    const uint32_t sg = s5_sum_of(d1[0], g);
-                    cnt[g] += __popcll(__ballot(on && sg < thr1[g]));
-                    okc[g] += __popcll(__ballot(on && sg < ok1[g]));
-                }
-            }
-            // room in the items' survivor rows: lane g reserves for query g (one atomic per wave and query), counts the proven ones
-            int mine = cnt[0], mok = okc[0];
-#pragma unroll
-            for (int g = 1; g < G; ++g) { mine = (lane == g) ? cnt[g] : mine; mok = (lane == g) ? okc[g] : mok; }
-            int base_l = 0;
-            if (lane < ng && mine > 0) {
-                base_l = atomicAdd(&item_n[sd->item[lane]], mine);
-                if (base_l + mine > S) ovf[sd->q[lane]] = 1;
-                if (mok > 0) atomicAdd(&cnt_ok[sd->q[lane]], mok);
-            }
-            int wbase[G];
-#pragma unroll
-            for (int g = 0; g < G; ++g) wbase[g] = __builtin_amdgcn_readlane(base_l, g);
-            for (int it = 0; it < nit2; ++it) {   // pass B: the entries
-                const bool on = it * 64 + lane < pn;
-                const uint32_t pos = on ? (uint32_t)ld16(&plist[it * 64 + lane]) : (uint32_t)len;
-                CodeWords<M> cc[1];
-                cc[0] = load_code_buf<M>(rs, (int)pos);
-                u32x4v d1[1];
-                adc16x8_rows<M, 1, OCT>(cc, tab, rc, d1);
-#pragma unroll
-                for (int g = 0; g < G; ++g) {
-                    if (g >= ng) continue;  // uniform
-                    const uint32_t sg = s5_sum_of(d1[0], g);
-                    const bool pass = on && sg < thr1[g];
-                    const unsigned long long mg = __ballot(pass);
-                    if (mg == 0ull) continue;
-                    const int idx = __builtin_amdgcn_mbcnt_hi((unsigned)(mg >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mg, wbase[g]));
-                    if (pass && idx < S) item_surv[(int64_t)__builtin_amdgcn_readfirstlane(sd->item[g]) * S + idx] = ((uint64_t)sg << 32) | pos;
-                    wbase[g] += __popcll(mg);
-                }
-            }
-        }
-        }
-    }
-}
-
-// tau[q] = the k-th smallest of the query's B bucket minima (float bits), k = P x sampled fraction; +inf when the query is short or
-// the sample thin (everything is listed then).  One wave per query; also clears the query's counters for the main pass.
-template <int PER>
-__global__ __launch_bounds__(256) void k_scan5_tau(const uint32_t* __restrict__ bmin, int B, const int* __restrict__ nsamp, const PlanOut* __restrict__ plan,
-                                                   int nq, int P, float* __restrict__ tau) {
-    const int q = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (q >= nq) return;
-    uint32_t v[PER];
-    bool ok[PER];
-    uint32_t lo = 0xffffffffu, hi = 0u;
-    int fin = 0;
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-        v[i] = bmin[(int64_t)q * B + i * 64 + lane];
-        ok[i] = v[i] < 0x7f800000u;
-        lo = (ok[i] && v[i] < lo) ? v[i] : lo;
-        hi = (ok[i] && v[i] > hi) ? v[i] : hi;
-        fin += __popcll(__ballot(ok[i]));
-    }
-    const int64_t ncand = plan[q].ncand;
-    const int ns = nsamp[q];
-    float t = __uint_as_float(0x7f800000u);
-    if (ns > 0 && ncand > 2 * (int64_t)P) {
-        int k = (int)(((int64_t)P * ns + ncand - 1) / ncand);
-        k = k < 4 ? 4 : k;
-        if (k <= fin && k <= B / 2) {
-            wave_minmax_all(lo, hi);
-            t = __uint_as_float(wave_kth_bisect<PER>(v, ok, lo, hi, k));
-        }
-    }
-    if (lane == 0) tau[q] = t;
-}
-
-// the proof (see the header comment of k_adc_scan5): a thread per slot; a slot with a query that fails goes to the fall-back list
-__global__ void k_scan5_check(const int* __restrict__ slots, const int* __restrict__ n_slots_ptr, const WorkItem* __restrict__ items,
-                              const PlanOut* __restrict__ plan, const int* __restrict__ cnt_ok, const int* __restrict__ ovf, int L,
-                              int* __restrict__ fhdr, int* __restrict__ fslots, int* __restrict__ item_n, int* __restrict__ dbg) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n_slots_ptr[0]) return;
-    int bad[S5G], nb = 0;
-#pragma unroll
-    for (int g = 0; g < S5G; ++g) {
-        const int idx = slots[j * S5G + g];
-        if (idx < 0) continue;
-        const int q = items[idx].q;
-        const int64_t nc = plan[q].ncand;
-        const int need = nc < (int64_t)L ? (int)nc : L;
-        if (ovf[q] != 0 || cnt_ok[q] < need) bad[nb++] = idx;
-    }
-    if (nb == 0) return;
-    atomicAdd(&dbg[1], 1);
-    for (int b0 = 0; b0 < nb; b0 += S3G) {  // fall-back slots hold S3G items
-        const int f = atomicAdd(&fhdr[17], 1);
-#pragma unroll
-        for (int g = 0; g < S3G; ++g) {
-            fslots[f * S3G + g] = b0 + g < nb ? bad[b0 + g] : -1;
-            if (b0 + g < nb) item_n[bad[b0 + g]] = 0;  // whatever the slot wrote is replaced
-        }
-    }
-}
-
-__global__ void k_scan5_init(uint32_t* __restrict__ bmin, int64_t n_b, int* __restrict__ ints, int n_ints) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_b) bmin[i] = 0x7f800000u;
-    if (i < n_ints) ints[i] = 0;
-}
-
-bool scan5_supported(int M, int K, int L) { return (M == 4 || M == 8) && K <= 256 && K % 4 == 0 && L >= 1 && L <= 440; }
-static const int S5_B = 512;
-size_t scan5_workspace_bytes(int nq) { return (size_t)nq * S5_B * 4 + (size_t)nq * 4 * 4 + 256; }
-
 // k_adc_scan3 over the batch's slot list in the form g.two_pass, or (fallback) over the slots a sampled form could not settle -- a second
 // slot header (fhdr: queue counters [0..7], queue starts [16..24] of which only [17] = count is used): the two-pass form for short chunks,
 // the streaming form for long ones
@@ -2415,48 +1821,6 @@ static void launch_scan3_k(const Scan3Geom& g, const ScanArgs& a, bool fallback)
     hipLaunchKernelGGL((k_adc_scan3<M, NR, U, NW, WPE>), dim3(grid), dim3(NW * 64), g.lds, a.st, a.items, a.tabs, fallback ? a.fslots : a.slots,
                        fallback ? a.fhdr + 8 : a.n_slots, a.T, a.T32, a.codes, a.K, a.L, g.S, fallback ? a.fhdr : a.qctr, a.hits, a.hitn, a.slack, a.qbound,
                        fallback ? (g.long_chunks ? 0 : 1) : g.two_pass, fallback ? 1 : 0);
-}
-
-template <int M, int NR>
-static void launch_scan5_t(const Scan3Geom& g, const ScanArgs& a, void* ws) {
-    const int nq = a.nq;
-    uint32_t* bmin = reinterpret_cast<uint32_t*>(ws);
-    int* ints = reinterpret_cast<int*>(bmin + (size_t)nq * S5_B);
-    int* nsamp = ints;
-    int* cnt_ok = ints + nq;
-    int* ovf = ints + 2 * nq;
-    float* tau = reinterpret_cast<float*>(ints + 3 * nq);
-    const int64_t n_b = (int64_t)nq * S5_B;
-    hipLaunchKernelGGL(k_scan5_init, dim3((unsigned)((n_b + 255) / 256)), dim3(256), 0, a.st, bmin, n_b, ints, 3 * nq);
-    (void)hipMemsetAsync(a.hitn, 0, (size_t)(a.n_items + 1) * sizeof(int), a.st);
-    constexpr int WPE = 4;
-    const size_t lds = scan5_lds(M, a.K);
-    const int by_lds = (int)(163840 / lds);
-    const int per_cu = by_lds < WPE ? by_lds : WPE;
-    const unsigned grid = 256u * (unsigned)(per_cu < 1 ? 1 : per_cu);
-    static const int P_env = getenv("CIS_S5_P") ? atoi(getenv("CIS_S5_P")) : 0;
-    static const int ss_env = getenv("CIS_S5_SS") ? atoi(getenv("CIS_S5_SS")) : 4;
-    const int P = P_env > 0 ? P_env : (a.L < 100 ? 240 : (int)(2.4 * a.L));
-    auto pass = [&](auto sample, const float* thr) {
-        hipLaunchKernelGGL((k_adc_scan5<M, decltype(sample)::value, WPE>), dim3(grid), dim3(256), lds, a.st, a.items, a.tabs, a.slots, a.n_slots, a.T32, a.T, a.codes, a.K,
-                           g.S, thr, bmin, S5_B, nsamp, ss_env, a.hits, a.hitn, a.slack, cnt_ok, ovf);
-    };
-    pass(std::true_type{}, nullptr);
-    hipLaunchKernelGGL(k_scan5_tau<S5_B / 64>, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, a.st, bmin, S5_B, nsamp, a.plan, nq, P, tau);
-    pass(std::false_type{}, tau);
-    const int64_t max_slots = a.n_items + 8;  // (an upper bound of the slot count: the kernel reads the real one)
-    hipLaunchKernelGGL(k_scan5_check, dim3((unsigned)((max_slots + 255) / 256)), dim3(256), 0, a.st, a.slots, a.n_slots, a.items, a.plan, cnt_ok, ovf, a.L, a.fhdr, a.fslots,
-                       a.hitn, a.qctr + 9);
-    if (getenv("CIS_SCAN5_DEBUG")) {
-        int h[6] = {0, 0, 0, 0, 0, 0};
-        if (hipMemcpyAsync(h, a.qctr + 9, sizeof(h), hipMemcpyDeviceToHost, a.st) == hipSuccess && hipStreamSynchronize(a.st) == hipSuccess)
-            fprintf(stderr, "[cis] k_adc_scan5: %d slots to the fall-back list\n", h[1]);
-    }
-    launch_scan3_k<M, NR>(g, a, true);  // the slots it could not settle (as after k_adc_scan4)
-}
-
-void launch_scan5(int M, const Scan3Geom& g, const ScanArgs& a, void* ws) {  // (scan5_supported: M = 4 or 8, limit <= 440)
-    dispatch_int<4, 8>(M, [&](auto m) { dispatch_nr<8>(a.L, [&](auto nr) { launch_scan5_t<decltype(m)::value, decltype(nr)::value>(g, a, ws); }); });
 }
 
 bool scan3_supported(int M, int K, int L) {
@@ -2525,18 +1889,13 @@ static void launch_scan3_t(const Scan3Geom& g, const ScanArgs& a) {
     const int frac_long = getenv("CIS_S4_FRAC") ? atoi(getenv("CIS_S4_FRAC")) : 8;
     const int nsx_long = getenv("CIS_S4_NSX") ? atoi(getenv("CIS_S4_NSX")) : 128;
     const int dyn_long = getenv("CIS_S4_DYN") ? atoi(getenv("CIS_S4_DYN")) : 0;
-    // waves per slot (NW4) and waves per SIMD the variant is compiled for (WPS): 4 x 64 threads at 4 (long chunks) / 6 (short) waves
-    // per SIMD were rounds 2-3; 8 waves per slot halve a slot's main pass, and three such workgroups per CU are 24 waves
-    const int nw4_long = getenv("CIS_S4_NWL") ? atoi(getenv("CIS_S4_NWL")) : CIS_S4_NW_LONG;
-    const int nw4_short = getenv("CIS_S4_NWS") ? atoi(getenv("CIS_S4_NWS")) : CIS_S4_NW_SHORT;
+    // four waves per slot, compiled for 6 (short chunks) / 4 (long chunks) waves per SIMD
     if (!g.long_chunks) {
         constexpr int WPE4 = (M == 16) ? 4 : CIS_S4_WPE;  // (M = 16: 41 KB of LDS hold three workgroups per CU anyway)
-        if (nw4_short == 8 && M != 16) launch_scan4<M, CIS_S4_U, 8, WPE4, S4_LCAP>(g, a, z_short, 1 << 20, S4_NS, 0);
-        else launch_scan4<M, CIS_S4_U, 4, WPE4, S4_LCAP>(g, a, z_short, 1 << 20, S4_NS, 0);
+        launch_scan4<M, CIS_S4_U, 4, WPE4, S4_LCAP>(g, a, z_short, 1 << 20, S4_NS, 0);
     } else {
-        constexpr int WPE4 = (M == 16) ? 3 : ((CIS_S4_DEFER != 0 && CIS_S4_GLISTS != 0) ? CIS_S4_WPE_LONG : 4);  // (M = 16: 49 KB of LDS = three workgroups per CU, 168 registers)
-        if (nw4_long == 8 && M != 16) launch_scan4<M, CIS_S4_UL, 8, CIS_S4_WPE8, S4_LCAP_LONG>(g, a, z_long, frac_long, nsx_long, dyn_long);
-        else launch_scan4<M, CIS_S4_UL, 4, WPE4, S4_LCAP_LONG>(g, a, z_long, frac_long, nsx_long, dyn_long);
+        constexpr int WPE4 = (M == 16) ? 3 : 4;  // (M = 16: 49 KB of LDS = three workgroups per CU, 168 registers)
+        launch_scan4<M, CIS_S4_UL, 4, WPE4, S4_LCAP_LONG>(g, a, z_long, frac_long, nsx_long, dyn_long);
     }
     if (getenv("CIS_SCAN4_DEBUG")) {  // diagnosis: how many slots the sample misjudged (blocks)
         int h[6] = {0, 0, 0, 0, 0, 0};

@@ -302,9 +302,7 @@ __global__ __launch_bounds__(256) void k_tables_from_px(const double* __restrict
                                                         double* __restrict__ T /* [ntab][nf][K] */,
                                                         float* __restrict__ T32 /* [ntab][nf][K] float32 copy for the scan */,
                                                         const int64_t* __restrict__ d_totals /* null, or the plan totals: n_tabs is a bound */) {
-#ifndef CIS_TABLES_SCALAR_PX  // (scalar loads of the projected residual instead of the LDS copy: measured 0.185 against 0.162 ms on C2)
     __shared__ double sf[TPB][W];
-#endif
     __shared__ int ssplit[TPB];
     const int j = blockIdx.y, z = blockIdx.z, k = threadIdx.x;
     const int t0 = blockIdx.x * TPB;
@@ -313,12 +311,10 @@ __global__ __launch_bounds__(256) void k_tables_from_px(const double* __restrict
         if (t0 >= n_tabs) return;
     }
     const int nt = (n_tabs - t0 < TPB) ? (n_tabs - t0) : TPB;
-#ifndef CIS_TABLES_SCALAR_PX  // (scalar loads of the projected residual instead of the LDS copy: measured 0.185 against 0.162 ms on C2)
     for (int e = threadIdx.x; e < nt * W; e += 256) {
         const int t = e / W, i = e - t * W;
         sf[t][i] = px[(int64_t)(t0 + t) * h + j * W + i];
     }
-#endif
     if (threadIdx.x < nt) ssplit[threadIdx.x] = tabs[t0 + threadIdx.x].split;
     __syncthreads();
     const bool on = k < K;  // all lanes stay in the loop: the per-table maximum below is a full-wave reduction
@@ -328,13 +324,7 @@ __global__ __launch_bounds__(256) void k_tables_from_px(const double* __restrict
     for (int i = 0; i < W; ++i) sc[i] = src[i];
     for (int t = 0; t < nt; ++t) {
         if (ssplit[t] != z) continue;
-#ifndef CIS_TABLES_SCALAR_PX  // (scalar loads of the projected residual instead of the LDS copy: measured 0.185 against 0.162 ms on C2)
         const double* f = sf[t];
-#else
-        // the projected residual of table t is the same for every lane: a uniform address, i.e. scalar loads into SGPR operands
-        // (it used to be staged in LDS and read back sixteen times per table by every wave)
-        const double* f = px + (int64_t)(t0 + t) * h + j * W;
-#endif
         auto elem = [&](int i) -> double { const double df = f[i] - sc[i]; return df * df; };
         const double v = pw_leaf<double>(elem, 0, W);
         const float v32 = (float)v;
@@ -342,12 +332,8 @@ __global__ __launch_bounds__(256) void k_tables_from_px(const double* __restrict
             // NON-TEMPORAL: the float64 copy (2/3 of the bytes this kernel writes) is read sparsely, by the merge, much later; written with
             // the default policy it pushed the float32 copy -- which the scan stages next -- and the codes out of L2 / Infinity Cache.
             // Round 6, same box, median of two runs each: C4 21.3 -> 21.8 M queries/s (scan 0.233 -> 0.230 ms), C2 19.7 -> 21.1 M
-            // (scan 0.157 -> 0.152, merge 0.115 -> 0.105 ms).  -DCIS_TABLES_NO_NT: the default policy (A/B).
-#ifndef CIS_TABLES_NO_NT
+            // (scan 0.157 -> 0.152, merge 0.115 -> 0.105 ms).
             __builtin_nontemporal_store(v, &T[((int64_t)(t0 + t) * nf + j) * K + k]);
-#else
-            T[((int64_t)(t0 + t) * nf + j) * K + k] = v;
-#endif
             if (T32) T32[((int64_t)(t0 + t) * nf + j) * K + k] = v32;  // (null: the scans convert the float64 entries themselves, see tab_f4; stored non-temporal too: no gain)
         }
         // largest float32 entry of the table (entries are >= 0: the bit patterns order like the values), for the
@@ -900,15 +886,11 @@ __device__ __forceinline__ void scan2_group(const WorkItem* __restrict__ items_a
                 // above it are strictly worse than L others, whichever cell they are in.  Cells of one query are
                 // scanned by different workgroups at different times (the slot list is sorted by cell), so the
                 // later ones start with a tight bound instead of +inf.  Only the amount of work depends on timing.
-#ifndef CIS_SCAN_NO_QBOUND
                 int qg = it_q[0];  // g is a thread index here: select, do not index the register array
 #pragma unroll
                 for (int gg = 1; gg < G; ++gg) qg = (g == gg) ? it_q[gg] : qg;
                 const unsigned long long e = (g < ng) ? __hip_atomic_load(&qbound[qg], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
                                                       : 0x7ff0000000000000ull;
-#else
-                const unsigned long long e = 0x7ff0000000000000ull;
-#endif
                 sh[g].ext = e;
                 // an absent second query: negative bound, nothing ever passes (its tables are +inf as well)
                 sh[g].bound_f = (g < ng) ? __double2float_ru(__longlong_as_double((long long)e)) : -1.0f;
@@ -933,7 +915,6 @@ __device__ __forceinline__ void scan2_group(const WorkItem* __restrict__ items_a
     bool any_dup = false;
 #pragma unroll
     for (int g = 0; g < G; ++g) { cnt[g] = 0; has_dup[g] = false; dup[g] = CodeWords<M>(); }
-#ifndef CIS_SCAN_PLAIN_LOADS
     // buffer descriptor over this chunk's codes, built from wave-uniform values only
     __amdgpu_buffer_rsrc_t rs;
     {
@@ -943,14 +924,10 @@ __device__ __forceinline__ void scan2_group(const WorkItem* __restrict__ items_a
         const int nbytes = __builtin_amdgcn_readfirstlane(len * M);
         rs = __builtin_amdgcn_make_buffer_rsrc((void*)(uintptr_t)(((uint64_t)bhi << 32) | blo), 0, nbytes, 0x00020000);
     }
-#define CIS_LOAD_CODE(p) load_code_buf<M>(rs, (p))
-#else
-#define CIS_LOAD_CODE(p) load_code<M>(codes, start + ((p) < len ? (p) : len - 1))
-#endif
     CodeWords<M> nxt[U];
     if (w < nit) {
 #pragma unroll
-        for (int u = 0; u < U; ++u) nxt[u] = CIS_LOAD_CODE(w * 64 * U + u * 64 + lane);
+        for (int u = 0; u < U; ++u) nxt[u] = load_code_buf<M>(rs, w * 64 * U + u * 64 + lane);
     }
     for (int iter = w; iter < nit; iter += NW) {
         const int base = iter * 64 * U;
@@ -959,10 +936,9 @@ __device__ __forceinline__ void scan2_group(const WorkItem* __restrict__ items_a
         for (int u = 0; u < U; ++u) cur[u] = nxt[u];
         if (iter + NW < nit) {  // software prefetch: the next iteration's codes are in flight while this one computes
 #pragma unroll
-            for (int u = 0; u < U; ++u) nxt[u] = CIS_LOAD_CODE((iter + NW) * 64 * U + u * 64 + lane);  // tail lanes are masked below
+            for (int u = 0; u < U; ++u) nxt[u] = load_code_buf<M>(rs, (iter + NW) * 64 * U + u * 64 + lane);  // tail lanes are masked below
         }
         float d[U][G];
-#ifndef CIS_SCAN_NO_PIPELINE
         if constexpr (G >= 2) {
             typename AdcVec<G>::type fbuf[2][M];
             adc32_issue<M, G>(cur[0], tab, rc, fbuf[0]);
@@ -973,9 +949,7 @@ __device__ __forceinline__ void scan2_group(const WorkItem* __restrict__ items_a
                 adc32_reduce<M, G>(fbuf[u & 1], d[u]);
                 __builtin_amdgcn_sched_barrier(0);
             }
-        } else
-#endif
-        {
+        } else {
 #pragma unroll
             for (int u = 0; u < U; ++u) adc32g<M, G>(cur[u], tab, rc, d[u]);
         }
@@ -993,10 +967,7 @@ __device__ __forceinline__ void scan2_group(const WorkItem* __restrict__ items_a
         unsigned long long any = 0ull;
 #pragma unroll
         for (int g = 0; g < G; ++g) {
-            float thrm = block_bound_f32(&sh[g]) * margin;
-#ifdef CIS_PROBE_HOTLOOP
-            thrm = (margin > 100.f) ? thrm : -1.0f;  // probe: nothing passes, only the float32 scan runs
-#endif
+            const float thrm = block_bound_f32(&sh[g]) * margin;
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 pm[u][g] = __ballot(d[u][g] <= thrm);
@@ -1122,12 +1093,10 @@ __device__ __forceinline__ void scan2_group(const WorkItem* __restrict__ items_a
         uint64_t* rk = rk_all + (g * NW + w) * R;
         cnt[g] = wave_filter_approx<NR, NW>(rk, cnt[g], margin, &sh[g]);
         if (lane == 0) sh[g].wcnt[w] = cnt[g];
-#ifndef CIS_SCAN_NO_QBOUND
         if (tid == 0) {
             const uint64_t b = block_bound<NW>(&sh[g]);
             if (b < sh[g].ext) atomicMin(&qbound[it_q[g]], (unsigned long long)b);
         }
-#endif
     }
     const long long clk_exact_end = CIS_CLK();
     (void)clk_exact_end;
@@ -1729,13 +1698,13 @@ extern "C" int cis_selftest(int* n_errors) {
 
 extern "C" int cis_index_set_scan_mode(cis_index* ix, int mode) {
     CIS_REQUIRE(ix != nullptr && mode >= 0 && mode <= 7, "bad scan mode");
+    if (mode == 7) mode = 5;  // 7 forced a kernel that was removed: it stays accepted and sets what 5 sets
     ix->force_stream = (mode == 6);
-    ix->force_scan5 = (mode == 7);
     ix->force_exact_scan = (mode == 1);
-    ix->force_prefilter_scan = (mode >= 2 && mode <= 5) || mode == 7;
+    ix->force_prefilter_scan = (mode >= 2 && mode <= 5);
     ix->force_scan2 = (mode == 2);
-    ix->force_scan3 = (mode == 3 || mode == 4 || mode == 5 || mode == 7);
-    ix->force_two_pass = mode == 3 ? 0 : (mode == 4 ? 1 : ((mode == 5 || mode == 7) ? 2 : -1));
+    ix->force_scan3 = (mode == 3 || mode == 4 || mode == 5);
+    ix->force_two_pass = mode == 3 ? 0 : (mode == 4 ? 1 : (mode == 5 ? 2 : -1));
     return CIS_OK;
 }
 
@@ -3304,16 +3273,6 @@ static int route_decide(Batch& b, Route* r) {
     }
     r->geom3 = scan3_geom(M, K, L, b.n_items > 0 ? b.n_cand_all / b.n_items : 0, ix->force_two_pass);
     r->S = r->fast ? (r->use3 ? r->geom3.S : r->geom.S) : L;
-    r->use5 = false;
-    if (!r->stream && !r->big && r->fast && b.n_items > 0) {  // (the scan route's fast kernels: the only readers)
-        // k_adc_scan5 (round 5): where the sampled form k_adc_scan4 would run -- one threshold per query for the whole batch
-        // instead of one per slot, eight queries per slot.  MEASURED AND LEFT OFF (profiles/r05g_*, r05h_*: C4 sample 64 + thresholds 17 +
-        // main pass 200 + check 12 us against 231 us for the whole of k_adc_scan4, and a merge of 134 instead of 76 us for the longer
-        // lists; both pipes ~40 % busy at three workgroups per CU: the loop is bound by latency, not by instructions).  CIS_SCAN5=1
-        // routes large batches to it, scan mode 7 forces it (tests: every search test passes on it).
-        static const int env_s5 = getenv("CIS_SCAN5") ? atoi(getenv("CIS_SCAN5")) : 0;
-        r->use5 = r->use3 && r->geom3.two_pass == 2 && scan5_supported(M, K, L) && (ix->force_scan5 || (env_s5 != 0 && !ix->force_scan3 && L <= 128));
-    }
     // The float32 copy of the tables is a third of what the tables kernel writes (8 + 4 bytes per entry: 402 MB per C2 batch, and that
     // kernel is bound by its writes); CIS_NO_T32=1 drops it -- the scans then convert the float64 entries while they stage them
     // (tab_f4: the same bits).  The tiny-cell path keeps its float32 px copy in this buffer.
@@ -3660,20 +3619,16 @@ static int run_fast_scan(Batch& b, const Route& r) {
     const Scan3Geom& geom3 = r.geom3;
     // slot list: work items grouped by coarse cell (counting sort; skipped for huge V), G per slot
     const bool sort_items = ix->ncells <= 65536;
-    const bool use5 = r.use5;
-    const int G = use5 ? 8 : (use3 ? geom3.G : r.geom.G);
+    const int G = use3 ? geom3.G : r.geom.G;
     // chunks per cell that get their own slot keys: what the largest cell needs (all shards' sizes bound this shard's)
     int64_t CH = use3 ? ceil_div(ix->max_cell > 0 ? ix->max_cell : 1, (int64_t)r.seg_max) : 1;
     CH = CH < 1 ? 1 : (CH > 16 ? 16 : CH);
     Slots sl;
     CIS_TRY(build_slots(b, sort_items ? SLOTS_SORTED : SLOTS_IDENTITY, G, CH, r.seg_max, &sl));
     CIS_TRY(mark(b, 5));
-    ix->last_scan_kernel = use5 ? 6 : (use3 ? (geom3.two_pass == 2 ? 4 : 3) : 2);  // 4: the sampled single-pass form k_adc_scan4 does the work (k_adc_scan3 only its fall-back slots)
+    ix->last_scan_kernel = use3 ? (geom3.two_pass == 2 ? 4 : 3) : 2;  // 4: the sampled single-pass form k_adc_scan4 does the work (k_adc_scan3 only its fall-back slots)
     const ScanArgs a = scan_args(b, sl);
-    if (use5) {
-        CIS_TRY(ix->w_s5.reserve(scan5_workspace_bytes(b.nq)));
-        launch_scan5(M, geom3, a, ix->w_s5.p);
-    } else if (use3) {
+    if (use3) {
         Scan3Geom g3 = geom3;
         // M = 16 on the sampled form: the saturating scale of k_adc_scan4 (sums of the near candidates at this fraction of the entry cap)
         const float sat16 = getenv("CIS_S4_SAT") ? (float)atof(getenv("CIS_S4_SAT")) : 0.75f;

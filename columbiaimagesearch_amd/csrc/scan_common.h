@@ -352,9 +352,6 @@ __device__ __forceinline__ RotConsts<M> make_rot(int lane) {
         const int th = t >> 2, tq = t & 3;
         const int j = ((h ^ th) << 2) | ((q + tq) & 3);
         rc.cj[t] = (uint32_t)j << 2;
-#ifdef CIS_SCAN_OPAQUE_CJ
-        asm volatile("" : "+v"(rc.cj[t]));  // keep the M offsets in M registers (else the compiler re-derives half of them per use)
-#endif
     }
     return rc;
 }
@@ -535,11 +532,6 @@ void launch_stream_scan(const CandArgs& c, const StreamArgs& s, bool sample);
 void launch_stream_tau(const CandArgs& c, const StreamArgs& s, int k);
 void launch_stream_keys(const CandArgs& c, const StreamArgs& s);
 void launch_stream_finish(const CandArgs& c, const StreamArgs& s, const SearchOut& out, int64_t* status_host_dev, int64_t seq);
-
-// ---- k_adc_scan5 (lopq_scan3.hip): one threshold per query for the whole batch, eight queries per slot -----------------------
-bool scan5_supported(int M, int K, int L);
-size_t scan5_workspace_bytes(int nq);
-void launch_scan5(int M, const Scan3Geom& g, const ScanArgs& a, void* ws);
 
 // ---- merges of ranked hit lists: the work items of a query (lopq_search.hip), the shards' partial results (lopq_exchange.hip) ----
 // block-wide bitonic sort of N (a power of two, chosen at run time) keys (a, b) with an optional payload, in LDS: the merge sorts

@@ -522,7 +522,7 @@ class LOPQSearcherHIP(LOPQSearcherBase):
         _lib.check(_lib.lib().cis_index_last_stats(self._ix, _lib.ptr(st)))
         kind = int(_lib.lib().cis_index_last_scan_kernel(self._ix))
         return {"candidates": int(st[0]), "items": int(st[1]), "tables": int(st[2]), "scan_launches": int(st[3]),
-                "scan_kernel": {0: None, 1: "k_adc_scan", 2: "k_adc_scan2", 3: "k_adc_scan3", 4: "k_adc_scan4", 5: "k_adc_stream", 6: "k_adc_scan5"}.get(kind)}
+                "scan_kernel": {0: None, 1: "k_adc_scan", 2: "k_adc_scan2", 3: "k_adc_scan3", 4: "k_adc_scan4", 5: "k_adc_stream"}.get(kind)}
 
 
     default_prefilter_only = False  # tests: new searchers keep the float32-prefilter kernel for every batch size
@@ -532,7 +532,8 @@ class LOPQSearcherHIP(LOPQSearcherBase):
         """Routing of limit <= 952 (tests; results are identical on every route): exact_only forces the float64 scan
         kernel, prefilter_only the float32-prefilter kernel for every batch size (small batches otherwise take the
         all-candidates path: shorter kernel chain at low occupancy; large ones the 16-bit fixed-point kernel);
-        mode = the raw cis_index_set_scan_mode value (3: the 16-bit fixed-point kernel for every batch size)."""
+        mode = the raw cis_index_set_scan_mode value (3: the 16-bit fixed-point kernel for every batch size;
+        7 is accepted and sets what 5 sets)."""
         if mode is None:
             if prefilter_only is None:
                 prefilter_only = type(self).default_prefilter_only

@@ -379,7 +379,7 @@ int cis_index_set_profiling(cis_index* ix, int level /* 0 off, 1 only the pair o
  * default -- an exhaustive quota = N run (lopq/lopq/search.py:128-133 consumes whole cells until the quota), or any quota over
  * cells of hundreds of thousands of codes: a sampled threshold per query, one pass over the codes at the HBM rate that lists the
  * few thousand candidates under it, exact float64 keys and ranking of the list, and a proof that the list holds the true top
- * `limit`; a query whose proof fails is answered again by the generic path).
+ * `limit`; a query whose proof fails is answered again by the generic path), 7 = accepted, and sets exactly what 5 sets.
  * All routes produce identical results; the switch exists so that tests can prove it. */
 int cis_index_set_scan_mode(cis_index* ix, int mode);
 /* counters[0] = batches the HBM-streaming route served, counters[1] = batches it handed back to the generic path (failed proof or

@@ -2,8 +2,10 @@
 the kernel of the same name in the listings after it (make -C columbiaimagesearch_amd/csrc build/x.s).  Compared per kernel: the
 instruction text of the body, the .amdhsa_* descriptor and the register / spill / scratch / LDS figures of the metadata; only local
 label numbers, line-info directives and comments are normalised.  Exit status 1 when a kernel is missing, new or different.
-usage: kernel_asm_diff.py old/lopq_search.s -- new/lopq_search.s new/lopq_plan.s"""
-import difflib, re, sys
+--removed SUBSTRING (may be repeated): a kernel of the old side only whose mangled or demangled name contains SUBSTRING was removed on
+purpose: it is printed as `removed:` and is no failure.
+usage: kernel_asm_diff.py old/lopq_search.s -- new/lopq_search.s new/lopq_plan.s [--removed k_old_kernel]"""
+import difflib, re, shutil, subprocess, sys
 
 META = r"^    \.(vgpr_spill_count|sgpr_spill_count|vgpr_count|agpr_count|sgpr_count|private_segment_fixed_size|group_segment_fixed_size|max_flat_workgroup_size):"
 
@@ -33,11 +35,24 @@ def kernels(paths):
     return out
 
 
-sep = sys.argv.index("--")
-old, new = kernels(sys.argv[1:sep]), kernels(sys.argv[sep + 1:])
+def demangled(name):  # "k<4, 2>" of "void k<4, 2>(int const*)"; the mangled name where there is no c++filt
+    if not shutil.which("c++filt"):
+        return name
+    return subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip().split("(")[0].replace("void ", "")
+
+
+args, removed = sys.argv[1:], []
+while "--removed" in args:
+    i = args.index("--removed")
+    removed.append(args[i + 1])
+    del args[i:i + 2]
+sep = args.index("--")
+old, new = kernels(args[:sep]), kernels(args[sep + 1:])
 bad = 0
 for name in sorted(set(old) | set(new)):
-    if name not in old or name not in new:
+    if name not in new and any(r in name or r in demangled(name) for r in removed):
+        print("removed: %s" % demangled(name))
+    elif name not in old or name not in new:
         print("%s only: %s" % ("old" if name in old else "new", name))
         bad += 1
     elif old[name] != new[name]:
