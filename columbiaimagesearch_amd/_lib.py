@@ -107,6 +107,7 @@ _PROTOS = {
     "cis_exact_knn_stats": (c_int, [c_void_p]),
     "cis_kmeans": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "cis_kmeans_dev": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cis_kmeanspp_dev": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cis_train_gram": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "cis_train_project": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "cis_index_last_stats": (c_int, [c_void_p, c_void_p]),

@@ -4,6 +4,10 @@ Restates the training recipe of the reference (lopq/lopq/model.py:19-437) withou
 Python loops: covariance accumulators become matrix products.  k-means results depend on the
 scikit-learn version, so training is judged by distortion/recall, not bit parity (SURVEY.md
 section 8c caveat ii, section 8f row 3).  Not on the encode/search hot path.
+
+Three switches move work to the GPU, all off by default: ACCUM_BACKEND ("hip": covariance accumulations and projections),
+KMEANS_BACKEND ("hip" / "device": Lloyd iterations) and SEED_BACKEND ("device": the k-means++ seeds of kmeans_dev are drawn on the
+resident data by cis_kmeanspp_dev, csrc/kmeans_seed.hip, and never visit the host).
 """
 import logging
 
@@ -146,6 +150,28 @@ def kmeans_pp_init(data, k, rs, sample=20000):
     return C
 
 
+def kmeans_pp_init_dev(x, k, rs, sample=20000):
+    """k-means++ seeding on the GPU (cis_kmeanspp_dev, csrc/kmeans_seed.hip): [k, d] float32 centroids, rows of `x`, as a tensor on
+    x's device; only enqueued on the current stream.  x: a resident float32 [n, d] tensor.  sample: an int seeds on
+    rs.choice(n, min(n, sample), replace=False), gathered on the device; None seeds on all n rows without a gather.  Then
+    u = rs.rand(k) is uploaded: centre 0 is row floor(u[0] * rows), draw j takes the first row whose running sum of squared
+    distances exceeds u[j] * total (include/cis_hip.h).  The RandomState is consumed differently from kmeans_pp_init (k uniforms at
+    once; no randint), so the two seedings give different seeds for one random_state."""
+    import torch
+    from .. import _lib
+    x = _resident(x)
+    n, d = int(x.shape[0]), int(x.shape[1])
+    if sample is not None:
+        pick = rs.choice(n, min(n, int(sample)), replace=False)
+        x = x[torch.as_tensor(pick, device=x.device)].contiguous()
+        n = int(x.shape[0])
+    u = torch.from_numpy(rs.rand(int(k))).to(x.device)
+    C = torch.empty((int(k), d), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().cis_kmeanspp_dev(x.data_ptr(), n, d, int(k), u.data_ptr(), C.data_ptr(), None, None,
+                                           torch.cuda.current_stream(x.device).cuda_stream))
+    return C
+
+
 def kmeans_hip(data, k, iters, n_init=1, random_state=None):
     """Lloyd iterations on the GPU (cis_kmeans) from k-means++ seeds drawn on the host; best of n_init by inertia.
     Counterpart of the scikit-learn call of the reference (lopq/lopq/model.py:359-372,:417-432); float32."""
@@ -178,8 +204,9 @@ def _resident(data):
 
 def kmeans_dev(data, k, iters, n_init=1, random_state=None):
     """kmeans_hip for codebooks of any size, on data that stays on the GPU (cis_kmeans_dev, csrc/kmeans_mfma.hip): k-means++ seeds
-    from the host, best of n_init by reported inertia; (float64 centroids, inertia).  data: a numpy array (uploaded once, reused by
-    every run) or a float32 tensor on the GPU."""
+    from the host (SEED_BACKEND = "host": kmeans_pp_init) or drawn on the device (SEED_BACKEND = "device": kmeans_pp_init_dev on
+    SEED_SAMPLE rows, handed to cis_kmeans_dev as they are), best of n_init by reported inertia; (float64 centroids, inertia).
+    data: a numpy array (uploaded once, reused by every run) or a float32 tensor on the GPU."""
     import torch
     from .. import _lib
     x = _resident(data)
@@ -187,9 +214,14 @@ def kmeans_dev(data, k, iters, n_init=1, random_state=None):
     rs = np.random.RandomState(random_state)
     stream = torch.cuda.current_stream(x.device).cuda_stream
     inertia = torch.empty(1, dtype=torch.float64, device=x.device)
+    if SEED_BACKEND not in ("host", "device"):
+        raise ValueError("SEED_BACKEND must be 'host' or 'device', got %r" % (SEED_BACKEND,))
     best, best_inertia = None, np.inf
     for _ in range(max(int(n_init), 1)):
-        C = torch.from_numpy(np.ascontiguousarray(kmeans_pp_init(x, k, rs), dtype=np.float32)).to(x.device)
+        if SEED_BACKEND == "device":
+            C = kmeans_pp_init_dev(x, k, rs, SEED_SAMPLE)
+        else:
+            C = torch.from_numpy(np.ascontiguousarray(kmeans_pp_init(x, k, rs), dtype=np.float32)).to(x.device)
         _lib.check(_lib.lib().cis_kmeans_dev(x.data_ptr(), n, d, int(k), int(iters), C.data_ptr(), None, inertia.data_ptr(), stream))
         got = float(inertia.cpu()[0])
         if got < best_inertia:
@@ -215,6 +247,11 @@ def assign_clusters_dev(data, C):
 # "hip": Lloyd iterations on the GPU where the codebook fits the LDS kernel (k * d <= 7680), scikit-learn beyond.
 # "device": every codebook, and every assignment of the training set, on the GPU (kmeans_dev / assign_clusters_dev).
 KMEANS_BACKEND = "sklearn"
+# Where kmeans_dev draws its k-means++ seeds.  "host": kmeans_pp_init, numpy on a subsample copied to the host (what kmeans_hip always
+# does: cis_kmeans takes host pointers).  "device": kmeans_pp_init_dev on SEED_SAMPLE rows of the resident data (None: all rows); a
+# different use of the RandomState, so different seeds for one random_state.
+SEED_BACKEND = "host"
+SEED_SAMPLE = 20000
 
 
 def _kmeans(data, k, iters, n_init, random_state, dev=None):

@@ -339,6 +339,29 @@ int cis_kmeans(const float* X, int64_t n, int d, int k, int iters, float* centro
 int cis_kmeans_dev(const float* d_X, int64_t n, int d, int k, int iters, float* d_centroids, int32_t* d_assign, double* d_inertia,
                    void* stream);
 
+/* k-means++ seeds (the D^2 draws of Arthur & Vassilvitskii) for cis_kmeans_dev, on data that is already on the device
+ * (csrc/kmeans_seed.hip).  Every pointer is a device pointer: d_X [n][d] float32 (never written), d_u [k] float64 uniforms in [0, 1)
+ * (the caller supplies the randomness: the call is a deterministic function of its inputs, and two calls with equal inputs give equal
+ * bytes), d_centroids [k][d] float32 out (each a row of d_X), d_picked [k] int32 out (the rows; or NULL), d_potential one double out
+ * (the sum over rows of the squared distance to the nearest of the k centres; or NULL).  The call only enqueues kernels on `stream`:
+ * no host synchronisation, no read-back; its grow-only workspace (n floats and a double per 256 rows) is allocated on the first use
+ * of a size.
+ *   Centre 0 is row floor(u[0] * n).
+ *   d2[r] is float32 in the direct form acc = fmaf(x[i] - c[i], x[i] - c[i], acc), in some fixed order over i: a chosen row and every
+ *   copy of it have d2 == 0 exactly.  After centre j, d2[r] = min(d2[r], dist(r, centre j)).
+ *   Draw j >= 1: tot = the sum of d2 in float64, t = u[j] * tot (one float64 multiply), and the pick is the smallest r with d2[r] > 0
+ *   whose inclusive float64 prefix sum S(r) exceeds t, strictly: a row with d2 == 0 is never picked while tot > 0.  Sums are taken over
+ *   fixed tiles of 256 rows with a fixed tree each, whatever the grid; tot and the prefix over tiles are one chain over the tile sums
+ *   (the last tile's prefix equals tot bit for bit, and the prefix never decreases); S(r) inside the tile is the tile's prefix plus a
+ *   fixed scan of its d2.  If rounding lets that scan run off the tile's end, the tile's last row with d2 > 0 is taken.
+ *   If tot == 0 (fewer distinct rows than centres), centre j is row floor(u[j] * n).
+ * On small-integer data every d2 and every sum is an exact integer and the picks equal an int64 restatement; otherwise S(r) carries
+ * the relative error of the float32 d2, about (d + 2) 2^-24.
+ * Limits (CIS_EINVAL beyond, refused before the device is touched): 1 <= n <= 2^31 - 256, k >= 1, d >= 1, k * d <= 2^30; d_X, d_u and
+ * d_centroids not NULL.  The calls share one process-wide workspace: they must not overlap on two streams or threads. */
+int cis_kmeanspp_dev(const float* d_X, int64_t n, int d, int k, const double* d_u, float* d_centroids, int32_t* d_picked,
+                     double* d_potential, void* stream);
+
 /* Training accumulations on the GPU (csrc/lopq_train.hip), float64, host pointers.  Rows of X [n][d] are sorted by group;
  * group_off [groups+1] are the row offsets (group_off[0] = 0, group_off[groups] = n).
  * cis_train_gram:    G[g] = sum_{r in g} x_r x_r^T [groups][d][d] and S[g] = sum x_r [groups][d] (S may be NULL): the np.outer
