@@ -215,19 +215,23 @@ __device__ __forceinline__ int wave_filter3(uint32_t* rk, int cnt, const QScale&
 // [o*OCT, (o+1)*OCT) of the lane-rotated sub-quantizer order -- and their sum.  M = 16 is two units per candidate, so
 // that the register footprint of the reads in flight is the same for every M.
 // TWO (k_adc_scan4's long-chunk M = 8 form): two interleaved copies of the table, a k-row is 2 M * 8 bytes and rc.cj carries the
-// lane's copy (two_copy_rot) -- the same two VALU per entry.
+// lane's copy (two_copy_rot).  One VALU per entry (gather_addr, scan_common.h); the unit's addresses come before its first read.
+template <int M, bool TWO = false>
+static constexpr int adc16_sh() { return ((M == 4) ? 2 : (M == 8 ? 3 : 4)) + 3 + (TWO ? 1 : 0); }  // log2(M * 8 bytes): one k-row of the table
+template <int M, bool TWO = false>
+using Adc16Consts = GatherConsts<M, adc16_sh<M, TWO>()>;
+template <int M, bool TWO = false>
+__device__ __forceinline__ Adc16Consts<M, TWO> adc16_consts(const RotConsts<M>& rc, const char* tab) {
+    return make_gather<M, adc16_sh<M, TWO>()>(rc, tab, 1);
+}
+
 template <int M, int OCT, bool TWO = false>
-__device__ __forceinline__ void adc16_issue(const uint32_t (&D)[(M + 3) / 4], int o, const char* __restrict__ tab,
-                                            const RotConsts<M>& rc, u32x2_t (&f)[OCT]) {
-    constexpr int SH = ((M == 4) ? 2 : (M == 8 ? 3 : 4)) + 3 + (TWO ? 1 : 0);  // log2(M * 8 bytes): one k-row of the table
+__device__ __forceinline__ void adc16_issue(const uint32_t (&D)[(M + 3) / 4], int o, const Adc16Consts<M, TWO>& gc, u32x2_t (&f)[OCT]) {
+    uint32_t a[OCT];
 #pragma unroll
-    for (int i = 0; i < OCT; ++i) {
-        const int t = o * OCT + i;
-        const uint32_t k = __builtin_amdgcn_ubfe(D[t >> 2], rc.sh[t & 3], 8);
-        // (TWO: written as a sum, so that every entry is one shift-add onto a constant that holds the table's base)
-        if constexpr (TWO) f[i] = *reinterpret_cast<const u32x2_t*>(tab + ((k << SH) + (rc.cj[t] << 1)));
-        else f[i] = *reinterpret_cast<const u32x2_t*>(tab + ((k << SH) | (rc.cj[t] << 1)));
-    }
+    for (int i = 0; i < OCT; ++i) a[i] = gather_addr(gc, D, o * OCT + i);
+#pragma unroll
+    for (int i = 0; i < OCT; ++i) f[i] = gather_ld<u32x2_t>(a[i]);
 }
 
 // two independent chains (queries 0-1 and 2-3), interleaved: no back-to-back dependent packed adds
@@ -349,6 +353,7 @@ __device__ __forceinline__ void scan3_group(const WorkItem* __restrict__ items, 
     __syncthreads();
     S3_CTR(3, S3_CLK() - c0);
     const RotConsts<M> rc = make_rot<M>(lane);
+    const Adc16Consts<M> gc = adc16_consts<M>(rc, tab);
     const int Lw = (L + NW - 1) / NW;
     const int len = __builtin_amdgcn_readfirstlane(it0.len);
     const int64_t start = ((int64_t)__builtin_amdgcn_readfirstlane((int)(it0.start >> 32)) << 32) |
@@ -390,14 +395,14 @@ __device__ __forceinline__ void scan3_group(const WorkItem* __restrict__ items, 
             u32x2_t fbuf[2][OCT];
             uint32_t D[2][(M + 3) / 4];
             rot_words<M>(cur[0], rc, D[0]);
-            adc16_issue<M, OCT>(D[0], 0, tab, rc, fbuf[0]);
+            adc16_issue<M, OCT>(D[0], 0, gc, fbuf[0]);
 #pragma unroll
             for (int q = 0; q < U * NU; ++q) {
                 const int u = q / NU, o = q % NU;
                 if (q + 1 < U * NU) {
                     const int u1 = (q + 1) / NU, o1 = (q + 1) % NU;
                     if (o1 == 0) rot_words<M>(cur[u1], rc, D[u1 & 1]);
-                    adc16_issue<M, OCT>(D[u1 & 1], o1, tab, rc, fbuf[(q + 1) & 1]);
+                    adc16_issue<M, OCT>(D[u1 & 1], o1, gc, fbuf[(q + 1) & 1]);
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 const u32x2_t part = adc16_sum<OCT>(fbuf[q & 1]);
@@ -608,14 +613,14 @@ __device__ __forceinline__ void scan3_group(const WorkItem* __restrict__ items, 
             u32x2_t fbuf[2][OCT];
             uint32_t D[2][(M + 3) / 4];
             rot_words<M>(cur[0], rc, D[0]);
-            adc16_issue<M, OCT>(D[0], 0, tab, rc, fbuf[0]);
+            adc16_issue<M, OCT>(D[0], 0, gc, fbuf[0]);
 #pragma unroll
             for (int q = 0; q < U * NU; ++q) {
                 const int u = q / NU, o = q % NU;
                 if (q + 1 < U * NU) {
                     const int u1 = (q + 1) / NU, o1 = (q + 1) % NU;
                     if (o1 == 0) rot_words<M>(cur[u1], rc, D[u1 & 1]);
-                    adc16_issue<M, OCT>(D[u1 & 1], o1, tab, rc, fbuf[(q + 1) & 1]);
+                    adc16_issue<M, OCT>(D[u1 & 1], o1, gc, fbuf[(q + 1) & 1]);
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 const u32x2_t part = adc16_sum<OCT>(fbuf[q & 1]);
@@ -912,20 +917,20 @@ struct Scan4Shared {  // per query
 
 // sums of UU rows of 64 candidates (software pipelined: the table reads of unit q+1 are issued before the adds of unit q)
 template <int M, int UU, int OCT = (M >= 8 ? 8 : 4), bool TWO = false>
-__device__ __forceinline__ void adc16_rows(const CodeWords<M> (&cur)[UU], const char* __restrict__ tab, const RotConsts<M>& rc,
+__device__ __forceinline__ void adc16_rows(const CodeWords<M> (&cur)[UU], const RotConsts<M>& rc, const Adc16Consts<M, TWO>& gc,
                                            u32x2_t (&d)[UU]) {
     constexpr int NU = M / OCT;
     u32x2_t fbuf[2][OCT];
     uint32_t D[2][(M + 3) / 4];
     rot_words<M>(cur[0], rc, D[0]);
-    adc16_issue<M, OCT, TWO>(D[0], 0, tab, rc, fbuf[0]);
+    adc16_issue<M, OCT, TWO>(D[0], 0, gc, fbuf[0]);
 #pragma unroll
     for (int q = 0; q < UU * NU; ++q) {
         const int u = q / NU, o = q % NU;
         if (q + 1 < UU * NU) {
             const int u1 = (q + 1) / NU, o1 = (q + 1) % NU;
             if (o1 == 0) rot_words<M>(cur[u1], rc, D[u1 & 1]);
-            adc16_issue<M, OCT, TWO>(D[u1 & 1], o1, tab, rc, fbuf[(q + 1) & 1]);
+            adc16_issue<M, OCT, TWO>(D[u1 & 1], o1, gc, fbuf[(q + 1) & 1]);
         }
         __builtin_amdgcn_sched_barrier(0);
         const u32x2_t part = adc16_sum<OCT>(fbuf[q & 1]);
@@ -997,7 +1002,7 @@ static_assert(4 * scan4_two_lds(256, S4_LCAP_LONG, 4) <= 163840, "the two-copy f
 static __device__ __forceinline__ RotConsts<8> two_copy_rot(const RotConsts<8>& rc, uint32_t copy) {
     RotConsts<8> r2 = rc;
 #pragma unroll
-    for (int t = 0; t < 8; ++t) r2.cj[t] = (rc.cj[t] << 1) | (copy << 2);  // (adc16_issue shifts by one more: (2 j + c) << 3)
+    for (int t = 0; t < 8; ++t) r2.cj[t] = (rc.cj[t] << 1) | (copy << 2);  // (adc16_consts shifts by one more: (2 j + c) << 3)
     return r2;
 }
 // byte of list word i in the odd slots of the table region
@@ -1071,6 +1076,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
     };
     RotConsts<M> rc = make_rot<M>(lane);
     if constexpr (TWO) rc = two_copy_rot(rc, ((uint32_t)lane >> 3) & 1u);
+    const Adc16Consts<M, TWO> gc = adc16_consts<M, TWO>(rc, tab);  // (the table's base and the lane's constants, once per kernel)
     // word i of the per-query lists [(g * NW + w) * WCAP + idx]
     auto list_at = [&](int i) -> uint32_t* { return reinterpret_cast<uint32_t*>(tab + two_list_byte(i)); };  // (TWO)
     const int nvec = (nf * K) >> 2;  // float4 per half table (<= 256 = threads)
@@ -1342,7 +1348,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                     // ---- sample pass: wave w computes sample rows 2w, 2w+1; an absent sample leaves 0xffff -------------------------------
                     {
                         u32x2_t dd[SPW];
-                        adc16_rows<M, SPW, S4_OCT>(sc, tab, rc, dd);
+                        adc16_rows<M, SPW, S4_OCT>(sc, rc, gc, dd);
 #pragma unroll
                         for (int u = 0; u < SPW; ++u) {
                             const int t = SPW * w + u;
@@ -1449,7 +1455,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                                 }
                             }
                             u32x2_t dd[SPW];
-                            adc16_rows<M, SPW, S4_OCT, TWO>(sc, tab, rc, dd);
+                            adc16_rows<M, SPW, S4_OCT, TWO>(sc, rc, gc, dd);
 #pragma unroll
                             for (int u = 0; u < SPW; ++u) {
                                 const bool ok = srow[u] < nrows && (srow[u] * 64 + lane < len);
@@ -1561,7 +1567,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                         const int iter = iter0 + k * NW;
                         const int base = iter * 64 * U;
                         u32x2_t dd[U];
-                        adc16_rows<M, U, S4_OCT, TWO>(ring[k], tab, rc, dd);
+                        adc16_rows<M, U, S4_OCT, TWO>(ring[k], rc, gc, dd);
                         // the set's next rows are requested as soon as its words have been consumed (the loads target the same registers:
                         // no copies).  Unconditional -- past the chunk the descriptor returns zeros -- so that every path through the
                         // loop has the same number of loads in flight and the wait before a set's use is vmcnt((PF - 1) * U), not vmcnt(0)
@@ -1620,13 +1626,13 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                     // TWO: B3b is also behind the last gather of every wave's main pass, so copy 1 ends here -- its slots take the
                     // per-query lists, and this gather reads copy 0 alone.  Its constants are derived here (the mask is laundered: hoisted,
                     // they would be eight more registers across the main pass)
-                    RotConsts<M> rc0;
+                    Adc16Consts<M, TWO> gc0;
                     if constexpr (TWO) {
-                        rc0 = rc;
-                        uint32_t keep0 = ~4u;
+                        gc0 = gc;
+                        uint32_t keep0 = ~8u;  // (the copy's bit of the entry address; the table's base is 16-byte aligned)
                         asm volatile("" : "+v"(keep0));
 #pragma unroll
-                        for (int t = 0; t < M; ++t) rc0.cj[t] = rc.cj[t] & keep0;
+                        for (int t = 0; t < M; ++t) gc0.c[t] = gc.c[t] & keep0;
                     }
                     if (pn > 0) {
                         const int nreg = (pn + 127) >> 7;  // registers that hold a position
@@ -1643,8 +1649,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                             CodeWords<M> cc[1];
                             cc[0] = cw[h];
                             u32x2_t d1[1];
-                            if constexpr (TWO) adc16_rows<M, 1, S4_OCT, true>(cc, tab, rc0, d1);
-                            else adc16_rows<M, 1, S4_OCT>(cc, tab, rc, d1);
+                            if constexpr (TWO) adc16_rows<M, 1, S4_OCT, true>(cc, rc, gc0, d1);
+                            else adc16_rows<M, 1, S4_OCT>(cc, rc, gc, d1);
                             // (requested once the row's words have been consumed, as in the main pass: the load targets the same registers;
                             // requested earlier it lands in new ones, and the copy at the loop's end waits for it with vmcnt(0))
                             cw[h] = load_code_buf<M>(rs, on_of(it + 2) ? (int)(h ? (pp[0] >> 16) : (pp[0] & 0xffffu)) : len);

@@ -741,19 +741,39 @@ __device__ __forceinline__ int wave_filter_approx(uint64_t* rk, int cnt, float m
 
 // float32 ADC sums of one candidate for G queries at once: the LDS table interleaves the queries,
 // tab[k][j][g], so ONE ds_read (b32 for G=1, b64 for G=2) serves all G queries of the workgroup.
+// adc32_sh: log2(M * G * 4 bytes), one k-row of the table; the addresses are gather_addr's (scan_common.h): one instruction per
+// entry, except at M = 16 with four queries -- rows of 256 bytes -- which keeps the two-instruction form.
 template <int M, int G>
-__device__ __forceinline__ void adc32g(const CodeWords<M>& c, const char* __restrict__ tab, const RotConsts<M>& rc,
-                                       float (&out)[G]) {
-    constexpr int SH = ((M == 4) ? 4 : (M == 8 ? 5 : 6)) + (G == 2 ? 1 : 0);  // log2(M * G * 4 bytes)
+static constexpr int adc32_sh() { return ((M == 4) ? 4 : (M == 8 ? 5 : 6)) + (G == 4 ? 2 : (G == 2 ? 1 : 0)); }
+template <int M, int G>
+using Adc32Consts = GatherConsts<M, adc32_sh<M, G>()>;
+template <int M, int G>
+__device__ __forceinline__ Adc32Consts<M, G> adc32_consts(const RotConsts<M>& rc, const char* tab) {
+    return make_gather<M, adc32_sh<M, G>()>(rc, tab, G == 4 ? 2 : (G == 2 ? 1 : 0));
+}
+
+// a candidate's M table reads, the addresses ahead of the reads (the hazard of gather_addr) in groups of at most eight; at M = 16 in
+// groups of four: sixteen addresses ahead of the first read spilled in the one-query forms
+template <int M, typename VT, typename GC>
+__device__ __forceinline__ void adc32_gather(const GC& gc, const uint32_t (&D)[(M + 3) / 4], VT (&f)[M]) {
+    constexpr int GRP = M == 16 ? 4 : M;
+#pragma unroll
+    for (int t0 = 0; t0 < M; t0 += GRP) {
+        uint32_t a[GRP];
+#pragma unroll
+        for (int i = 0; i < GRP; ++i) a[i] = gather_addr(gc, D, t0 + i);
+#pragma unroll
+        for (int i = 0; i < GRP; ++i) f[t0 + i] = gather_ld<VT>(a[i]);
+    }
+}
+
+template <int M, int G>
+__device__ __forceinline__ void adc32g(const CodeWords<M>& c, const RotConsts<M>& rc, const Adc32Consts<M, G>& gc, float (&out)[G]) {
     uint32_t D[(M + 3) / 4];
     rot_words<M>(c, rc, D);
     if constexpr (G == 1) {
         float f[M];
-#pragma unroll
-        for (int t = 0; t < M; ++t) {
-            const uint32_t k = __builtin_amdgcn_ubfe(D[t >> 2], rc.sh[t & 3], 8);
-            f[t] = *reinterpret_cast<const float*>(tab + ((k << SH) | rc.cj[t]));
-        }
+        adc32_gather<M>(gc, D, f);
 #pragma unroll
         for (int st = 1; st < M; st <<= 1)
 #pragma unroll
@@ -762,11 +782,7 @@ __device__ __forceinline__ void adc32g(const CodeWords<M>& c, const char* __rest
     } else {
         // the two queries' entries sit side by side: one ds_read_b64 per table entry, one packed add per tree node
         f32x2_t f[M];
-#pragma unroll
-        for (int t = 0; t < M; ++t) {
-            const uint32_t k = __builtin_amdgcn_ubfe(D[t >> 2], rc.sh[t & 3], 8);
-            f[t] = *reinterpret_cast<const f32x2_t*>(tab + ((k << SH) | (rc.cj[t] << 1)));
-        }
+        adc32_gather<M>(gc, D, f);
 #pragma unroll
         for (int st = 1; st < M; st <<= 1)
 #pragma unroll
@@ -785,18 +801,12 @@ template <> struct AdcVec<2> { typedef f32x2_t type; };
 template <> struct AdcVec<4> { typedef f32x4_t type; };
 
 template <int M, int G>
-__device__ __forceinline__ void adc32_issue(const CodeWords<M>& c, const char* __restrict__ tab, const RotConsts<M>& rc,
+__device__ __forceinline__ void adc32_issue(const CodeWords<M>& c, const RotConsts<M>& rc, const Adc32Consts<M, G>& gc,
                                             typename AdcVec<G>::type (&f)[M]) {
     typedef typename AdcVec<G>::type VT;
-    constexpr int LG = (G == 2) ? 1 : 2;
-    constexpr int SH = ((M == 4) ? 4 : (M == 8 ? 5 : 6)) + LG;  // log2(M * G * 4 bytes)
     uint32_t D[(M + 3) / 4];
     rot_words<M>(c, rc, D);
-#pragma unroll
-    for (int t = 0; t < M; ++t) {
-        const uint32_t k = __builtin_amdgcn_ubfe(D[t >> 2], rc.sh[t & 3], 8);
-        f[t] = *reinterpret_cast<const VT*>(tab + ((k << SH) | (rc.cj[t] << LG)));
-    }
+    adc32_gather<M>(gc, D, f);
 }
 
 template <int M, int G>
@@ -901,6 +911,7 @@ __device__ __forceinline__ void scan2_group(const WorkItem* __restrict__ items_a
     const long long clk_tab_end = CIS_CLK();
     (void)clk_tab_end;
     const RotConsts<M> rc = make_rot<M>(lane);
+    const Adc32Consts<M, G> gc = adc32_consts<M, G>(rc, tab);
     const int Lw = (L + NW - 1) / NW;
     // wave-uniform by construction; tell the compiler so (scalar loop control, scalar tail test)
     const int len = __builtin_amdgcn_readfirstlane(it0_len);
@@ -941,17 +952,17 @@ __device__ __forceinline__ void scan2_group(const WorkItem* __restrict__ items_a
         float d[U][G];
         if constexpr (G >= 2) {
             typename AdcVec<G>::type fbuf[2][M];
-            adc32_issue<M, G>(cur[0], tab, rc, fbuf[0]);
+            adc32_issue<M, G>(cur[0], rc, gc, fbuf[0]);
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                if (u + 1 < U) adc32_issue<M, G>(cur[u + 1], tab, rc, fbuf[(u + 1) & 1]);
+                if (u + 1 < U) adc32_issue<M, G>(cur[u + 1], rc, gc, fbuf[(u + 1) & 1]);
                 __builtin_amdgcn_sched_barrier(0);
                 adc32_reduce<M, G>(fbuf[u & 1], d[u]);
                 __builtin_amdgcn_sched_barrier(0);
             }
         } else {
 #pragma unroll
-            for (int u = 0; u < U; ++u) adc32g<M, G>(cur[u], tab, rc, d[u]);
+            for (int u = 0; u < U; ++u) adc32g<M, G>(cur[u], rc, gc, d[u]);
         }
         // Fast path: one compare + ballot per (candidate row, query), ONE branch if no mask is set.  Lanes past
         // the end of the chunk (last iteration only) get NaN distances, which never compare <=; the duplicate

@@ -375,6 +375,60 @@ __device__ __forceinline__ void rot_words(const CodeWords<M>& c, const RotConsts
     }
 }
 
+// The LDS address of a rotated gather: entry (k, j(t, lane)) of a table whose k-rows are 1 << SH bytes, k = the byte of D that step
+// t uses.  ONE instruction where the chip has the byte dot product: v_dot4_u32_u8 addr, D, sel, c with sel = 1 << SH in the byte this
+// lane uses at sub-step t & 3 and zero in the other three -- k * (1 << SH) + c, at most 255 * 128 + c: nothing carries between the
+// bytes' products, and the three other bytes contribute nothing.  Else, and for rows of 256 bytes (the factor does not fit a byte), two:
+// v_bfe_u32 takes the byte, v_lshl_add_u32 shifts it and adds c.  Either way c holds the table's LDS base, so that the result feeds the
+// ds_read as it is (a pointer `tab + offset` costs one more add of the base per entry), and the addresses are the same numbers.
+// A ds_read needs its address three wait states after a dot instruction wrote it: the callers compute the addresses of a whole
+// pipeline unit before the unit's first read.  v_dot4_u32_u8 issues at the rate of either instruction it replaces (4.2 cycles per
+// wave-instruction and SIMD, profiles/scan_dot4_ab.txt).  The selectors depend on the row size, which differs between the tables of
+// one file, so they live beside the constants of a table (GatherConsts) and not in RotConsts.  The stream kernel (lopq_stream.hip)
+// keeps the two-instruction address written out: converted, its one-query form measured 1 % slower (same file).
+#if defined(__has_builtin)
+#if __has_builtin(__builtin_amdgcn_udot4)
+#define CIS_GATHER_DOT4 1
+#endif
+#endif
+#ifndef CIS_GATHER_DOT4
+#define CIS_GATHER_DOT4 0
+#endif
+template <int SH>
+static constexpr bool gather_dot4() { return CIS_GATHER_DOT4 && SH <= 7; }
+
+template <int M, int SH>
+struct GatherConsts {
+    uint32_t sel[4];  // dot4: the selector of sub-step tq, (1 << SH) << rc.sh[tq]; else rc.sh[tq]
+    uint32_t c[M];    // LDS byte address of row 0's entry for step t
+};
+
+// tab: the table in LDS; entry (k, j) at byte (k << SH) + (j << (2 + LG)) -- rc.cj[t] << LG (rc.cj may carry more: two_copy_rot)
+template <int M, int SH>
+__device__ __forceinline__ GatherConsts<M, SH> make_gather(const RotConsts<M>& rc, const void* tab, int LG) {
+    static_assert(SH >= 0 && (!gather_dot4<SH>() || (1 << SH) <= 255), "the row size is a factor of the byte dot product");
+    GatherConsts<M, SH> gc;
+    const uint32_t base = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)tab;
+#pragma unroll
+    for (int tq = 0; tq < 4; ++tq) gc.sel[tq] = gather_dot4<SH>() ? ((1u << SH) << rc.sh[tq]) : rc.sh[tq];
+#pragma unroll
+    for (int t = 0; t < M; ++t) gc.c[t] = base + (rc.cj[t] << LG);
+    return gc;
+}
+
+template <int M, int SH>
+__device__ __forceinline__ uint32_t gather_addr(const GatherConsts<M, SH>& gc, const uint32_t (&D)[(M + 3) / 4], int t) {
+#if CIS_GATHER_DOT4
+    if constexpr (gather_dot4<SH>()) return __builtin_amdgcn_udot4(D[t >> 2], gc.sel[t & 3], gc.c[t], false);
+#endif
+    return (__builtin_amdgcn_ubfe(D[t >> 2], gc.sel[t & 3], 8) << SH) + gc.c[t];
+}
+
+template <typename VT>
+__device__ __forceinline__ VT gather_ld(uint32_t addr) {
+    return *reinterpret_cast<const __attribute__((address_space(3))) VT*>((const __attribute__((address_space(3))) char*)(uintptr_t)addr);
+}
+
 // the same through a buffer descriptor that covers exactly the chunk being scanned: one 32-bit offset per
 // load instead of 64-bit address arithmetic, and positions past the end of the chunk read as zero
 typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
