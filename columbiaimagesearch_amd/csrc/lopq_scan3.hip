@@ -1015,9 +1015,15 @@ static size_t scan4_lds(int M, int K, int lcap, int nw) {
     return (size_t)K * M * S3G * 2 + (lists > samp ? lists : samp) + S3G * sizeof(Scan4Shared) + 32 + (size_t)S3G * nw * 4 + (S4_DS + 1) * sizeof(Slot4);
 }
 
-// row of sample t of ns over a chunk of nrows rows: t * nrows / ns.  t < ns <= nrows <= 1024 (a chunk is at most 65536 candidates), so the
-// product fits 32 bits: the 64-bit division this once was is a few hundred scalar instructions, several times per wave and slot.
-static __device__ __forceinline__ int sample_row(int t, int nrows, int ns) { return (int)(((uint32_t)t * (uint32_t)nrows) / (uint32_t)ns); }
+// row of sample t of ns over a chunk of nrows rows: t * nrows / ns for t < ns, nrows (a row past the chunk: reads zeros) from ns on.
+// ns <= nrows <= 1024 (a chunk is at most 65536 candidates), so x = min(t, ns) * nrows <= 2^20, and the quotient is one multiplication by
+// inv = floor((2^31 - 1) / ns) + 1, taken once per slot: x * inv / 2^31 = x / ns + x * e / (ns * 2^31) with 0 <= e = inv * ns - 2^31 <= ns,
+// and x * e <= 2^30 keeps the second term below 1 / ns -- the floor is exact, and t >= ns gives nrows without a branch.  A division per
+// row was ~40 instructions, four times per wave and round of the sample.
+static __device__ __forceinline__ uint32_t sample_inv(int ns) { return 0x7fffffffu / (uint32_t)ns + 1u; }
+static __device__ __forceinline__ int sample_row(int t, int nrows, int ns, uint32_t inv) {
+    return (int)__umulhi(2u * (uint32_t)(t < ns ? t : ns) * (uint32_t)nrows, inv);
+}
 
 template <int M, int U, int NW, int WPE, int LCAPT>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void k_adc_scan4(
@@ -1051,7 +1057,6 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
     Scan4Shared* sh = reinterpret_cast<Scan4Shared*>(reinterpret_cast<char*>(lists) + LIST_B);
     uint16_t* thr1 = reinterpret_cast<uint16_t*>(sh + G);  // [G] collection thresholds + 1, packed like the sums
     int* s_flag = reinterpret_cast<int*>(thr1 + 4);
-    int* s_cnt = s_flag + 1;                               // [G] zeroed per slot, read by nobody: to go with the next change of this kernel's code
     int* wcnt = reinterpret_cast<int*>(reinterpret_cast<char*>(thr1) + 32);  // [G][NW] entries of the wave-private lists
     Slot4* sd = reinterpret_cast<Slot4*>(reinterpret_cast<char*>(thr1) + 32 + G * NW * 4);
     constexpr int WCAP = LCAPT / NW;  // every wave appends to its own quarter of a query's list (no LDS atomic in the loop)
@@ -1312,7 +1317,6 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                     sh[g].q = q;
                     sh[g].ext = (g < ng) ? __hip_atomic_load(&qbound[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0x7ff0000000000000ull;
                     sh[g].cnt = 0;
-                    s_cnt[g] = 0;
                     if (g < ng) {
                         item_slack[2 * (int64_t)item + 0] = __double2float_ru(ub * ((double)M + 0.1));
                         item_slack[2 * (int64_t)item + 1] = __double2float_ru(ub);
@@ -1328,6 +1332,23 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                 }
                 const int nrows = (len + 63) >> 6;
                 constexpr bool MULTI = LCAPT > 504;  // long chunks: a tenth of the rows as the sample, bucket minima instead of the sums
+                // The main pass's code rows travel PF iterations of a wave ahead of their use (a ring of PF register sets, see there).  Its
+                // first PF x U rows are requested in front of barrier B2, at the end of the sample pass: the threshold phase issues no
+                // global load and covers their round trip, which every wave otherwise met exposed at the head of its main pass.
+                // (M = 16 already spills: there the rows stay requested behind B3.)
+                constexpr int PF = CIS_S4_PF;
+                constexpr bool RING_EARLY = M <= 8;
+                CodeWords<M> ring[PF][U];
+                auto ring_first = [&]() {
+#pragma unroll
+                    for (int k = 0; k < PF; ++k) {
+#pragma unroll
+                        for (int u = 0; u < U; ++u) ring[k][u] = load_code_buf<M>(rs, (w + k * NW) * 64 * U + u * 64 + lane);  // past the chunk: zeros, never consumed
+                        // (the sets are requested in the order the loop consumes them: entering the loop with set 0 as the NEWEST request would
+                        // make the wait at the loop head vmcnt(0) on every trip)
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                };
                 if constexpr (!MULTI) {
                     // sample rows: t * nrows / ns for t < ns = min(nrows, NS) (all rows when the chunk has <= NS of them)
                     const int ns = nrows < NS ? nrows : NS;
@@ -1336,10 +1357,11 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                     static_assert(NS % (2 * NW) == 0, "sample rows come in pairs per wave");
                     CodeWords<M> sc[SPW];
                     int srow[SPW];
+                    const uint32_t sinv = sample_inv(ns);
 #pragma unroll
                     for (int i = 0; i < SPW; ++i) {
                         const int t = SPW * w + i;
-                        srow[i] = t < ns ? sample_row(t, nrows, ns) : nrows;
+                        srow[i] = sample_row(t, nrows, ns, sinv);
                         sc[i] = load_code_buf<M>(rs, srow[i] * 64 + lane);  // rows past the chunk read zeros (masked below)
                     }
                     S3_CTR(11, S3_CLK() - c0);
@@ -1360,6 +1382,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                             }
                         }
                     }
+                    if constexpr (RING_EARLY) ring_first();
                     lds_barrier();  // B2
                     S3_CTR(3, S3_CLK() - c0);
                     // ---- thresholds: wave g serves query g ---------------------------------------------------------------------------------
@@ -1424,15 +1447,34 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                     ns = ns > nsx ? nsx : ns;
                     ns = ns < nrows ? ns : nrows;
                     constexpr int SPW = 4;  // sample rows per wave and round
-                    const int rounds = (ns + NW * SPW - 1) / (NW * SPW);
-                    // the first round's code rows travel while the tables are staged
-                    CodeWords<M> sc[SPW];
-                    int srow[SPW];
+                    // (sets x rows 2 x 4, 4 x 2, 6 x 2, 3 x 4 and 8 x 1 measured the same sample pass on C4; 4 x 2 is sixteen registers at
+                    // M = 8 and leaves the M = 16 form without a spill: profiles/scan4_sample_ring_ab.txt)
+                    constexpr int SRS = 2;  // rows of a register set
+                    constexpr int SD = 4;   // register sets of a wave: its next SD * SRS rows are in flight
+                    static_assert(SPW % SRS == 0, "a set does not straddle rounds");
+                    const uint32_t sinv = sample_inv(ns);
+                    // Sample row t = (r * NW + w) * SPW + i belongs to wave w in round r: the wave's j-th row is t_of(j), and it has rows_w of
+                    // them below ns.  The rows travel in a ring of SD register sets of SRS rows with static names (the loop is unrolled SD
+                    // times), as in the main pass: a set's next rows -- SD sets on -- are requested into the set's own registers once
+                    // adc16_rows has consumed its words, and the wait before a set's use is vmcnt((SD - 1) * SRS).  (One round ahead in fresh
+                    // registers, copied into place at the round's end, made every round end on vmcnt(0): the sample cost twice the main
+                    // pass's time per row, profiles/scan4_sample_ring_ab.txt.)  A request past the sample asks for row nrows, where the
+                    // descriptor returns zeros without a memory access.
+                    auto t_of = [&](int j) -> int { return ((j / SPW) * NW + w) * SPW + (j % SPW); };
+                    int rows_w = ns % (NW * SPW) - SPW * w;
+                    rows_w = (ns / (NW * SPW)) * SPW + (rows_w < 0 ? 0 : (rows_w > SPW ? SPW : rows_w));
+                    const int nsets = (rows_w + SRS - 1) / SRS;
+                    CodeWords<M> sring[SD][SRS];
+                    int srow[SD][SRS];
+                    // the first SD sets travel while the tables are staged
 #pragma unroll
-                    for (int i = 0; i < SPW; ++i) {
-                        const int t = SPW * w + i;
-                        srow[i] = t < ns ? sample_row(t, nrows, ns) : nrows;
-                        sc[i] = load_code_buf<M>(rs, srow[i] * 64 + lane);  // rows past the chunk read zeros (masked below)
+                    for (int k = 0; k < SD; ++k) {
+#pragma unroll
+                        for (int i = 0; i < SRS; ++i) {
+                            srow[k][i] = sample_row(t_of(k * SRS + i), nrows, ns, sinv);
+                            sring[k][i] = load_code_buf<M>(rs, srow[k][i] * 64 + lane);  // rows past the chunk read zeros (masked below)
+                        }
+                        __builtin_amdgcn_sched_barrier(0);  // (in the order of their use, like the main pass's sets)
                     }
                     S3_CTR(11, S3_CLK() - c0);
                     lds_barrier();  // B1: tables and scales visible
@@ -1441,34 +1483,32 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                     {
                         uint32_t bm0 = 0xffffffffu, bm1 = 0xffffffffu;
 #pragma unroll 1
-                        for (int r = 0; r < rounds; ++r) {
-                            CodeWords<M> nsc[SPW];
-                            int nrow[SPW];
-                            if constexpr (MULTI) {
-                                if (r + 1 < rounds) {
+                        for (int s0 = 0; s0 < nsets; s0 += SD) {
 #pragma unroll
-                                    for (int i = 0; i < SPW; ++i) {
-                                        const int t = ((r + 1) * NW + w) * SPW + i;
-                                        nrow[i] = t < ns ? sample_row(t, nrows, ns) : nrows;
-                                        nsc[i] = load_code_buf<M>(rs, nrow[i] * 64 + lane);
+                            for (int k = 0; k < SD; ++k) {
+                                const int st = s0 + k;
+                                // (wave-uniform.  Only the sums are skipped for a set past the wave's last, never its request: an exit from inside
+                                // the group reaches the back edge with fewer loads in flight on one path, and every wait of a trip becomes the
+                                // count of that path)
+                                if (st < nsets) {
+                                    u32x2_t dd[SRS];
+                                    adc16_rows<M, SRS, S4_OCT, TWO>(sring[k], rc, gc, dd);
+#pragma unroll
+                                    for (int u = 0; u < SRS; ++u) {
+                                        const bool ok = srow[k][u] * 64 + lane < len;  // (false for row nrows as well: len <= 64 nrows)
+                                        bm0 = pk_min_u16(bm0, ok ? dd[u][0] : 0xffffffffu);
+                                        bm1 = pk_min_u16(bm1, ok ? dd[u][1] : 0xffffffffu);
                                     }
                                 }
-                            }
-                            u32x2_t dd[SPW];
-                            adc16_rows<M, SPW, S4_OCT, TWO>(sc, rc, gc, dd);
+                                // unconditional, so that every path has the same number of loads in flight
 #pragma unroll
-                            for (int u = 0; u < SPW; ++u) {
-                                const bool ok = srow[u] < nrows && (srow[u] * 64 + lane < len);
-                                bm0 = pk_min_u16(bm0, ok ? dd[u][0] : 0xffffffffu);
-                                bm1 = pk_min_u16(bm1, ok ? dd[u][1] : 0xffffffffu);
-                            }
-                            if constexpr (MULTI) {
-                                if (r + 1 < rounds) {
-#pragma unroll
-                                    for (int i = 0; i < SPW; ++i) { sc[i] = nsc[i]; srow[i] = nrow[i]; }
+                                for (int i = 0; i < SRS; ++i) {
+                                    srow[k][i] = sample_row(t_of((st + SD) * SRS + i), nrows, ns, sinv);
+                                    sring[k][i] = load_code_buf<M>(rs, srow[k][i] * 64 + lane);
                                 }
                             }
                         }
+                        if constexpr (RING_EARLY) ring_first();
                         u32x2_t bm;
                         bm[0] = bm0; bm[1] = bm1;
                         reinterpret_cast<u32x2_t*>(samp)[w * 64 + lane] = bm;  // [NW][64] x four queries
@@ -1538,16 +1578,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                     // code rows travel PF iterations of this wave ahead of their use (a ring of PF register sets, the loop unrolled PF
                     // times so that the sets are static): one iteration ahead left the wave waiting at the end of most iterations --
                     // an iteration is ~100 instructions, a code row comes from L2 / Infinity Cache / HBM
-                    constexpr int PF = CIS_S4_PF;
-                    CodeWords<M> ring[PF][U];
-#pragma unroll
-                    for (int k = 0; k < PF; ++k) {
-#pragma unroll
-                        for (int u = 0; u < U; ++u) ring[k][u] = load_code_buf<M>(rs, (w + k * NW) * 64 * U + u * 64 + lane);  // past the chunk: zeros, never consumed
-                        // (the sets are requested in the order the loop consumes them: entering the loop with set 0 as the NEWEST request would
-                        // make the wait at the loop head vmcnt(0) on every trip)
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
+                    if constexpr (!RING_EARLY) ring_first();
                     int wcur[G];
 #pragma unroll
                     for (int g = 0; g < G; ++g) wcur[g] = 0;
