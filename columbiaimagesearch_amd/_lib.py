@@ -63,6 +63,11 @@ _PROTOS = {
     "cis_index_size": (c_int64, [c_void_p]),
     "cis_index_add_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, POINTER(c_int64), POINTER(c_int64),
                                   c_void_p, c_void_p]),
+    "cis_index_remove_dev": (c_int, [c_void_p, c_void_p, c_int64, POINTER(c_int64), c_void_p, c_void_p]),
+    "cis_index_remove": (c_int, [c_void_p, c_void_p, c_int64, POINTER(c_int64)]),
+    "cis_index_remove_profile": (c_int, [c_void_p, c_void_p]),
+    "cis_index_sub_remote_counts": (c_int, [c_void_p, c_void_p]),
+    "cis_index_sub_remote_counts_dev": (c_int, [c_void_p, c_void_p, c_void_p]),
     "cis_l2_normalize_dev": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p]),
     "cis_index_cell_counts_dev": (c_int, [c_void_p, c_void_p, c_void_p]),
     "cis_index_add_remote_counts_dev": (c_int, [c_void_p, c_void_p, c_void_p]),

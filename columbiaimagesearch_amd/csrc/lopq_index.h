@@ -105,6 +105,8 @@ struct cis_index {
     struct ProfRec { hipEvent_t ev[6]; bool has_scan; };  // ev[5]: just before the scan kernel (after slot building)
     std::vector<ProfRec> prof;
     double prof_ms[5] = {0, 0, 0, 0, 0};
+    hipEvent_t rm_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // removal (lopq_remove.hip) with profiling on: start / set built / marked / compacted
+    double rm_ms[3] = {0, 0, 0};    // stage times of the last such removal: set build, mark, touched list + compaction (own store)
     int64_t prof_launches = 0;
 
     bool owns(int64_t cell) const {
@@ -114,8 +116,17 @@ struct cis_index {
     }
 };
 
+// statistics words of an insert or a removal (device memory, ix->d_stats; copied into pinned host memory, ix->h_ins, when the host
+// needs them)
+enum { INS_ACC_OWN = 0, INS_INVALID = 1, INS_NTOTAL = 2, INS_MAXCELL = 3, INS_NONEMPTY = 4, INS_ERR = 5, INS_ACC_GHOST = 6,
+       INS_REMOTE_PLAIN = 7, INS_OVERFLOW = 8, INS_REM_OWN = 9, INS_REM_GHOST = 10, INS_WORDS = 11 };
+
 // Makes the device arrays exist (empty index: offsets all zero) -- called at the head of every search.
 int cis_index_ready(cis_index* ix);
+
+// lopq_index.hip: n_total / max_cell / nonempty_cells / nb_indexed from the global cell sizes (k_gcount_stats on `st`); copies ALL
+// statistics words to ix->h_ins and waits for the stream
+int cis_index_refresh_stats(cis_index* ix, hipStream_t st);
 
 // lopq_host.hip: a handle that is being destroyed leaves the list of handles whose copy-out is still to be enqueued
 void cis_host_forget(cis_index* ix);

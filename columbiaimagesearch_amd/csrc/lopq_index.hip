@@ -38,99 +38,7 @@
 #include <algorithm>
 
 #include "lopq_index.h"
-
-// ================================================================================================
-// device-wide exclusive scan (tile sums -> scan of the sums -> add)
-// ================================================================================================
-static const int SCAN_T = 256, SCAN_PER = 8, SCAN_TILE = SCAN_T * SCAN_PER;
-
-template <typename T>
-__device__ __forceinline__ T wave_incl_scan(T v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const T u = __shfl_up(v, o);
-        if (lane >= o) v += u;
-    }
-    return v;
-}
-
-// exclusive scan of one value per thread over a block of SCAN_T threads; returns the block total in *total
-template <typename T>
-__device__ __forceinline__ T block_excl_scan(T v, T* sh /* [SCAN_T / 64 + 1] */, T* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const T inc = wave_incl_scan(v);
-    if (lane == 63) sh[w] = inc;
-    __syncthreads();
-    T base = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < SCAN_T / 64; ++i) {
-        const T s = sh[i];
-        base += (i < w) ? s : (T)0;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return base + inc - v;
-}
-
-template <typename TI, typename TO>
-__global__ __launch_bounds__(SCAN_T) void k_scan_tiles(const TI* __restrict__ in, TO* __restrict__ out, TO* __restrict__ sums, int64_t n) {
-    __shared__ TO sh[SCAN_T / 64 + 1];
-    const int64_t base = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * SCAN_PER;
-    TO v[SCAN_PER];
-    TO s = 0;
-#pragma unroll
-    for (int i = 0; i < SCAN_PER; ++i) {
-        v[i] = (base + i < n) ? (TO)in[base + i] : (TO)0;
-        s += v[i];
-    }
-    TO tot;
-    TO run = block_excl_scan<TO>(s, sh, &tot);
-#pragma unroll
-    for (int i = 0; i < SCAN_PER; ++i) {
-        if (base + i < n) out[base + i] = run;
-        run += v[i];
-    }
-    if (threadIdx.x == 0) sums[blockIdx.x] = tot;
-}
-
-// one workgroup: exclusive scan of the tile sums in place, the grand total to total[0] (and total2[0], may be null)
-template <typename TO>
-__global__ __launch_bounds__(SCAN_T) void k_scan_sums(TO* __restrict__ sums, int64_t m, TO* __restrict__ total, int64_t* __restrict__ total2) {
-    __shared__ TO sh[SCAN_T / 64 + 1];
-    TO carry = 0;
-    for (int64_t b = 0; b < m; b += SCAN_T) {
-        const int64_t i = b + threadIdx.x;
-        const TO v = i < m ? sums[i] : (TO)0;
-        TO tot;
-        const TO e = block_excl_scan<TO>(v, sh, &tot);
-        if (i < m) sums[i] = carry + e;
-        carry += tot;
-    }
-    if (threadIdx.x == 0) {
-        if (total) total[0] = carry;
-        if (total2) total2[0] = (int64_t)carry;
-    }
-}
-
-template <typename TO>
-__global__ __launch_bounds__(SCAN_T) void k_scan_add(TO* __restrict__ out, const TO* __restrict__ sums, int64_t n) {
-    const TO add = sums[blockIdx.x];
-    const int64_t base = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * SCAN_PER;
-#pragma unroll
-    for (int i = 0; i < SCAN_PER; ++i)
-        if (base + i < n) out[base + i] += add;
-}
-
-// out[i] = sum of in[0 .. i); total (device, may be null) = sum of all; sums: scratch of ceil(n / SCAN_TILE) + 1 elements
-template <typename TI, typename TO>
-static void dev_exclusive_scan(const TI* in, TO* out, int64_t n, TO* sums, TO* total, int64_t* total2, hipStream_t st) {
-    const int64_t m = n > 0 ? ceil_div(n, SCAN_TILE) : 0;
-    if (m > 0) hipLaunchKernelGGL((k_scan_tiles<TI, TO>), dim3((unsigned)m), dim3(SCAN_T), 0, st, in, out, sums, n);
-    hipLaunchKernelGGL((k_scan_sums<TO>), dim3(1), dim3(SCAN_T), 0, st, sums, m, total, total2);
-    if (m > 1) hipLaunchKernelGGL((k_scan_add<TO>), dim3((unsigned)m), dim3(SCAN_T), 0, st, out, (const TO*)sums, n);
-}
+#include "dev_scan.h"
 
 // ================================================================================================
 // stable LSD radix sort of (key uint32, value uint32), 8 bits per pass, one wave per tile of 2048 items
@@ -187,9 +95,7 @@ __global__ __launch_bounds__(64) void k_rs_scatter(const uint32_t* __restrict__ 
 // ================================================================================================
 // insert kernels
 // ================================================================================================
-// statistics words (device memory; copied into pinned host memory when the host needs them)
-enum { INS_ACC_OWN = 0, INS_INVALID = 1, INS_NTOTAL = 2, INS_MAXCELL = 3, INS_NONEMPTY = 4, INS_ERR = 5, INS_ACC_GHOST = 6,
-       INS_REMOTE_PLAIN = 7, INS_OVERFLOW = 8, INS_WORDS = 9 };
+// (the statistics words INS_*: lopq_index.h)
 
 __device__ __forceinline__ bool dev_owns(int64_t cell, const int32_t* __restrict__ owner, int rank, int world) {
     if (world <= 1) return true;
@@ -795,6 +701,8 @@ extern "C" void cis_index_destroy(cis_index* ix) {
     for (DevBuf* b : bufs) b->release();
     ix->own.release();
     ix->ghost.release();
+    for (hipEvent_t e : ix->rm_ev)
+        if (e) (void)hipEventDestroy(e);
     if (ix->h_totals) (void)hipHostFree(ix->h_totals);
     if (ix->h_ins) (void)hipHostFree(ix->h_ins);
     delete ix;
@@ -1016,7 +924,7 @@ static int stats_fetch(cis_index* ix, hipStream_t st) {
     return CIS_OK;
 }
 
-static int refresh_stats(cis_index* ix, hipStream_t st) {
+int cis_index_refresh_stats(cis_index* ix, hipStream_t st) {
     int64_t* stats = ix->d_stats.as<int64_t>();
     CIS_CHECK_HIP(hipMemsetAsync(stats + INS_NTOTAL, 0, 3 * sizeof(int64_t), st));
     const int64_t nc = ix->ncells;
@@ -1079,7 +987,7 @@ static int index_add_dev(cis_index* ix, const int64_t* d_ids, const uint16_t* d_
     if (d_cell_delta)
         hipLaunchKernelGGL(k_cell_delta, dim3(grid_for(ix->ncells, 256)), dim3(256), 0, st, (const int64_t*)ix->d_gcount.as<int64_t>(),
                            d_cell_delta, ix->ncells);
-    if (!ix->stats_fresh) CIS_TRY(refresh_stats(ix, st));  // (an in-place batch read them back with its own statistics)
+    if (!ix->stats_fresh) CIS_TRY(cis_index_refresh_stats(ix, st));  // (an in-place batch read them back with its own statistics)
     if (n_added) *n_added = added;
     if (n_invalid) *n_invalid = invalid;
     return CIS_OK;
@@ -1150,7 +1058,7 @@ static int add_remote_dev(cis_index* ix, const int64_t* d_delta, hipStream_t st)
     CIS_TRY(stats_zero(ix, st));
     hipLaunchKernelGGL(k_add_remote, dim3(grid_for(ix->ncells, 256)), dim3(256), 0, st, ix->d_gcount.as<int64_t>(), d_delta, ix->ncells,
                        (const int32_t*)ix->d_owner.as<int32_t>(), ix->rank, ix->world, ix->d_stats.as<int64_t>());
-    CIS_TRY(refresh_stats(ix, st));
+    CIS_TRY(cis_index_refresh_stats(ix, st));
     CIS_REQUIRE(ix->h_ins[INS_ERR] == 0, "negative per-cell count");
     return CIS_OK;
 }

@@ -321,6 +321,45 @@ class ShardedSearcher(object):
             print("Could not push {} codes (out of range for this model, or negative ids).".format(bad.value))
         return int(added.value)
 
+    def remove_ids_dev(self, ids):
+        """Remove items by device id (int64 tensor in HBM); EVERY rank is given the same ids.  Each rank removes them from the cells
+        it owns (LOPQSearcherHIP.remove_ids_dev), the per-cell removed counts are summed over the ranks (staged through the host on
+        gloo, as add_codes_routed_dev stages its all-reduce) and subtracted from the sizes of the cells the others own
+        (cis_index_sub_remote_counts_dev), so that every rank ends with the whole cell-size table.  Ordered against the searches in
+        flight like an insert.  Returns the number of items removed over all shards -- the same on every rank."""
+        import torch
+        import torch.distributed as dist
+        from . import _lib
+        L = _lib.lib()
+        V = self.local.model.V
+        dev = ids.device
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        self._insert_fence()
+        try:
+            delta = torch.empty(V * V, dtype=torch.int64, device=dev)
+            self.local.remove_ids_dev(ids, cell_delta=delta)
+            if dist.get_backend(self.group) != "nccl":
+                d_h = delta.cpu()
+                dist.all_reduce(d_h, group=self.group)
+                delta.copy_(d_h)
+            else:
+                dist.all_reduce(delta, group=self.group)
+            _lib.check(L.cis_index_sub_remote_counts_dev(self.local._ix, delta.data_ptr(), stream))
+            removed = int(delta.sum().item())
+        finally:
+            self._insert_release()
+        self.local.nb_indexed = int(L.cis_index_size(self.local._ix))
+        return removed
+
+    def remove_ids(self, ids):
+        """remove_ids_dev on caller ids of any kind (mapped through LOPQSearcherHIP.device_ids_of; unknown ids are ignored)."""
+        import torch
+        if isinstance(ids, np.ndarray) and ids.dtype.kind in "iu":
+            dev_ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        else:
+            dev_ids = self.local.device_ids_of(ids)
+        return self.remove_ids_dev(torch.as_tensor(dev_ids).cuda())
+
     def get_nb_indexed(self):
         return self.local.get_nb_indexed()
 
@@ -763,6 +802,13 @@ class GridSearcher(object):
         if self.row is not None:
             return self.row.add_codes_routed_dev(coarse, fine, ids, dedup=dedup)
         return self.local.add_codes_dev(coarse, fine, ids, dedup=dedup)[0]
+
+    def remove_ids_dev(self, ids):
+        """Remove items by device id from every copy of the index: EVERY rank is given the same ids (no column collective: the
+        copies hold the same items).  Returns the number removed from one copy."""
+        if self.row is not None:
+            return self.row.remove_ids_dev(ids)
+        return self.local.remove_ids_dev(ids)
 
     def get_nb_indexed(self):
         return self.local.get_nb_indexed()

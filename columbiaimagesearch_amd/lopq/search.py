@@ -319,6 +319,49 @@ class LOPQSearcherHIP(LOPQSearcherBase):
         if good_c:
             self.add_codes_array(np.array(good_c, dtype=np.uint16), np.array(good_f, dtype=np.uint8), good_ids)
 
+    # -- removal ---------------------------------------------------------------------------------
+    def _writable_handle(self):
+        if not self._ix:
+            raise ValueError("this searcher is closed")
+        if getattr(self, "_base", None) is not None:
+            raise ValueError("a view is read-only: remove through the searcher it was created from")
+        return self._ix
+
+    def remove_ids(self, ids):
+        """Remove every stored item whose id is in `ids` (caller ids of any kind): from every cell that holds it, every copy
+        inside a cell; kept items keep their order inside their cell.  Ids that are not stored (or were never given to this
+        searcher), repeated ids and negative ids are ignored; an empty list is a no-op.  Afterwards the index equals one built
+        by the same insert calls without those ids (include/cis_hip.h:cis_index_remove_dev), so a removed id may be inserted
+        again.  A non-integer id keeps its slot: a re-insert reuses it.  Returns the number of items removed."""
+        ix = self._writable_handle()
+        if isinstance(ids, np.ndarray) and ids.dtype.kind in "iu":
+            dev_ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        else:
+            dev_ids = self.device_ids_of(ids)  # unknown ids: -1, which the kernels ignore
+        removed = _lib.c_int64(0)
+        _lib.check(_lib.lib().cis_index_remove(ix, _lib.ptr(dev_ids), dev_ids.shape[0], _lib.ctypes.byref(removed)))
+        self.nb_indexed = int(_lib.lib().cis_index_size(ix))
+        return int(removed.value)
+
+    def remove_ids_dev(self, ids, cell_delta=None):
+        """remove_ids on an int64 tensor of DEVICE ids in HBM (what search_batch_dev returns; device_ids_of maps caller ids), by
+        kernels on the current stream (csrc/lopq_remove.hip); nothing travels through the host but the removed count.
+        cell_delta: optional int64 [V*V] tensor that receives the items removed per cell of this shard."""
+        import torch
+        ix = self._writable_handle()
+        if not (ids.is_cuda and ids.is_contiguous() and ids.dtype == torch.int64 and ids.dim() == 1):
+            raise ValueError("ids must be a contiguous int64 [n] tensor on the GPU")
+        V = self.model.V
+        if cell_delta is not None and not (cell_delta.is_cuda and cell_delta.is_contiguous() and cell_delta.dtype == torch.int64
+                                           and cell_delta.numel() == V * V):
+            raise ValueError("cell_delta must be a contiguous int64 [%d] tensor on the GPU" % (V * V))
+        removed = _lib.c_int64(0)
+        _lib.check(_lib.lib().cis_index_remove_dev(ix, ids.data_ptr(), int(ids.shape[0]), _lib.ctypes.byref(removed),
+                                                   None if cell_delta is None else cell_delta.data_ptr(),
+                                                   torch.cuda.current_stream(ids.device).cuda_stream))
+        self.nb_indexed = int(_lib.lib().cis_index_size(ix))
+        return int(removed.value)
+
     def get_cell(self, cell):
         """reference: lopq/lopq/search.py:372-382 -> [(id, LOPQCode), ...] in insertion order"""
         c0, c1 = int(cell[0]), int(cell[1])
@@ -617,7 +660,9 @@ class LOPQSearcherLMDB(LOPQSearcherBase):
     through ``id_lambda``.  The key/value store lives on the host (a dict) and is PERSISTENT at ``lmdb_path``: in LMDB when
     the ``lmdb`` module is importable (the reference's own files; without the module an existing ``data.mdb`` is opened
     read-only through lopq/lmdb_read.py), otherwise in an append-only log of the same key / value bytes (lopq/kvlog.py) -- a restart re-opens the index (cold start tested in tests/test_reference_surfaces.py); the
-    device index is rebuilt in key order before the first search after an insert."""
+    device index is rebuilt in key order before the first search after an insert.
+
+    Removal by id (LOPQSearcherHIP.remove_ids) is not offered here: the key/value store and its persistent log have no delete."""
 
     def __init__(self, model, lmdb_path=None, id_lambda=int):
         super(LOPQSearcherLMDB, self).__init__()

@@ -184,6 +184,29 @@ int cis_index_add(cis_index* ix, const int64_t* ids, const uint16_t* coarse, con
 int cis_index_add_dev(cis_index* ix, const int64_t* d_ids, const uint16_t* d_coarse, const uint8_t* d_fine, int64_t n,
                       int dedup, int64_t* n_added, int64_t* n_invalid, int64_t* d_cell_delta /* [V*V] accepted per cell, or NULL */,
                       void* stream);
+/* Removal by id, on the device (csrc/lopq_remove.hip; the reference's dict index cannot remove).  Every stored item whose id is in
+ * the list leaves the index: from every cell that holds it, every copy inside a cell (dedup = 0 inserts can store an id more than
+ * once).  Kept items keep their relative order inside their cell.  Ids that are not stored, ids that occur more than once in the
+ * list and negative ids are ignored; n = 0 is a no-op.  Afterwards the index equals one built by the same insert calls with the
+ * removed ids filtered out of every batch (cells, counts, every search route, the duplicate test of later inserts): a removed id
+ * may be inserted again and lands behind its cell's last item.  The storage of a cell does not shrink: its room stays, only its used
+ * end moves down (more slack for in-place inserts), and the next rebuild of the layout renews the slack as it does today.
+ * Like cis_index_add_dev the call enqueues kernels on `stream` and returns after the stream has drained (the removed count and the
+ * cell-size statistics are read back: its one host round trip).  n < 2^31.  *n_removed = items removed from THIS shard's cells.
+ * A view is read-only: removal through it returns CIS_EINVAL; removals from the base must be stream-ordered against the views'
+ * searches by the caller, like inserts.  On a cell-sharded index every rank is given the same ids; the id-only store of the other
+ * shards' cells drops them too, and the sizes of the cells that other shards own change ONLY through cis_index_sub_remote_counts
+ * (whatever insert mode built the index): sum the d_cell_delta arrays over the ranks and hand the sum to it. */
+int cis_index_remove_dev(cis_index* ix, const int64_t* d_ids, int64_t n, int64_t* n_removed,
+                         int64_t* d_cell_delta /* [V*V] items removed per cell of THIS shard, or NULL */, void* stream);
+int cis_index_remove(cis_index* ix, const int64_t* ids, int64_t n, int64_t* n_removed); /* host array: uploaded, then the above */
+/* Stage times in ms of the last cis_index_remove[_dev] on this handle that ran with profiling on (cis_index_set_profiling != 0; HIP events
+ * on the launch stream): ms[0] building the removal set, ms[1] the mark pass, ms[2] the touched-cell list and the compaction. */
+int cis_index_remove_profile(cis_index* ix, double ms[3]);
+/* The counterpart of cis_index_add_remote_counts: per-cell decrements [V*V] >= 0 for the cells owned by OTHER ranks (entries of
+ * owned cells are ignored).  A first pass checks that no count would go negative; if one would, CIS_EINVAL and nothing changes. */
+int cis_index_sub_remote_counts(cis_index* ix, const int64_t* delta);
+int cis_index_sub_remote_counts_dev(cis_index* ix, const int64_t* d_delta, void* stream);
 /* featsio.normfeatB64encode's normalisation (cufacesearch/cufacesearch/featurizer/featsio.py:13-22) on n device rows of d
  * values, in place, in the rows' dtype; zero rows stay zero. */
 int cis_l2_normalize_dev(void* d_x, int dtype, int64_t n, int d, void* stream);
