@@ -911,7 +911,7 @@ struct Scan4Shared {  // per query
     uint64_t ext;
     uint32_t tau;     // >= limit candidates are expected (sample) to have a sum <= tau
     int verify;       // the collection threshold rests on the sample: count before trusting it
-    int cnt;          // entries in the query's list
+    int scaled;       // M = 16: the query runs on the saturating scale (entries may be clamped at CAP); 0: on its tables' own scale
     int q;
 };
 
@@ -1085,6 +1085,11 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
     // word i of the per-query lists [(g * NW + w) * WCAP + idx]
     auto list_at = [&](int i) -> uint32_t* { return reinterpret_cast<uint32_t*>(tab + two_list_byte(i)); };  // (TWO)
     const int nvec = (nf * K) >> 2;  // float4 per half table (<= 256 = threads)
+    // query g's entries may be clamped at CAP: it runs on the saturating scale (Scan4Shared::scaled, set with the scale below)
+    auto clamped = [&](int g) -> bool {
+        if constexpr (M == 16) return sat > 0.f && sh[g].scaled != 0;
+        else return sat > 0.f;
+    };
     const long long k0 = S3_CLK();
     (void)k0;
     for (int kb = 0;; kb += S4_DS) {
@@ -1218,6 +1223,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                     // guarantees: thresholds and cuts at or above CAP send the slot to the forms that need no such scale.
                     if (w < G) {
                         const int g = w;
+                        bool taken = false;
                         if (g < ng) {  // wave-uniform
                             const int t0 = __builtin_amdgcn_readfirstlane(d->tab0[g]), t1 = __builtin_amdgcn_readfirstlane(d->tab1[g]);
                             const int64_t Ta = (int64_t)t0 * nf * K, Tb = (int64_t)t1 * nf * K;
@@ -1250,7 +1256,15 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                             const float d4 = __uint_as_float(mn);
                             const float qs = (sat * (float)CAP) / fmaxf(d4, 1e-30f);
                             const float q0 = d->qinv[g];
-                            if (lane == 0 && q0 > 0.0f && qs > q0 && qs < 3.0e38f && d4 < 1.0e38f) const_cast<Slot4*>(d)->qinv[g] = qs;
+                            taken = q0 > 0.0f && qs > q0 && qs < 3.0e38f && d4 < 1.0e38f;
+                            if (lane == 0 && taken) const_cast<Slot4*>(d)->qinv[g] = qs;
+                        }
+                        // A query whose sample asks for a COARSER scale than its tables' own (far candidates only: qs <= q0) stays on
+                        // q0, where no entry reaches CAP and every sum brackets its distance: the rules for clamped entries below
+                        // (tau and the cut below CAP) are not for it.  Held to them it lost its bound whenever the limit-th sum lay
+                        // above CAP -- sixteen entries reach 16 CAP -- listed every candidate and sent the slot to the fall-back.
+                        if constexpr (M == 16) {  // (only M = 16 is launched with a saturating scale; the previous slot's readers of sh[] are behind B5)
+                            if (lane == 0) sh[g].scaled = taken ? 1 : 0;
                         }
                     }
                     lds_barrier();
@@ -1316,7 +1330,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                     sh[g].ub = ub;
                     sh[g].q = q;
                     sh[g].ext = (g < ng) ? __hip_atomic_load(&qbound[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0x7ff0000000000000ull;
-                    sh[g].cnt = 0;
+                    if constexpr (M != 16) sh[g].scaled = 0;  // (never read there)
                     if (g < ng) {
                         item_slack[2 * (int64_t)item + 0] = __double2float_ru(ub * ((double)M + 0.1));
                         item_slack[2 * (int64_t)item + 1] = __double2float_ru(ub);
@@ -1419,7 +1433,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                                 else lo = p + 1;
                             }
                             tau = lo;
-                            have_bound = tau < (sat > 0.f ? CAP - (uint32_t)M - 2u : 65534u);  // (saturating scale: the bracket needs sums below CAP)
+                            have_bound = tau < (clamped(g) ? CAP - (uint32_t)M - 2u : 65534u);  // (saturating scale: the bracket needs sums below CAP)
                         }
                         if (lane == 0) {
                             uint32_t keep = 65534u;
@@ -1548,7 +1562,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                                 else lo = p + 1;
                             }
                             tau = lo;
-                            have_bound = tau < (sat > 0.f ? CAP - (uint32_t)M - 2u : 65534u);  // (saturating scale: the bracket needs sums below CAP)
+                            have_bound = tau < (clamped(g) ? CAP - (uint32_t)M - 2u : 65534u);  // (saturating scale: the bracket needs sums below CAP)
                         }
                         if (lane == 0) {
                             uint32_t keep = 65534u;
@@ -1777,13 +1791,13 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                                     }
                                 }
                                 cut = hi + (uint32_t)M + 1u;
-                                if (sat > 0.f && cut >= CAP) {  // saturating scale: the L best are not all below CAP -- no valid bracket from this scale
+                                if (clamped(g) && cut >= CAP) {  // saturating scale: the L best are not all below CAP -- no valid bracket from this scale
                                     bad = true;
                                     if (lane_v == 0) atomicAdd(&dbg[4], 1);
                                 }
                                 const uint64_t b = val_to_bound(hi, M, sh[g].ub);  // >= L candidates of this chunk do not exceed it
                                 if (lane_v == 0 && !bad && b < sh[g].ext) atomicMin(&qbound[sh[g].q], (unsigned long long)b);
-                            } else if (sat > 0.f) {
+                            } else if (clamped(g)) {
                                 // fewer than L collected: everything leaves; with the saturating scale every survivor must still be below CAP
                                 // (the merge turns a survivor's sum into an upper bound of its distance, which a saturated entry would break)
                                 bool sat = false;

@@ -17,19 +17,23 @@ rows ahead, so the cells below are chosen by the number of rounds (a wave's rows
 
 A wrong sample still gives exact results -- the verification sends the slot to the fall-back -- so every case also pins the number of
 slots that k_adc_scan4 hands to the fall-back list (CIS_SCAN4_DEBUG prints it per launch) to what the build before the ring reported for
-the same case, measured with that build's library on the same queries: 0 in every M = 8 case (random codes without duplicates).  In the
-two M = 16 cases that build sends every slot to the fall-back (1 of 1 and 3 of 3: uniformly random codes under the saturating scale),
-so those two pin the results and the unchanged count, but cannot tell a wrong sample from a right one.  Each case
+the same case, measured with that build's library on the same queries: 0 in every case (random codes without duplicates).  The two
+M = 16 cases used to send every slot to the fall-back (1 of 1 and 3 of 3) and so could not tell a wrong sample from a right one.  The
+reason was the kernel's: uniformly random codes are all far from a query, their scale sample asks for a COARSER scale than the tables'
+own, the query stays on its own scale -- and was still held to the saturating scale's rule that tau lie below CAP - M - 2 = 4077, while
+sixteen unclamped entries put the limit-th sum at 4100 .. 4900 for three of the four queries.  Without a bound such a query lists every
+candidate: the position lists overflow (counted once, through query 0) and the one query that had a bound finds its list empty (1
+overflowed, 1 failed the verification in the 20077 cell).  Only a query that TOOK the saturating scale has clamped entries; with the
+rule applied to those alone both cells settle, and tests/scan4_model.py predicts both sets of counters.  Each case
 aims four queries (a full slot) or one (a partly filled slot) at a cell, compares the sampled form (scan mode 5) with the float64 scan
 kernel (mode 1) bit for bit and the queries with the oracle (_check of test_scan4_long_chunks.py), and asserts that the batch ran the
 long-chunk form: with CIS_SEG_MAX=65536 a cell is one chunk, and scan3_geom takes that form from 6144 candidates per work item on.  The
 short cells sit beside the two 65 k cells for that reason: a query visits cells until it has seen 10000 candidates, so whatever the
 order, its items average more than 6144."""
-import re
-
 import numpy as np
 import pytest
 
+from scan4_model import parse_debug
 from test_scan4_long_chunks import _check, _queries, _world
 
 pytestmark = pytest.mark.gpu
@@ -42,8 +46,6 @@ WORLDS = {
 }
 # slots handed to the fall-back list by the build before the ring, per (world, cell length, queries)
 PARENT_FALLBACKS = {(wn, n, nq): 0 for wn, (_, cells) in WORLDS.items() for _, n in cells for nq in (4, 1)}
-PARENT_FALLBACKS[("m16", 20077, 4)] = 1  # of 1 slot
-PARENT_FALLBACKS[("m16", 8705, 4)] = 3   # of 3 slots
 
 _ring_worlds = {}
 
@@ -83,11 +85,10 @@ def _run(monkeypatch, capfd, wname, cell, nq):
     capfd.readouterr()
     _check(w, w["fine"], Q, modes=(5,))
     err = capfd.readouterr().err
-    lines = re.findall(r"k_adc_scan4: (\d+) slots, (\d+) to the fall-back list", err)
+    lines, total = parse_debug(err)
     st = stats[-1]  # the mode-5 search
-    fallbacks = sum(int(f) for _, f in lines)
-    print("%s len %d nq %d: %d launches, %d slots, %d to the fall-back list; %d candidates / %d items" % (
-        wname, n, nq, len(lines), sum(int(s) for s, _ in lines), fallbacks, st["candidates"], st["items"]))
+    fallbacks = total.fallbacks
+    print("%s len %d nq %d: %d launches, %s; %d candidates / %d items" % (wname, n, nq, len(lines), total, st["candidates"], st["items"]))
     assert st["scan_kernel"] == "k_adc_scan4" and lines, "the sampled form ran"
     assert st["candidates"] >= 6144 * st["items"], "the long-chunk form ran"
     assert fallbacks == PARENT_FALLBACKS[(wname, n, nq)]
