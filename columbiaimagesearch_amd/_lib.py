@@ -105,6 +105,16 @@ _PROTOS = {
     "cis_rerank_select_dev": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p,
                                       c_void_p, c_int, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p]),
+    "cis_featstore_create": (c_int, [POINTER(c_void_p), c_int, c_int, c_int64]),
+    "cis_featstore_destroy": (None, [c_void_p]),
+    "cis_featstore_size": (c_int64, [c_void_p]),
+    "cis_featstore_reserve": (c_int, [c_void_p, c_int64, c_void_p]),
+    "cis_featstore_put_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, POINTER(c_int64), POINTER(c_int64), c_void_p]),
+    "cis_featstore_remove_dev": (c_int, [c_void_p, c_void_p, c_int64, POINTER(c_int64), c_void_p]),
+    "cis_featstore_get_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "cis_featstore_rows_dev": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "cis_featstore_view": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
+                                   POINTER(c_int64), POINTER(c_int64)]),
     "cis_exact_knn_dev": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_int, c_int64, c_int, c_void_p, c_void_p,
                                   c_void_p]),
     "cis_exact_knn": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_int, c_int64, c_int, c_void_p, c_void_p]),

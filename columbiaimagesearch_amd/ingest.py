@@ -30,29 +30,72 @@ def l2_normalize_dev(feats):
 class BatchIngest(object):
     """net: SentiBankNet / DLibFaceNet (forward_dev), model: LOPQModel[PCA] (predict_batch_dev),
     searcher: LOPQSearcherHIP, ShardedSearcher / GridSearcher (device insert) or any searcher with add_codes_array
-    (LOPQSearcherLMDB: host key / value store)."""
+    (LOPQSearcherLMDB: host key / value store).
 
-    def __init__(self, net, model, searcher, feat_dtype=None):
+    features: a rerank.FeatureStore of the descriptors' width and dtype (or None).  With a store, every path of ingest_batch /
+    ingest_batches puts the normalised descriptors under the ids it inserts, on the caller's stream right behind the insert, so
+    an item that came in through the GPU path has a feature to re-rank with (LOPQSearcherHIP.search_rerank_dev(q, features)).
+    Tensor and integer ids are the store's ids as they are; other ids (the reference's sha1 strings) go in after the insert has
+    created their slots, through searcher.device_ids_of.  One asymmetry: the index's dedup skips an id already in the SAME cell
+    and stores the id a second time when its new code lands in another cell, as the reference does; the store keeps one row
+    per id, the last.  With features=None nothing changes."""
+
+    def __init__(self, net, model, searcher, feat_dtype=None, features=None):
         self.net, self.model, self.searcher = net, model, searcher
         self.feat_dtype = feat_dtype  # torch dtype the descriptors are cast to before normalisation (dlib: float64)
+        self.features = features
         self.nb_ingested = 0
+
+    def _descriptors_dev(self, feats):
+        """The net's output -> the normalised descriptors the codes are made of (and the store keeps)."""
+        if self.feat_dtype is not None and feats.dtype != self.feat_dtype:
+            feats = feats.to(self.feat_dtype)
+        return l2_normalize_dev(feats).contiguous()
+
+    def _check_store(self, desc, ids):
+        """Raises ValueError, before anything is inserted, when the store cannot take these descriptors under these ids."""
+        f = self.features
+        if desc.dtype != f.dtype or int(desc.shape[1]) != f.D:
+            raise ValueError("the feature store holds %s rows of width %d, the descriptors are %s of width %d"
+                             % (str(f.dtype).split(".")[-1], f.D, str(desc.dtype).split(".")[-1], int(desc.shape[1])))
+        if ids is not None and not hasattr(ids, "is_cuda"):
+            try:
+                ids_h = np.ascontiguousarray(ids, dtype=np.int64)
+            except (TypeError, ValueError):
+                ids_h = None
+            if (ids_h is None or ids_h.shape != (int(desc.shape[0]),)) and not hasattr(self.searcher, "device_ids_of"):
+                raise ValueError("non-integer ids need a searcher with device_ids_of to address the feature store")
+
+    def remove_ids_dev(self, ids):
+        """Remove the device ids (int64 tensor on the GPU) from the searcher and, when there is one, from the feature store, on
+        the current stream.  Returns the number of items the searcher removed."""
+        removed = self.searcher.remove_ids_dev(ids)
+        if self.features is not None:
+            self.features.remove_dev(ids)
+        return removed
 
     def encode_batch_dev(self, x):
         """x: preprocessed input batch on the GPU -> (coarse uint16-as-int16 [n,2], fine uint8 [n,M]) on the GPU."""
-        feats = self.net.forward_dev(x)
-        if self.feat_dtype is not None and feats.dtype != self.feat_dtype:
-            feats = feats.to(self.feat_dtype)
-        return self.model.predict_batch_dev(l2_normalize_dev(feats).contiguous())
+        return self.model.predict_batch_dev(self._descriptors_dev(self.net.forward_dev(x)))
 
     def ingest_batch(self, x, ids=None):
         """Encode one batch and insert it; ids default to consecutive integers.  Returns the number of new items.
         Codes and ids stay in HBM: the insert is the device-side merge of csrc/lopq_index.hip (through the all-to-all of
         distributed.ShardedSearcher.add_codes_routed_dev when the searcher is sharded)."""
-        import torch
-        coarse, fine = self.encode_batch_dev(x)
-        return self._insert_codes(coarse, fine, ids)
+        desc = self._descriptors_dev(self.net.forward_dev(x))
+        if self.features is not None:
+            self._check_store(desc, ids)
+        coarse, fine = self.model.predict_batch_dev(desc)
+        return self._insert_codes(coarse, fine, ids, desc if self.features is not None else None)
 
-    def _insert_codes(self, coarse, fine, ids=None):
+    def _put_features(self, dev_ids, desc):
+        import torch
+        if not hasattr(dev_ids, "is_cuda"):
+            dev_ids = torch.as_tensor(np.ascontiguousarray(dev_ids, dtype=np.int64)).to(desc.device)
+        self.features.put_dev(dev_ids.contiguous(), desc)
+
+    def _insert_codes(self, coarse, fine, ids=None, desc=None):
+        """desc: the batch's normalised descriptors when there is a feature store (they go in under the inserted ids)."""
         import torch
         n = int(coarse.shape[0])
         s = self.searcher
@@ -65,6 +108,8 @@ class BatchIngest(object):
                 ids = ids.cpu().numpy()
             before = s.get_nb_indexed()
             s.add_codes_array(coarse.cpu().numpy().view(np.uint16), fine.cpu().numpy(), ids)
+            if desc is not None:
+                self._put_features(s.device_ids_of(ids) if hasattr(s, "device_ids_of") else ids, desc)
             self.nb_ingested += n
             return int(s.get_nb_indexed() - before)
         if ids is None:
@@ -76,7 +121,11 @@ class BatchIngest(object):
                 ids_h = None
             if ids_h is None or ids_h.shape != (n,):
                 # non-integer ids (the reference's sha1 strings): the Python mirror maps them to slots, codes take the host entry point
-                added = s.add_codes_array(coarse.cpu().numpy().view(np.uint16), fine.cpu().numpy(), list(ids))
+                ids = list(ids)
+                added = s.add_codes_array(coarse.cpu().numpy().view(np.uint16), fine.cpu().numpy(), ids)
+                if desc is not None:  # (the insert has created the ids' slots; zip() semantics when ids is shorter)
+                    dev_ids = s.device_ids_of(ids[:n])
+                    self._put_features(dev_ids, desc[:len(dev_ids)].contiguous())
                 self.nb_ingested += n
                 return added
             ids = torch.as_tensor(ids_h).to(coarse.device)
@@ -86,6 +135,8 @@ class BatchIngest(object):
             added = s.add_codes_dev(coarse, fine, ids)
         if isinstance(added, tuple):  # LOPQSearcherHIP.add_codes_dev -> (added, skipped); the sharded forms return the count
             added = added[0]
+        if desc is not None:
+            self._put_features(ids, desc)
         self.nb_ingested += n
         return int(added)
 
@@ -114,10 +165,11 @@ class BatchIngest(object):
             feats, ev, bid, _x = queue.popleft()   # (_x: the input batch, kept alive until its forward has been waited for)
             cur.wait_event(ev)
             feats.record_stream(cur)
-            if self.feat_dtype is not None and feats.dtype != self.feat_dtype:
-                feats = feats.to(self.feat_dtype)
-            coarse, fine = self.model.predict_batch_dev(l2_normalize_dev(feats).contiguous())
-            out.append(self._insert_codes(coarse, fine, bid))
+            desc = self._descriptors_dev(feats)
+            if self.features is not None:
+                self._check_store(desc, bid)
+            coarse, fine = self.model.predict_batch_dev(desc)
+            out.append(self._insert_codes(coarse, fine, bid, desc if self.features is not None else None))
         for i, x in enumerate(batches):
             net, stream = self._lanes[i % lanes]
             stream.wait_stream(cur)  # the batch was produced on the caller's stream

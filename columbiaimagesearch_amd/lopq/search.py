@@ -507,6 +507,24 @@ class LOPQSearcherHIP(LOPQSearcherBase):
         out["visited"] = r["visited"]
         return out
 
+    def search_by_ids_dev(self, ids, feats, quota=10, limit=None, rerank_nb=None, max_returned=None, near_dup_th=None):
+        """Query by stored item (the reference's search_bySHA1, api.py:260-285, with the features it leaves as a TODO): ids int64
+        [m] device ids on the GPU (device_ids_of maps caller ids), feats a rerank.FeatureStore.  One gather of the stored rows
+        (feats.get_dev) in front of search_rerank_dev, all on the current stream.  With a PCA model the store holds the
+        input-space features, which is what search_rerank_dev takes.  Returns search_rerank_dev's dict plus ``found`` (bool [m]);
+        a query whose id is not stored comes back with ids -1, dists NaN, src -1 and n_kept 0."""
+        q, rows = feats.get_dev(ids)
+        out = self.search_rerank_dev(q, feats, quota=quota, limit=limit, rerank_nb=rerank_nb, max_returned=max_returned,
+                                     near_dup_th=near_dup_th)
+        found = rows >= 0
+        missing = ~found
+        out["ids"].masked_fill_(missing[:, None], -1)
+        out["dists"].masked_fill_(missing[:, None], float("nan"))
+        out["src"].masked_fill_(missing[:, None], -1)
+        out["n_kept"].masked_fill_(missing, 0)
+        out["found"] = found
+        return out
+
     def search_partial_dev(self, q, quota=10, limit=None):
         """This shard's ranked hits: (hits uint8 [nq, L, 32] viewable as cis_hit, visited [nq])."""
         import torch

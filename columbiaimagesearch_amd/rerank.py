@@ -192,3 +192,209 @@ class ResidentFeatures(object):
             order = np.argsort(d[keep], axis=0, kind="stable") if keep else []
             out.append(([ids[qi, keep[j]] for j in order], [float(d[keep[j]]) for j in order]))
         return out
+
+
+class FeatureStore(object):
+    """Features that live in HBM and change by kernels (include/cis_hip.h:cis_featstore_*; csrc/feat_store.hip): the reference's
+    HBase feature table (``put`` per item, hbase_indexer_minimal.py:779-831) for a live index.  `put_dev` stores or overwrites
+    rows by id, `remove_dev` takes them out again, `get_dev` gathers them, and `rerank_dev` / `rows_of_dev` / `search_exact`
+    have the signatures and the results of ResidentFeatures', so LOPQSearcherHIP.search_rerank_dev(q, store, ...) takes a store
+    where it takes a ResidentFeatures.
+
+    Ids are DEVICE ids, int64 >= 0: an integer id is its own device id; for other ids (the reference's sha1_bbox strings) the
+    caller maps with LOPQSearcherHIP.device_ids_of, after the insert that created their slots.  The store keeps ONE row per id,
+    the last one put.  (The index's dedup only skips an id already in the same cell: an id whose new code lands in another cell
+    is stored a second time there, as in the reference; its feature is the last one either way.)
+
+    Rows [0, len) are dense.  A removal fills the holes below the new length with the rows from the tail, so after a removal
+    the row order is not the insertion order, and `search_exact` breaks exact distance ties by row.  One store per device;
+    calls on a store must be ordered by the caller's streams.  Nothing is persisted."""
+
+    def __init__(self, D, dtype, reserve=0, device=None):
+        import torch
+        if dtype not in (torch.float32, torch.float64):
+            raise ValueError("dtype must be torch.float32 or torch.float64")
+        self.D, self.dtype = int(D), dtype
+        self._code = _lib.CIS_F32 if dtype == torch.float32 else _lib.CIS_F64
+        self._fs = None
+        h = _lib.ctypes.c_void_p()
+        # (the library comes first: without a GPU this is its loud failure, not torch's)
+        _lib.check(_lib.lib().cis_featstore_create(_lib.ctypes.byref(h), self.D, self._code, int(reserve)))
+        self._fs = h
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+
+    # -- life cycle --------------------------------------------------------------------------------------------------------------
+    def close(self):
+        if self._fs:
+            _lib.lib().cis_featstore_destroy(self._fs)
+            self._fs = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _handle(self):
+        if not self._fs:
+            raise ValueError("this feature store is closed")
+        return self._fs
+
+    def __len__(self):
+        return int(_lib.lib().cis_featstore_size(self._handle()))
+
+    def _stream(self):
+        import torch
+        return torch.cuda.current_stream(self.device)
+
+    def reserve(self, rows):
+        """Room for `rows` rows and their table entries, so that later puts up to that size allocate nothing."""
+        _lib.check(_lib.lib().cis_featstore_reserve(self._handle(), int(rows), self._stream().cuda_stream))
+
+    def _view(self):
+        """(feats, row_ids, keys, rows pointers, cap, n): borrowed, valid until the next put or reserve -- fetched per call."""
+        c = _lib.ctypes
+        f, ri, k, r = c.c_void_p(), c.c_void_p(), c.c_void_p(), c.c_void_p()
+        cap, n = c.c_int64(0), c.c_int64(0)
+        _lib.check(_lib.lib().cis_featstore_view(self._handle(), c.byref(f), c.byref(ri), c.byref(k), c.byref(r), c.byref(cap), c.byref(n)))
+        return f.value, ri.value, k.value, r.value, int(cap.value), int(n.value)
+
+    def table_capacity(self):
+        """Slots of the id -> row table (a power of two)."""
+        return self._view()[4]
+
+    def _check_ids(self, ids, what="ids"):
+        import torch
+        if not (torch.is_tensor(ids) and ids.is_cuda and ids.is_contiguous() and ids.dtype == torch.int64 and ids.dim() == 1):
+            raise ValueError("%s must be a contiguous int64 [n] tensor on the GPU" % what)
+
+    # -- put / remove / get ------------------------------------------------------------------------------------------------------
+    def put_dev(self, ids, feats):
+        """Store feats [n, D] under the device ids [n] (tensors in HBM), by kernels on the current stream: a stored id is
+        overwritten, a repeated id keeps its last row, ids < 0 are skipped.  Returns (new, skipped)."""
+        self._check_ids(ids)
+        if not (feats.is_cuda and feats.is_contiguous() and feats.dim() == 2 and feats.dtype == self.dtype
+                and tuple(feats.shape) == (int(ids.shape[0]), self.D)):
+            raise ValueError("feats must be a contiguous %s [%d, %d] tensor on the GPU" % (str(self.dtype).split(".")[-1], int(ids.shape[0]), self.D))
+        new, skipped = _lib.c_int64(0), _lib.c_int64(0)
+        _lib.check(_lib.lib().cis_featstore_put_dev(self._handle(), ids.data_ptr(), feats.data_ptr(), int(ids.shape[0]),
+                                                    _lib.ctypes.byref(new), _lib.ctypes.byref(skipped), self._stream().cuda_stream))
+        return int(new.value), int(skipped.value)
+
+    def remove_dev(self, ids):
+        """Remove the stored ids of the list (unknown, negative and repeated ones are ignored).  Returns the number removed."""
+        self._check_ids(ids)
+        removed = _lib.c_int64(0)
+        _lib.check(_lib.lib().cis_featstore_remove_dev(self._handle(), ids.data_ptr(), int(ids.shape[0]), _lib.ctypes.byref(removed),
+                                                       self._stream().cuda_stream))
+        return int(removed.value)
+
+    def get_dev(self, ids):
+        """(feats [m, D], rows int64 [m]) of the device ids [m]: an unknown or negative id gives row -1 and a row of zeros.
+        No synchronise."""
+        import torch
+        self._check_ids(ids)
+        m = int(ids.shape[0])
+        feats = torch.empty((m, self.D), dtype=self.dtype, device=ids.device)
+        rows = torch.empty(m, dtype=torch.int64, device=ids.device)
+        _lib.check(_lib.lib().cis_featstore_get_dev(self._handle(), ids.data_ptr(), m, feats.data_ptr(), rows.data_ptr(),
+                                                    self._stream().cuda_stream))
+        return feats, rows
+
+    def _upload_ids(self, ids):
+        import torch
+        return torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)).to(self.device)
+
+    def put(self, ids, feats):
+        """put_dev on host arrays (uploaded first)."""
+        import torch
+        a = np.ascontiguousarray(feats, dtype=np.float32 if self.dtype == torch.float32 else np.float64).reshape(-1, self.D)
+        return self.put_dev(self._upload_ids(ids), torch.as_tensor(a).to(self.device))
+
+    def remove(self, ids):
+        """remove_dev on a host array of device ids."""
+        return self.remove_dev(self._upload_ids(ids))
+
+    def row_ids(self):
+        """The device id of every row [0, len): an int64 tensor, copied from the store's column on the current stream (the
+        column itself moves when the rows grow, so no tensor is left pointing into it)."""
+        return self.rows_dev(feats=False)[1]
+
+    def rows_dev(self, first=0, count=None, feats=True):
+        """(feats [count, D] or None, ids int64 [count]) of the rows [first, first + count) as they lie in the store, copied on the
+        current stream (count=None: up to the last row)."""
+        import torch
+        first = int(first)
+        count = len(self) - first if count is None else int(count)
+        if first < 0 or count < 0:
+            raise ValueError("first and count must be >= 0")
+        f = torch.empty((count, self.D), dtype=self.dtype, device=self.device) if feats else None
+        ids = torch.empty(count, dtype=torch.int64, device=self.device)
+        _lib.check(_lib.lib().cis_featstore_rows_dev(self._handle(), first, count, None if f is None else f.data_ptr(), ids.data_ptr(),
+                                                     self._stream().cuda_stream))
+        return f, ids
+
+    # -- what ResidentFeatures offers, on the store's own arrays --------------------------------------------------------------------
+    def rows_of_dev(self, ids):
+        """ResidentFeatures.rows_of_dev: int64 tensor of ids' shape, -1 where the id is not stored.  No synchronise."""
+        import torch
+        if not (torch.is_tensor(ids) and ids.is_cuda and ids.is_contiguous() and ids.dtype == torch.int64):
+            raise ValueError("ids must be a contiguous int64 tensor on the GPU")
+        _, _, keys, rows, cap, n = self._view()
+        out = torch.empty_like(ids)
+        _lib.check(_lib.lib().cis_idmap_lookup_dev(keys, rows, cap, n, ids.data_ptr(), ids.numel(), out.data_ptr(),
+                                                   torch.cuda.current_stream(ids.device).cuda_stream))
+        return out
+
+    def rerank_dev(self, q, ids, adc, rerank_nb=None, max_returned=None, near_dup_th=None, out=None):
+        """ResidentFeatures.rerank_dev on the store's rows and table as they are now (cis_featstore_view, fetched anew on every
+        call): the same kernel, the same results.  A result whose id is not stored keeps its ADC distance."""
+        import torch
+        if not (q.is_cuda and q.is_contiguous() and q.dim() == 2 and q.dtype == self.dtype and q.shape[1] == self.D):
+            raise ValueError("q must be a contiguous [nq, D] tensor on the GPU with the features' dtype and width")
+        nq = int(q.shape[0])
+        for t, dt, what in ((ids, torch.int64, "ids"), (adc, torch.float64, "adc")):
+            if not (torch.is_tensor(t) and t.is_cuda and t.is_contiguous() and t.dim() == 2 and t.dtype == dt and t.shape[0] == nq):
+                raise ValueError("%s must be a contiguous %s [nq, L] tensor on the GPU" % (what, str(dt).split(".")[-1]))
+        if ids.shape != adc.shape:
+            raise ValueError("ids and adc must have the same shape")
+        L = int(ids.shape[1])
+        nb = L if rerank_nb is None else min(int(rerank_nb), L)
+        if nb < 0 or (max_returned or 0) < 0:
+            raise ValueError("rerank_nb and max_returned must be >= 0")
+        dev = q.device
+        shapes = (("ids", torch.int64, (nq, nb)), ("dists", torch.float64, (nq, nb)), ("src", torch.int32, (nq, nb)),
+                  ("n_kept", torch.int32, (nq,)))
+        if out is None:
+            out = {k: torch.empty(shp, dtype=dt, device=dev) for k, dt, shp in shapes}
+        for k, dt, shp in shapes:
+            t = out[k]
+            if not (t.is_cuda and t.is_contiguous() and t.dtype == dt and tuple(t.shape) == shp):
+                raise ValueError("out[%r] must be a contiguous %s tensor of shape %r on the GPU" % (k, str(dt).split(".")[-1], shp))
+        feats, _, keys, rows, cap, n = self._view()
+        _lib.check(_lib.lib().cis_rerank_select_dev(
+            feats, self._code, n, self.D, keys, rows, cap, q.data_ptr(), nq, ids.data_ptr(), adc.data_ptr(), L, nb,
+            int(max_returned or 0), 0 if near_dup_th is None else 1, 0.0 if near_dup_th is None else float(near_dup_th),
+            out["ids"].data_ptr(), out["dists"].data_ptr(), out["src"].data_ptr(), out["n_kept"].data_ptr(),
+            torch.cuda.current_stream(dev).cuda_stream))
+        return out
+
+    def search_exact(self, q, k):
+        """ResidentFeatures.search_exact over the rows [0, len): (ids, dists) [nq, k] numpy arrays ranked by (distance, row), ids
+        mapped through the store's id column (-1 / NaN padded).  After a removal the rows are not in insertion order: that is
+        the order exact distance ties are broken in."""
+        import torch
+        if not (q.is_cuda and q.is_contiguous() and q.dim() == 2 and q.dtype in (torch.float32, torch.float64) and q.shape[1] == self.D):
+            raise ValueError("q must be a contiguous float32/float64 [nq, D] tensor on the GPU with the features' width")
+        nq, k = int(q.shape[0]), int(k)
+        rows = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=q.device)
+        dists = torch.empty((nq, max(k, 0)), dtype=torch.float64, device=q.device)
+        feats, _, _, _, _, n = self._view()
+        _lib.check(_lib.lib().cis_exact_knn_dev(feats, self._code, n, self.D, q.data_ptr(),
+                                                _lib.CIS_F32 if q.dtype == torch.float32 else _lib.CIS_F64, nq, k, 0, 0,
+                                                rows.data_ptr(), dists.data_ptr(), torch.cuda.current_stream(q.device).cuda_stream))
+        table = self.row_ids().cpu().numpy()
+        rows, dists = rows.cpu().numpy(), dists.cpu().numpy()
+        if table.shape[0] == 0:
+            return np.full_like(rows, -1), dists
+        return np.where(rows >= 0, table[np.maximum(rows, 0)], -1), dists

@@ -322,6 +322,54 @@ int cis_rerank_select_dev(const void* d_feats, int f_dtype, int64_t n_feats, int
                           const double* d_adc, int L, int nb, int max_returned, int use_th, double near_dup_th,
                           int64_t* d_out_ids, double* d_out_dists, int32_t* d_out_src, int32_t* d_n_kept, void* stream);
 
+/* A feature store that lives in HBM and changes by kernels (csrc/feat_store.hip): the `put` and the fetch of the reference's
+ * HBase feature table (hbase_indexer_minimal.py:779-831) for the exact re-rank above, addressed by the index's device ids.  The
+ * store owns a feature matrix [rows][D] in f_dtype (4 = float32, 8 = float64), the row -> id column, and an id -> row table with
+ * the layout, hash, probing and -1 = empty of cis_idmap_build_dev, so cis_idmap_lookup_dev and cis_rerank_select_dev read it as it
+ * is.  Rows [0, n) are always dense.  Every call enqueues kernels on `stream`; put and remove return after the stream has drained
+ * (their counts are read back: one host round trip each, like cis_index_add_dev / cis_index_remove_dev); get does not wait.
+ * A store belongs to the device selected when it was created; calls on one store must be stream-ordered by the caller.
+ *
+ * cis_featstore_reserve: room for `rows` rows and a table that takes them (and as many tombstones) without a rebuild, so that a
+ * measured loop allocates nothing (cis_alloc_stats counts every block of a store).  The per-call scratch is sized by the largest
+ * batch seen so far.
+ *
+ * cis_featstore_put_dev: d_ids [n], d_feats [n][D].  Exactly this loop, whatever the thread timing:
+ *     for i in range(n):
+ *         if ids[i] < 0: skipped += 1; continue
+ *         if ids[i] not in row: row[ids[i]] = len(row); new += 1
+ *         feats[row[ids[i]]] = batch[i]; row_ids[row[ids[i]]] = ids[i]
+ * A stored id is overwritten in place (HBase put: last write wins), an id repeated inside the batch takes one row and keeps its
+ * last feature, new ids take rows n, n + 1, ... in order of first occurrence; equal calls give equal bytes.  Rows and table grow as
+ * needed: rows into a new block (the old one is freed after the stream has drained), the table by a rebuild from the id column at
+ * the next power of two >= 4 (n + batch), which also clears the tombstones.  n <= 2^30.
+ *
+ * cis_featstore_remove_dev: stored ids of the list leave; unknown, negative and repeated ids are ignored; n = 0 is a no-op.  With k
+ * removed and n' = n - k, the removed rows below n' (ascending) are filled by the kept rows at or above n' (ascending), one each:
+ * feature row, id and table entry move.  O(k D + k log k), nothing passes over all rows or the whole table; a removed id's table
+ * slot becomes a tombstone (key -2) until the next rebuild.  After a removal the row order is NOT the insertion order, and
+ * cis_exact_knn_dev over the store breaks exact distance ties by row.
+ *
+ * cis_featstore_get_dev: d_out_feats [m][D] = the rows of d_ids [m], d_out_rows [m] (or NULL) their rows; an unknown or negative id
+ * gives row -1 and a zero-filled feature row.
+ *
+ * cis_featstore_view: borrowed device pointers for cis_rerank_select_dev, cis_idmap_lookup_dev and cis_exact_knn_dev (any output may
+ * be NULL): the matrix, the id column [n], the table (keys, rows, cap) and n.  Any later put or reserve invalidates them. */
+typedef struct cis_featstore cis_featstore;
+int cis_featstore_create(cis_featstore** out, int D, int f_dtype, int64_t reserve_rows);
+void cis_featstore_destroy(cis_featstore* fs);
+int64_t cis_featstore_size(cis_featstore* fs);
+int cis_featstore_reserve(cis_featstore* fs, int64_t rows, void* stream);
+int cis_featstore_put_dev(cis_featstore* fs, const int64_t* d_ids, const void* d_feats, int64_t n, int64_t* n_new,
+                          int64_t* n_skipped, void* stream);
+int cis_featstore_remove_dev(cis_featstore* fs, const int64_t* d_ids, int64_t n, int64_t* n_removed, void* stream);
+int cis_featstore_get_dev(cis_featstore* fs, const int64_t* d_ids, int64_t m, void* d_out_feats, int64_t* d_out_rows, void* stream);
+/* Rows [first, first + count) as they lie in the store, copied on `stream`: d_out_feats [count][D] and d_out_ids [count] (either may
+ * be NULL).  A range that does not lie inside [0, n) is CIS_EINVAL. */
+int cis_featstore_rows_dev(cis_featstore* fs, int64_t first, int64_t count, void* d_out_feats, int64_t* d_out_ids, void* stream);
+int cis_featstore_view(cis_featstore* fs, const void** d_feats, const int64_t** d_row_ids, const int64_t** d_keys,
+                       const int64_t** d_rows, int64_t* cap, int64_t* n);
+
 /* Exact k nearest neighbours (csrc/lopq_eval.hip): the ground truth of lopq.eval (lopq/lopq/eval.py:7-38: scipy's cdist + argmin /
  * argsort per row).  data [m2][d] and q [m1][d], each float32 or float64 (mixed allowed: the reference promotes both to float64).
  * dist = sqrt(s), s the float64 chain s = s + (x[i] - y[i])^2 for i ascending, every operation rounded on its own -- scipy's value
