@@ -5,9 +5,11 @@ Python loops: covariance accumulators become matrix products.  k-means results d
 scikit-learn version, so training is judged by distortion/recall, not bit parity (SURVEY.md
 section 8c caveat ii, section 8f row 3).  Not on the encode/search hot path.
 
-Three switches move work to the GPU, all off by default: ACCUM_BACKEND ("hip": covariance accumulations and projections),
-KMEANS_BACKEND ("hip" / "device": Lloyd iterations) and SEED_BACKEND ("device": the k-means++ seeds of kmeans_dev are drawn on the
-resident data by cis_kmeanspp_dev, csrc/kmeans_seed.hip, and never visit the host).
+Four switches move work to the GPU, all off by default: ACCUM_BACKEND ("hip": covariance accumulations and projections),
+KMEANS_BACKEND ("hip" / "device": Lloyd iterations), SEED_BACKEND ("device": the k-means++ seeds of kmeans_dev are drawn on the
+resident data by cis_kmeanspp_dev, csrc/kmeans_seed.hip, and never visit the host) and ROTATION_BACKEND ("device": the whole
+local-rotation stage -- residuals, covariances, eigendecompositions (cis_sym_eig_dev, csrc/sym_eig.hip), projections -- on the
+data the k-means uploaded; only the eigenvalues and the rotations themselves, O(V d^2) numbers, visit the host).
 """
 import logging
 
@@ -36,6 +38,35 @@ def eigenvalue_allocation(num_buckets, eigenvalues):
         perm[b, fill[b]] = dim
         fill[b] += 1
     return perm.reshape(D)
+
+
+def eigenvalue_allocation_batch(num_buckets, eigenvalues):
+    """eigenvalue_allocation for every row of `eigenvalues` [G, d] at once: [G, d] int64, row g the permutation of row g.  One
+    loop over the d dimensions, vector operations over the G rows.  Equal eigenvalues are taken in the reverse of a stable
+    ascending sort (what the scalar function does whenever the values are distinct)."""
+    W = np.asarray(eigenvalues, dtype=np.float64)
+    if W.ndim != 2:
+        raise ValueError("expected [G, d] eigenvalues, got shape %r" % (W.shape,))
+    G, D = W.shape
+    per_bucket = D // num_buckets
+    if per_bucket * num_buckets != D:
+        raise ValueError("%d dimensions do not split into %d buckets" % (D, num_buckets))
+    smallest = np.where(W != 0, np.abs(W), np.inf).min(axis=1) if D else np.ones(G)
+    scaled = W / np.where(np.isfinite(smallest), smallest, 1.0)[:, None]
+    with np.errstate(divide="ignore"):
+        logs = np.log2(np.abs(scaled))
+    order = np.argsort(scaled, axis=1, kind="stable")[:, ::-1]
+    rows = np.arange(G)
+    load = np.zeros((G, num_buckets))
+    fill = np.zeros((G, num_buckets), dtype=np.int64)
+    perm = np.zeros((G, num_buckets, per_bucket), dtype=np.int64)
+    for t in range(D):
+        dim = order[:, t]
+        b = np.where(fill < per_bucket, load, np.inf).argmin(axis=1)  # the first of the least loaded open buckets
+        load[rows, b] += logs[rows, dim]
+        perm[rows, b, fill[rows, b]] = dim
+        fill[rows, b] += 1
+    return perm.reshape(G, D)
 
 
 def assign_clusters(data, C, chunk=8192):
@@ -229,19 +260,135 @@ def kmeans_dev(data, k, iters, n_init=1, random_state=None):
     return best.astype(np.float64), best_inertia
 
 
-def assign_clusters_dev(data, C):
-    """assign_clusters on the GPU: one assignment pass of cis_kmeans_dev (iters = 0) in float32, int64 assignments on the host.
-    The kernel minimises |c|^2 - 2 x.c, so a point between two almost equally near centroids may go to either (DESIGN.md)."""
+def _assign_dev(x, C):
+    """One assignment pass of cis_kmeans_dev (iters = 0) on the resident float32 `x`: int32 assignments, a tensor on x's device."""
     import torch
     from .. import _lib
-    x = _resident(data)
     Cd = torch.from_numpy(np.ascontiguousarray(C, dtype=np.float32)).to(x.device)
     if Cd.dim() != 2 or Cd.shape[1] != x.shape[1]:
         raise ValueError("centroids %r do not match data %r" % (tuple(Cd.shape), tuple(x.shape)))
     assign = torch.empty(int(x.shape[0]), dtype=torch.int32, device=x.device)
     _lib.check(_lib.lib().cis_kmeans_dev(x.data_ptr(), int(x.shape[0]), int(x.shape[1]), int(Cd.shape[0]), 0, Cd.data_ptr(),
                                          assign.data_ptr(), None, torch.cuda.current_stream(x.device).cuda_stream))
-    return assign.cpu().numpy().astype(np.int64)
+    return assign
+
+
+def assign_clusters_dev(data, C):
+    """assign_clusters on the GPU: one assignment pass of cis_kmeans_dev (iters = 0) in float32, int64 assignments on the host.
+    The kernel minimises |c|^2 - 2 x.c, so a point between two almost equally near centroids may go to either (DESIGN.md)."""
+    return _assign_dev(_resident(data), C).cpu().numpy().astype(np.int64)
+
+
+def _stream(t):
+    import torch
+    return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def sym_eig_dev(A):
+    """Eigendecompositions of a float64 [batch, d, d] tensor of symmetric matrices on the GPU (cis_sym_eig_dev, d <= 128):
+    (W [batch, d] ascending, V [batch, d, d] with column j the eigenvector of W[:, j], info [batch] int32: the Jacobi sweeps used, or
+    -1 for a matrix that was not finite or did not converge).  Tensors on A's device; only enqueued on the current stream."""
+    import torch
+    from .. import _lib
+    if not (_is_tensor(A) and A.is_cuda and A.dim() == 3 and A.dtype == torch.float64 and A.shape[1] == A.shape[2]):
+        raise ValueError("expected a float64 [batch, d, d] tensor on the GPU")
+    A = A.contiguous()
+    batch, d = int(A.shape[0]), int(A.shape[1])
+    W = torch.empty((batch, d), dtype=torch.float64, device=A.device)
+    V = torch.empty((batch, d, d), dtype=torch.float64, device=A.device)
+    info = torch.empty(batch, dtype=torch.int32, device=A.device)
+    _lib.check(_lib.lib().cis_sym_eig_dev(A.data_ptr(), batch, d, W.data_ptr(), V.data_ptr(), info.data_ptr(), _stream(A)))
+    return W, V, info
+
+
+def _groups_dev(assign, V):
+    """Plumbing of the grouped kernels, on the device: (stable order of the rows by group [n] int64, group offsets [V+1] int64,
+    largest group's size).  Only the last comes to the host."""
+    import torch
+    order = torch.argsort(assign, stable=True)
+    counts = torch.bincount(assign, minlength=V)
+    off = torch.zeros(V + 1, dtype=torch.int64, device=assign.device)
+    off[1:] = torch.cumsum(counts, 0)
+    return order, off, (int(counts.max()) if assign.numel() else 0)
+
+
+def residuals_dev(x, C, assign, rows):
+    """float64 [len(rows), d] tensor: x[rows] - C[assign[rows]] (cis_train_residuals_dev).  x: resident float32 [n, d], C: float64
+    [V, d] tensor, assign: int32 [n] tensor, rows: int64 tensor of row numbers."""
+    import torch
+    from .. import _lib
+    out = torch.empty((int(rows.shape[0]), int(x.shape[1])), dtype=torch.float64, device=x.device)
+    _lib.check(_lib.lib().cis_train_residuals_dev(x.data_ptr(), int(x.shape[0]), int(x.shape[1]), C.data_ptr(), int(C.shape[0]),
+                                                  assign.data_ptr(), rows.data_ptr(), int(rows.shape[0]), out.data_ptr(), _stream(x)))
+    return out
+
+
+def gram_dev(res, off, groups):
+    """gram_hip on rows that are on the device and sorted by group (cis_train_gram_dev): (G [groups,d,d], S [groups,d]) tensors."""
+    import torch
+    from .. import _lib
+    n, d = int(res.shape[0]), int(res.shape[1])
+    G = torch.empty((groups, d, d), dtype=torch.float64, device=res.device)
+    S = torch.empty((groups, d), dtype=torch.float64, device=res.device)
+    _lib.check(_lib.lib().cis_train_gram_dev(res.data_ptr(), n, d, off.data_ptr(), groups, G.data_ptr(), S.data_ptr(), _stream(res)))
+    return G, S
+
+
+def local_rotations_dev(x, C, num_buckets, assign=None):
+    """local_rotations on the resident float32 `x` (ROTATION_BACKEND = "device"): residuals in group order, their Gram sums, the
+    covariances, one batched eigendecomposition and the rotation rows, all on the device; the eigenvalues [V, d] come to the host
+    for eigenvalue_allocation_batch and the permutations go back.  Returns (R [V,d,d], mu [V,d], assign, W [V,d]): R, mu and
+    the eigenvalues W as float64 numpy arrays, assign as the int32 tensor on the device it was computed from (or the one given).
+    A cluster with fewer than d points gets the identity covariance, hence W = 1 and a permutation matrix R, as on the host."""
+    import torch
+    from .. import _lib
+    L = _lib.lib()
+    V, d = C.shape
+    if d > 128:
+        raise ValueError("ROTATION_BACKEND = 'device' holds a d x d covariance in LDS: d = D/2 must be <= 128, got %d" % d)
+    if assign is None:
+        assign = _assign_dev(x, C)
+    st = _stream(x)
+    Cd = torch.from_numpy(np.ascontiguousarray(C, dtype=np.float64)).to(x.device)
+    order, off, _ = _groups_dev(assign, V)
+    res = residuals_dev(x, Cd, assign, order)
+    G, S = gram_dev(res, off, V)
+    del res
+    cov, mu = torch.empty_like(G), torch.empty_like(S)
+    _lib.check(L.cis_train_cov_dev(G.data_ptr(), S.data_ptr(), off.data_ptr(), V, d, cov.data_ptr(), mu.data_ptr(), st))
+    W, vecs, info = sym_eig_dev(cov)
+    Wh, failed = W.cpu().numpy(), np.nonzero(info.cpu().numpy() < 0)[0]
+    if failed.size:
+        raise FloatingPointError("no eigendecomposition for the residual covariance of cluster(s) %s (not finite, or not converged)"
+                                 % failed[:8].tolist())
+    small = np.nonzero(np.diff(off.cpu().numpy()) < d)[0]
+    for c in small[:16]:
+        logger.warning("Fewer points than dimensions (%d) in rotation computation for cluster %d", d, c)
+    perm = torch.from_numpy(eigenvalue_allocation_batch(num_buckets, Wh).astype(np.int32)).to(x.device)
+    R = torch.empty_like(cov)
+    _lib.check(L.cis_train_rotation_pack_dev(vecs.data_ptr(), perm.data_ptr(), V, d, R.data_ptr(), st))
+    return R.cpu().numpy(), mu.cpu().numpy(), assign, Wh
+
+
+def project_to_local_dev(x, C, assign, R, mu, rows=None):
+    """project_to_local on the device: R[a] . (x[r] - C[a] - mu[a]) for r in `rows` (default: every row), a float64 [len(rows), d]
+    tensor in the order of `rows`.  x: resident float32, assign: its int32 assignments on the device, C / R / mu: numpy arrays;
+    rows: int64 row numbers (numpy or tensor).  The rows are grouped by cluster for the kernel and scattered back by it."""
+    import torch
+    from .. import _lib
+    V, d = mu.shape
+    if rows is None:
+        rows = torch.arange(int(x.shape[0]), dtype=torch.int64, device=x.device)
+    elif not _is_tensor(rows):
+        rows = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int64)).to(x.device)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(x.device)
+    Cd, Rd, md = up(C), up(R), up(mu)
+    order, off, max_rows = _groups_dev(assign[rows], V)
+    res = residuals_dev(x, Cd, assign, rows[order].contiguous())
+    Y = torch.empty_like(res)
+    _lib.check(_lib.lib().cis_train_project_dev(res.data_ptr(), int(res.shape[0]), d, off.data_ptr(), V, max_rows, Rd.data_ptr(),
+                                                md.data_ptr(), order.data_ptr(), Y.data_ptr(), _stream(x)))
+    return Y
 
 
 # "hip": Lloyd iterations on the GPU where the codebook fits the LDS kernel (k * d <= 7680), scikit-learn beyond.
@@ -252,6 +399,9 @@ KMEANS_BACKEND = "sklearn"
 # different use of the RandomState, so different seeds for one random_state.
 SEED_BACKEND = "host"
 SEED_SAMPLE = 20000
+# "host": local_rotations / project_to_local (numpy, or the ACCUM_BACKEND kernels on host arrays).  "device": local_rotations_dev /
+# project_to_local_dev on the upload the coarse k-means made; needs KMEANS_BACKEND = "device" and d = D/2 <= 128 (ValueError otherwise).
+ROTATION_BACKEND = "host"
 
 
 def _kmeans(data, k, iters, n_init, random_state, dev=None):
@@ -303,17 +453,31 @@ def train(data, V=8, M=4, subquantizer_clusters=256, parameters=None, kmeans_coa
     if Rs is None or mus is None:
         Rs = mus = None
     halves = np.split(data, 2, axis=1)
+    if ROTATION_BACKEND not in ("host", "device"):
+        raise ValueError("ROTATION_BACKEND must be 'host' or 'device', got %r" % (ROTATION_BACKEND,))
+    on_dev = ROTATION_BACKEND == "device"
+    if on_dev and KMEANS_BACKEND != "device":
+        raise ValueError("ROTATION_BACKEND = 'device' works on the data KMEANS_BACKEND = 'device' uploads; KMEANS_BACKEND is %r"
+                         % (KMEANS_BACKEND,))
+    if on_dev and halves[0].shape[1] > 128:
+        raise ValueError("ROTATION_BACKEND = 'device' holds a d x d covariance in LDS: d = D/2 must be <= 128, got %d"
+                         % halves[0].shape[1])
     devs = [None, None]
-    if KMEANS_BACKEND == "device" and (Cs is None or Rs is None):  # one upload per half: the coarse k-means and the assignment share it
+    # one upload per half: the coarse k-means, the assignment and the device rotation stage share it
+    if KMEANS_BACKEND == "device" and (Cs is None or Rs is None or (on_dev and subs is None)):
         devs = [_resident(h) for h in halves]
     if Cs is None:
         Cs = tuple(_kmeans(h, V, kmeans_coarse_iters, n_init, random_state, dev) for h, dev in zip(halves, devs))
     fitted = None
     if Rs is None:
-        fitted = [local_rotations(h, C, M // 2, dev) for h, C, dev in zip(halves, Cs, devs)]
+        if on_dev:
+            fitted = [local_rotations_dev(dev, C, M // 2) for C, dev in zip(Cs, devs)]
+        else:
+            fitted = [local_rotations(h, C, M // 2, dev) for h, C, dev in zip(halves, Cs, devs)]
         Rs = tuple(f[0] for f in fitted)
         mus = tuple(f[1] for f in fitted)
-    del devs
+    if not on_dev:
+        del devs
     if subs is not None:
         return tuple(Cs), tuple(Rs), tuple(mus), subs
     N = data.shape[0]
@@ -321,6 +485,16 @@ def train(data, V=8, M=4, subquantizer_clusters=256, parameters=None, kmeans_coa
     sample = np.random.RandomState(random_state).choice(N, n_sub, False)
     subs = []
     for s, (h, C) in enumerate(zip(halves, Cs)):
+        if on_dev:  # the projected residuals stay on the GPU; each subquantizer gets its columns as one contiguous float32 block
+            import torch
+            assign = fitted[s][2] if fitted is not None else _assign_dev(devs[s], C)
+            projected = project_to_local_dev(devs[s], C, assign, Rs[s], mus[s], sample)
+            if projected.shape[1] % (M // 2):
+                raise ValueError("%d dimensions do not split into %d subquantizers" % (projected.shape[1], M // 2))
+            subs.append([_kmeans(None, subquantizer_clusters, kmeans_local_iters, n_init, random_state, p.to(torch.float32).contiguous())
+                         for p in torch.chunk(projected, M // 2, dim=1)])
+            del projected
+            continue
         if fitted is not None:
             assign, residuals = fitted[s][2][sample], fitted[s][3][sample]
         else:

@@ -444,6 +444,45 @@ int cis_train_gram(const double* X, int64_t n, int d, const int64_t* group_off, 
 int cis_train_project(const double* X, int64_t n, int d, const int64_t* group_off, int groups, const double* R,
                       const double* mu, double* Y);
 
+/* The same stage on data that is already on the device: every pointer below is a device pointer, and every call only enqueues
+ * kernels on `stream` and returns without waiting.  Sizes are refused with CIS_EINVAL before the device is touched.
+ * cis_train_residuals_dev:     d_out[r] = (double)d_X[d_order[r]] - d_C[d_assign[d_order[r]]] for r < rows.  d_X [n][d] float32,
+ *                              d_C [groups][d] float64, d_assign [n] int32, d_order [rows] int64, d_out [rows][d] float64.  float32
+ *                              minus float64 is exact in double: these are the host path's residuals bit for bit, in the order
+ *                              of d_order.  A d_order or d_assign entry outside its array gives a row of NaN.
+ * cis_train_gram_dev:          cis_train_gram on d_X [n][d] float64 with the group offsets on the device (d_S may be NULL).
+ * cis_train_project_dev:       cis_train_project likewise.  max_group_rows is the largest group's row count (it sizes the grid:
+ *                              rows of a group beyond it are not projected).  With d_order [n] int64 (or NULL), row r's result
+ *                              goes to row d_order[r] of d_Y [n][d]: a grouped input is written back in its original order.
+ *                              The two host entry points above run the same kernels and return the same bits.
+ * cis_train_cov_dev:           with n_g = d_group_off[g+1] - d_group_off[g]: d_mu[g] = d_S[g] / n_g (zeros for an empty group)
+ *                              and d_cov[g] = (G + G^T) / (2 (n_g - 1)) - mu mu^T from d_G [groups][d][d], or the identity matrix
+ *                              where n_g < d (the reference's fallback for a cluster too small for a rotation).
+ * cis_train_rotation_pack_dev: d_R[g][i][:] = d_V[g][:, d_perm[g][i]], d_perm [groups][d] int32 (the bucket allocation of the
+ *                              eigenvalues), d_V as cis_sym_eig_dev writes it. */
+int cis_train_residuals_dev(const float* d_X, int64_t n, int d, const double* d_C, int groups, const int32_t* d_assign,
+                            const int64_t* d_order, int64_t rows, double* d_out, void* stream);
+int cis_train_gram_dev(const double* d_X, int64_t n, int d, const int64_t* d_group_off, int groups, double* d_G, double* d_S,
+                       void* stream);
+int cis_train_project_dev(const double* d_X, int64_t n, int d, const int64_t* d_group_off, int groups, int64_t max_group_rows,
+                          const double* d_R, const double* d_mu, const int64_t* d_order, double* d_Y, void* stream);
+int cis_train_cov_dev(const double* d_G, const double* d_S, const int64_t* d_group_off, int groups, int d, double* d_cov,
+                      double* d_mu, void* stream);
+int cis_train_rotation_pack_dev(const double* d_V, const int32_t* d_perm, int groups, int d, double* d_R, void* stream);
+
+/* Batched symmetric eigendecomposition in float64 (csrc/sym_eig.hip): cyclic Jacobi in a round-robin ordering, one workgroup per
+ * matrix, the matrix in LDS.  Device pointers: d_A [batch][d][d] symmetric (never written), d_W [batch][d] the eigenvalues in
+ * ascending order, d_V [batch][d][d] row-major with column j the unit eigenvector of W[j] (numpy.linalg.eigh's layout), d_info
+ * [batch] int32 or NULL: the sweeps used, or -1 when the cap of 40 sweeps was reached or the input was not finite; W and V of such a
+ * matrix are written and unspecified, and no other matrix of the batch is affected.  Each eigenvector's component of largest
+ * magnitude is positive (the lowest index wins a tie), and a matrix's result does not depend on the batch around it.
+ * A matrix is done after a full sweep that rotated nothing; a pair (p, q) is left alone when a_pq == 0 or
+ * |a_pq| <= 2^-53 sqrt(|a_pp a_qq|).  Measured bounds (tests/test_sym_eig.py, u = 2^-53): |A V - V diag(W)| and |W - eigvalsh(A)|
+ * within 16 d u |A|_2, |V^T V - I| within 16 d u.
+ * Limits (CIS_EINVAL, before the device is touched): 1 <= d <= 128, batch >= 0 (0: nothing is launched); d_A, d_W and d_V not NULL.
+ * The call only enqueues on `stream` and needs no workspace. */
+int cis_sym_eig_dev(const double* d_A, int64_t batch, int d, double* d_W, double* d_V, int32_t* d_info, void* stream);
+
 /* Counters of the last search on this handle (for bench.py's roofline):
  *   stats[0] candidates scanned (sum over queries of retrieved items on this shard)
  *   stats[1] (query, cell) work items   stats[2] ADC tables built   stats[3] scan kernel launches */
