@@ -98,6 +98,11 @@ _PROTOS = {
                                      c_void_p, c_void_p, c_void_p, c_void_p]),
     "cis_pyramid_down2_dev": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "cis_extract_chips_dev": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "cis_shapepred_create": (c_int, [POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p]),
+    "cis_shapepred_destroy": (None, [c_void_p]),
+    "cis_shapepred_run_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "cis_dlib_decode_reals": (c_int, [c_void_p, ctypes.c_size_t, POINTER(ctypes.c_size_t), c_void_p, ctypes.c_size_t]),
     "cis_exchange_offsets_dev": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cis_rerank_dev": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "cis_idmap_build_dev": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),

@@ -117,7 +117,8 @@ class GenericExtractor(object):
     def _process_batch_dets(self, img_buffers, _raise):
         """Detector branch (:236-247) for a list of images.  With a featurizer that separates alignment from the network
         (`_chip` + `featurize_chips`: the dlib face featurizer) the aligned chips of ALL images' detections are gathered and
-        go through the network in GPU batches of up to `chip_batch` chips; otherwise one `featurize(img, det)` per detection
+        go through the network in GPU batches of up to `chip_batch` chips (`_chips`, where the featurizer has it, aligns all detections
+        of an image at once: one landmark-predictor launch with ``landmark_backend = "hip"``); otherwise one `featurize(img, det)` per detection
         like the reference.  An image without detections keeps ``processed = "0"`` like init_out_dict (:201-210)."""
         import numpy as np
         out = [None] * len(img_buffers)
@@ -131,7 +132,10 @@ class GenericExtractor(object):
                 if dets and batched:
                     if len(img.shape) == 2:
                         img = np.stack([img] * 3, axis=-1)  # dlib_featurizer.py:97-99 gray2rgb
-                    mine = [np.asarray(self.featurizer._chip(img, d)) for d in dets]  # any failure fails the image, not the batch
+                    if hasattr(self.featurizer, "_chips"):  # all detections of the image in one predictor launch and one chip pass
+                        mine = [np.asarray(c) for c in self.featurizer._chips(img, dets)]
+                    else:
+                        mine = [np.asarray(self.featurizer._chip(img, d)) for d in dets]  # any failure fails the image, not the batch
                     chips.extend(mine)
                     owner.extend((i, d) for d in dets)
                 elif dets:

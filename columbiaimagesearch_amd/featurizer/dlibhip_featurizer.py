@@ -2,10 +2,12 @@
 
 Mirror of DLibFeaturizer (cufacesearch/cufacesearch/featurizer/dlib_featurizer.py:50-105): constructor
 ``(global_conf_in, prefix)`` reading ``<prefix>pred_path`` (68-landmark shape predictor) and ``<prefix>rec_path``
-(recognition network weights), ``featurize(img, bbox)`` -> 128 float64 values.  The landmark predictor is dlib host code (out
-of scope, like image decoding: supply it through ``landmark_fn`` or pass ``landmarks=``); the chip alignment
-(get_face_chip_details + extract_image_chip, featurizer/face_chip.py + csrc/face_chip.hip) and the 29-convolution ResNet run in
-libcis_hip.so.  ``featurize_chips`` takes already aligned 150x150 RGB chips, ``featurize_landmarks`` an image and its shapes.
+(recognition network weights), ``featurize(img, bbox)`` -> 128 float64 values.  The landmark predictor (:103) is chosen by the config
+key ``<prefix>landmark_backend``: ``"dlib"`` (the default) is dlib's host code, as in the reference, unless the landmarks come through
+``landmark_fn`` or ``landmarks=``; ``"hip"`` reads ``pred_path`` (dlib's ``.dat`` or an ``.npz``: featurizer/shape_predictor.py, parity
+with dlib UNPINNED) on first use and runs the regression trees in libcis_hip.so (csrc/shape_predictor.hip), all detections of an image
+in one launch.  The chip alignment (get_face_chip_details + extract_image_chip, featurizer/face_chip.py + csrc/face_chip.hip) and the
+29-convolution ResNet run in libcis_hip.so.  ``featurize_chips`` takes already aligned 150x150 RGB chips, ``featurize_landmarks`` an image and its shapes.
 
 Weights: ``rec_path`` is dlib's ``.dat`` (featurizer/dlib_dat.py, unpinned), an ``.npz`` with the 117 arrays of ``tensor_names()``, or the XML that dlib's own
 ``net_to_xml`` writes from ``dlib_face_recognition_resnet_model_v1.dat`` (featurizer/dlib_weights.py; the ``.dat`` itself
@@ -90,6 +92,9 @@ class DLibHIPFeaturizer(GenericFeaturizer):
         super(DLibHIPFeaturizer, self).__init__(global_conf_in, prefix)
         self.set_pp(pp="DLibHIPFeaturizer")
         self.pred_path = self.get_param("pred_path")
+        self.landmark_backend = self.get_param("landmark_backend", "dlib")
+        if self.landmark_backend not in ("dlib", "hip"):
+            raise ValueError("[{}: error] '{}landmark_backend' is {!r}: 'dlib' or 'hip' expected".format(self.pp, prefix, self.landmark_backend))
         self.rec_path = str(self.get_required_param("rec_path"))
         if self.rec_path.endswith(".npz"):
             z = np.load(self.rec_path)
@@ -108,6 +113,7 @@ class DLibHIPFeaturizer(GenericFeaturizer):
                                       "117 network tensors -- see INTEGRATION.md section 4")
         self.net = DLibFaceNet(weights)
         self._sp = None
+        self._sp_hip = None      # landmark_backend "hip": loaded from pred_path on first use
         self.chip_fn = None      # (img, bbox) -> aligned 150x150x3 chip
         self.landmark_fn = None  # (img, bbox) -> [68, 2] landmarks (x, y): the chip is then cut on the GPU (featurizer/face_chip.py)
 
@@ -120,7 +126,7 @@ class DLibHIPFeaturizer(GenericFeaturizer):
         detection, generic_extractor.py:238)."""
         if len(img.shape) == 2:
             img = np.stack([img] * 3, axis=-1)  # reference :97-99 gray2rgb
-        return self.featurize_chips(np.stack([self._chip(img, d) for d in dets]))
+        return self.featurize_chips(np.stack(list(self._chips(img, dets))))
 
     def featurize_landmarks(self, img, shapes):
         """img [H, W, 3] uint8 RGB + n landmark sets [68, 2] (what dlib.shape_predictor returns, :103) -> [n, 128] float64:
@@ -143,9 +149,29 @@ class DLibHIPFeaturizer(GenericFeaturizer):
             return self.featurize_landmarks(img, [landmarks])[0]
         return self.featurize_chips(np.asarray(self._chip(img, bbox))[None])[0]
 
+    def landmarks_hip(self, img, dets):
+        """landmark_backend "hip": the [n, 68, 2] int64 landmarks of all detections of one image in ONE launch of the predictor"""
+        if self._sp_hip is None:
+            from .shape_predictor import ShapePredictorHIP, load_shape_predictor
+            self._sp_hip = ShapePredictorHIP(load_shape_predictor(self.pred_path))
+        rects = [[int(d["left"]), int(d["top"]), int(d["right"]), int(d["bottom"])] for d in dets]
+        return self._sp_hip.predict(img, rects)
+
+    def _chips(self, img, dets):
+        """The aligned chips (n of [150, 150, 3]) of all detections of one image.  landmark_backend "hip": one predictor launch, the
+        landmarks (n x 68 x 2 integers) back on the host once for get_face_chip_details, one face_chips call; else one _chip each."""
+        if len(img.shape) == 2:
+            img = np.stack([img] * 3, axis=-1)
+        if self.chip_fn is not None or self.landmark_backend != "hip" or len(dets) == 0:
+            return [self._chip(img, d) for d in dets]
+        from .face_chip import face_chips
+        return face_chips(img, list(self.landmarks_hip(img, dets).astype(np.float64))).cpu().numpy()
+
     def _chip(self, img, bbox):
         if self.chip_fn is not None:
             return np.asarray(self.chip_fn(img, bbox))
+        if self.landmark_backend == "hip":
+            return self._chips(img, [bbox])[0]
         try:
             import dlib
         except ImportError:

@@ -86,3 +86,28 @@ def dlib_weights(seed=0):
 def dlib_chips(n, seed=1):
     """n aligned face chips, uint8 RGB [n,150,150,3] (what get_face_chip would hand to the network)."""
     return np.random.RandomState(seed).randint(0, 256, size=(n, DLIB_INPUT_HW, DLIB_INPUT_HW, 3)).astype(np.uint8)
+
+
+def shape_predictor_model(seed=0, P=68, K=15, T=500, depth=4, F=500):
+    """A seeded landmark-predictor model (featurizer/shape_predictor.py) of the given dimensions; the defaults are those of dlib's
+    68-point model.  A plausible mean shape in [0, 1]^2 (P = 68: dlib's mean face of face_chip.py plus a jaw arc), feature-pixel offsets
+    of about 0.1 of the box, thresholds on half-integers in [-64, 64] (grey-level differences are integers: no ties), leaves of about
+    0.01 / T, so that a shape stays near its box through all levels."""
+    from .face_chip import MEAN_FACE_X, MEAN_FACE_Y
+    from .shape_predictor import ShapePredictorModel
+    rs = np.random.RandomState(seed)
+    S = (1 << depth) - 1
+    pts = np.empty((P, 2))
+    if P == 68:
+        pts[:17, 0] = np.linspace(0.0, 1.0, 17)
+        pts[:17, 1] = 0.3 + 0.7 * np.sin(np.linspace(0, np.pi, 17))
+        pts[17:, 0], pts[17:, 1] = MEAN_FACE_X, MEAN_FACE_Y
+    else:
+        pts[:] = 0.15 + 0.7 * rs.rand(P, 2)
+    return ShapePredictorModel(
+        initial_shape=pts.reshape(-1).astype(np.float32),
+        split_idx=rs.randint(0, F, size=(K, T, S, 2)).astype(np.int32),
+        split_thresh=(rs.randint(-64, 64, size=(K, T, S)) + 0.5).astype(np.float32),
+        leaves=(rs.randn(K, T, S + 1, 2 * P) * (0.01 / T)).astype(np.float32),
+        anchor_idx=rs.randint(0, P, size=(K, F)).astype(np.int32),
+        deltas=(0.1 * rs.randn(K, F, 2)).astype(np.float32))

@@ -556,6 +556,29 @@ int cis_cnn_create_view(cis_cnn** out, cis_cnn* base);
 int cis_pyramid_down2_dev(const uint8_t* d_img, int nr, int nc, uint8_t* d_out, int* d_tmp, void* stream);
 int cis_extract_chips_dev(const uint8_t* d_img, int nr, int nc, const double* d_maps, int n, int size, float* d_chips, void* stream);
 
+/* ---- face landmarks: dlib's shape_predictor, the call `self.pred(img, rect)` of DLibFeaturizer.featurize ---------------------------
+ * (cufacesearch/cufacesearch/featurizer/dlib_featurizer.py:103).  An ensemble of regression trees (Kazemi and Sullivan 2014) restated
+ * from dlib's published image_processing/shape_predictor.h as remembered; parity with dlib itself is UNPINNED (no dlib, no model file
+ * here): the yardstick is the numpy model tests/shape_model.py, which csrc/shape_predictor.hip meets bit for bit.
+ * The model: P landmarks, K cascade levels of T trees of `depth` levels (S = 2^depth - 1 splits, S + 1 leaves), F feature pixels per
+ * level.  initial_shape [2P] (x0, y0, x1, y1, ...), split_idx [K][T][S][2], split_thresh [K][T][S], leaves [K][T][S+1][2P],
+ * anchor_idx [K][F], deltas [K][F][2] are HOST arrays; create copies them to the current device.  Limits: 2P <= 256, F <= 4096,
+ * T <= 4096, depth <= 8; anchor_idx < P and split_idx < F are checked (CIS_EINVAL, nothing is launched).
+ * cis_shapepred_run_dev: one image [nr][nc][3] uint8 RGB and n rectangles (left, top, right, bottom) on the device -> the P landmark
+ * pixels of every rectangle, d_parts [n][P][2] (x, y), and, if d_shape is not NULL, the normalised shapes [n][2P] float32.  Only
+ * enqueues on `stream`, allocates nothing, returns at once for n = 0; the handle has no workspace, so calls may overlap.
+ * cis_dlib_decode_reals: HOST helper of the model reader (featurizer/shape_predictor.py): n floats of dlib's stream serialisation (each
+ * an integer mantissa and an integer exponent, value = mantissa * 2^exponent) from buf[*pos...]; advances *pos; at the first bad
+ * control byte or at the end of the buffer returns CIS_EINVAL with *pos ON the offending byte. */
+typedef struct cis_shapepred cis_shapepred;
+int cis_shapepred_create(cis_shapepred** out, int P, int K, int T, int depth, int F, const float* initial_shape,
+                         const int32_t* split_idx, const float* split_thresh, const float* leaves, const int32_t* anchor_idx,
+                         const float* deltas);
+void cis_shapepred_destroy(cis_shapepred* sp);
+int cis_shapepred_run_dev(cis_shapepred* sp, const uint8_t* d_img, int nr, int nc, const int32_t* d_rects, int n, int32_t* d_parts,
+                          float* d_shape, void* stream);
+int cis_dlib_decode_reals(const uint8_t* buf, size_t len, size_t* pos, float* out, size_t n);
+
 #ifdef __cplusplus
 }
 #endif
