@@ -137,6 +137,8 @@ _PROTOS = {
     "cis_train_cov_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "cis_train_rotation_pack_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "cis_sym_eig_dev": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cis_sym_eig_large_workspace": (c_int64, [c_int]),
+    "cis_sym_eig_large_dev": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "cis_index_last_stats": (c_int, [c_void_p, c_void_p]),
     "cis_index_last_scan_kernel": (c_int, [c_void_p]),
     "cis_cnn_create": (c_int, [POINTER(c_void_p), c_int, c_void_p, c_int]),

@@ -17,6 +17,7 @@
 // have, and the transposed vectors live in the matrix's own slice of d_V (128 KiB, read and written by this workgroup only, between
 // barriers; it stays in the caches), which is read back into A's LDS at the end and written out in its final layout.
 #include "common.h"
+#include "sym_eig.h"
 
 namespace {
 
@@ -198,7 +199,10 @@ extern "C" int cis_sym_eig_dev(const double* d_A, int64_t batch, int d, double* 
     if (batch == 0) return CIS_OK;
     CIS_REQUIRE(d_A && d_W && d_V, "NULL d_A, d_W or d_V");
     CIS_TRY(cis_lazy_init());
-    hipStream_t st = (hipStream_t)stream;
+    return cis_sym_eig_launch(d_A, batch, d, d_W, d_V, d_info, (hipStream_t)stream);
+}
+
+int cis_sym_eig_launch(const double* d_A, int64_t batch, int d, double* d_W, double* d_V, int32_t* d_info, hipStream_t st) {
     // a round has d/2 * d work items per phase: 128 threads cover d <= 32 (7 workgroups of 21 KiB per CU), 512 threads d <= 64
     // (2 x 69 KiB), 1024 threads the one workgroup a CU holds beyond
     if (d <= 32) return launch_sym_eig<128, true>(d_A, batch, d, d_W, d_V, d_info, st);

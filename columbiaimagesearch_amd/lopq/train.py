@@ -5,7 +5,8 @@ Python loops: covariance accumulators become matrix products.  k-means results d
 scikit-learn version, so training is judged by distortion/recall, not bit parity (SURVEY.md
 section 8c caveat ii, section 8f row 3).  Not on the encode/search hot path.
 
-Four switches move work to the GPU, all off by default: ACCUM_BACKEND ("hip": covariance accumulations and projections),
+Five switches move work to the GPU, all off by default: PCA_BACKEND ("device": train_pca's sums and eigendecomposition,
+train_pca_dev with cis_sym_eig_large_dev, csrc/sym_eig_block.hip), ACCUM_BACKEND ("hip": covariance accumulations and projections),
 KMEANS_BACKEND ("hip" / "device": Lloyd iterations), SEED_BACKEND ("device": the k-means++ seeds of kmeans_dev are drawn on the
 resident data by cis_kmeanspp_dev, csrc/kmeans_seed.hip, and never visit the host) and ROTATION_BACKEND ("device": the whole
 local-rotation stage -- residuals, covariances, eigendecompositions (cis_sym_eig_dev, csrc/sym_eig.hip), projections -- on the
@@ -416,8 +417,105 @@ def _kmeans(data, k, iters, n_init, random_state, dev=None):
     return km.cluster_centers_
 
 
+def sym_eig_large_dev(A, block=0):
+    """Eigendecomposition of one float64 [d, d] symmetric tensor on the GPU, 1 <= d <= 4096 (cis_sym_eig_large_dev,
+    csrc/sym_eig_block.hip: block Jacobi in HBM, blocks of `block` = 64 or 32 columns, 0 = the default): (W [d] ascending, V [d, d]
+    with column j the eigenvector of W[j], info [1] int32: the block sweeps used, or -1 for a matrix that was not finite or did not
+    converge).  Tensors on A's device.  The call waits for the device once per block sweep; the workspace is a torch allocation."""
+    import torch
+    from .. import _lib
+    if not (_is_tensor(A) and A.is_cuda and A.dim() == 2 and A.dtype == torch.float64 and A.shape[0] == A.shape[1]):
+        raise ValueError("expected a float64 [d, d] tensor on the GPU")
+    A = A.contiguous()
+    d = int(A.shape[0])
+    L = _lib.lib()
+    need = int(L.cis_sym_eig_large_workspace(d))
+    if need < 0:
+        _lib.check(need)
+    W = torch.empty(d, dtype=torch.float64, device=A.device)
+    V = torch.empty((d, d), dtype=torch.float64, device=A.device)
+    info = torch.empty(1, dtype=torch.int32, device=A.device)
+    work = torch.empty(need, dtype=torch.uint8, device=A.device)
+    _lib.check(L.cis_sym_eig_large_dev(A.data_ptr(), d, int(block), W.data_ptr(), V.data_ptr(), info.data_ptr(), work.data_ptr(), need,
+                                       _stream(A)))
+    return W, V, info
+
+
+# "host": train_pca below in numpy (its sums through cis_train_gram with ACCUM_BACKEND = "hip").  "device": train_pca_dev: the sums by
+# cis_train_gram_dev and the eigendecomposition by cis_sym_eig_large_dev on data that is, or is uploaded once to, the GPU.
+PCA_BACKEND = "host"
+PCA_GRAM_ROWS = 32768  # rows converted to float64 and summed per cis_train_gram_dev call
+
+
+def train_pca_dev(x, pca_dims=256, pca_subsample=None, stats=None):
+    """train_pca on the GPU (PCA_BACKEND = "device"): the same dict and pca_dims, as numpy arrays.  x: a float32 or float64 [n, D]
+    tensor on the GPU, or a numpy array, uploaded once as float32 (a float64 array as float64).  The sums G = X^T X and S = sum x
+    come from cis_train_gram_dev with one group, PCA_GRAM_ROWS rows at a time as float64; mu = S / n and A = G / (n - 1) - mu mu^T
+    are the host's expressions; cis_sym_eig_large_dev's last pca_dims eigenpairs are permuted by eigenvalue_allocation(2, E), which
+    runs on the host on pca_dims numbers.  D <= 4096.  stats: a dict that receives the stage times in seconds (each stage waits for
+    the device) and the block sweeps."""
+    import time
+    import torch
+    if _is_tensor(x):
+        if not (x.is_cuda and x.dim() == 2 and x.dtype in (torch.float32, torch.float64)):
+            raise ValueError("expected a float32 or float64 [n, D] tensor on the GPU, got %s %s on %s" % (x.dtype, tuple(x.shape), x.device))
+        dev = x.device
+    else:
+        x = np.asarray(x)
+        if x.ndim != 2:
+            raise ValueError("expected an [n, D] matrix, got shape %r" % (x.shape,))
+        dev = torch.device("cuda", torch.cuda.current_device())
+    if pca_subsample:
+        x = x[:min(pca_subsample, x.shape[0])]
+    n, D = int(x.shape[0]), int(x.shape[1])
+    pca_dims = min(pca_dims, D)
+
+    def lap(t0):
+        torch.cuda.synchronize(dev)
+        return time.perf_counter() - t0
+
+    t0 = time.perf_counter()
+    if not _is_tensor(x):
+        x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64 if x.dtype == np.float64 else np.float32)).to(dev)
+    t_upload = lap(t0) if stats is not None else 0.0
+
+    t0 = time.perf_counter()
+    G = torch.zeros((D, D), dtype=torch.float64, device=dev)
+    S = torch.zeros(D, dtype=torch.float64, device=dev)
+    for a in range(0, n, PCA_GRAM_ROWS):
+        rows = x[a:a + PCA_GRAM_ROWS].to(torch.float64).contiguous()
+        off = torch.tensor([0, int(rows.shape[0])], dtype=torch.int64, device=dev)
+        g, s = gram_dev(rows, off, 1)
+        G += g[0]
+        S += s[0]
+    # a division by a number on the device: torch turns a division by a host scalar into a product with its inverse
+    mu = S / torch.tensor(float(n), dtype=torch.float64, device=dev)
+    A = G / torch.tensor(float(n - 1), dtype=torch.float64, device=dev) - torch.outer(mu, mu)
+    t_sums = lap(t0) if stats is not None else 0.0
+
+    t0 = time.perf_counter()
+    W, V, info = sym_eig_large_dev(A)
+    sweeps = int(info.cpu()[0])
+    t_eig = lap(t0) if stats is not None else 0.0
+    if sweeps < 0:
+        raise FloatingPointError("no eigendecomposition for the PCA covariance (not finite, or not converged)")
+
+    t0 = time.perf_counter()
+    E = W[D - pca_dims:].cpu().numpy()
+    perm = torch.from_numpy(eigenvalue_allocation(2, E)).to(dev)
+    P = V[:, D - pca_dims:][:, perm]
+    out = {"mu": mu.cpu().numpy(), "P": P.cpu().numpy(), "E": E, "A": A.cpu().numpy(), "c": n}
+    if stats is not None:
+        stats.update(upload_s=t_upload, sums_s=t_sums, eig_s=t_eig, rest_s=lap(t0), block_sweeps=sweeps)
+    return out, pca_dims
+
+
 def train_pca(data, pca_dims=256, pca_subsample=None):
     """PCA basis with variance balanced over the two halves.  reference: lopq/lopq/model.py:242-287."""
+    if PCA_BACKEND not in ("host", "device"):
+        raise ValueError("PCA_BACKEND must be 'host' or 'device', got %r" % (PCA_BACKEND,))
+    if PCA_BACKEND == "device":
+        return train_pca_dev(data, pca_dims, pca_subsample)
     if pca_subsample:
         data = data[:min(pca_subsample, data.shape[0])]
     n, D = data.shape

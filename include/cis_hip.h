@@ -483,6 +483,28 @@ int cis_train_rotation_pack_dev(const double* d_V, const int32_t* d_perm, int gr
  * The call only enqueues on `stream` and needs no workspace. */
 int cis_sym_eig_dev(const double* d_A, int64_t batch, int d, double* d_W, double* d_V, int32_t* d_info, void* stream);
 
+/* Symmetric eigendecomposition of ONE float64 matrix of 1 <= d <= 4096 that lives in HBM (csrc/sym_eig_block.hip): the eigh of the PCA
+ * stage of training.  Cyclic two-sided block Jacobi: the matrix is cut into blocks of `block` columns (64 or 32; 0 takes the default:
+ * 64 up to d = 128, 32 beyond, the faster of the two at d = 512 ... 4096), block pairs are visited in a round-robin ordering, the
+ * disjoint pairs of a round at once: their 2 block x 2 block pivots are diagonalised as one batch by the solver of cis_sym_eig_dev,
+ * and A <- Q^T A Q, V <- V Q are float64 tile products.  d need not be a multiple of the block: the matrix is padded with zero rows
+ * and columns, which stay exactly decoupled and are dropped at the end.
+ * d_A [d][d] symmetric (never written; its lower triangle is read, as by numpy.linalg.eigh), d_W [d], d_V [d][d] and the sign rule as
+ * for cis_sym_eig_dev, d_info one int32 or NULL: the block sweeps used, or -1 when the input was not finite, a pivot failed or the
+ * cap of 40 block sweeps was reached (W and V are then unspecified).
+ * The solve is done after a block sweep in which every pivot's first sweep rotated nothing.  For d <= 128 and block 0 or 64 the
+ * matrix is one pivot and d_W holds cis_sym_eig_dev's eigenvalues bit for bit.
+ * Bounds (tests/test_sym_eig_large.py at d <= 320, u = 2^-53): |A V - V diag(W)| and |W - eigvalsh(A)| within C d u |A|_2 and
+ * |V^T V - I| within C d u, C = 59 for blocks of 32 and 35 for blocks of 64; the pivots' orthogonality errors add up over the rounds.
+ * The workspace is the caller's: d_work, device memory aligned to 256 bytes, of at least cis_sym_eig_large_workspace(d) bytes (about
+ * 2 (d + 64)^2 doubles; CIS_EINVAL, returned as the int64, for a d outside 1 .. 4096).  Limits (CIS_EINVAL, before the device is
+ * touched): 1 <= d <= 4096; block 0, 32 or 64; d_A, d_W, d_V and d_work not NULL; work_bytes at least the workspace.
+ * The call enqueues on `stream` and blocks on one 4-byte read-back per block sweep (the status of the sweep's pivots decides whether
+ * another follows): when it returns, at most the finalisation is still in flight on `stream`.  It cannot be captured into a graph. */
+int64_t cis_sym_eig_large_workspace(int d);
+int cis_sym_eig_large_dev(const double* d_A, int d, int block, double* d_W, double* d_V, int32_t* d_info, void* d_work,
+                          int64_t work_bytes, void* stream);
+
 /* Counters of the last search on this handle (for bench.py's roofline):
  *   stats[0] candidates scanned (sum over queries of retrieved items on this shard)
  *   stats[1] (query, cell) work items   stats[2] ADC tables built   stats[3] scan kernel launches */
