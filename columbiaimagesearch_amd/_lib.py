@@ -103,6 +103,17 @@ _PROTOS = {
     "cis_shapepred_destroy": (None, [c_void_p]),
     "cis_shapepred_run_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "cis_dlib_decode_reals": (c_int, [c_void_p, ctypes.c_size_t, POINTER(ctypes.c_size_t), c_void_p, ctypes.c_size_t]),
+    "cis_fhogdet_create": (c_int, [POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                   c_double, c_double]),
+    "cis_fhogdet_destroy": (None, [c_void_p]),
+    "cis_fhogdet_workspace_bytes": (c_int64, [c_void_p, c_int, c_int, c_int]),
+    "cis_fhogdet_run_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int,
+                                    c_void_p, c_void_p]),
+    "cis_fhogdet_profile": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int,
+                                    c_void_p, c_void_p, POINTER(c_float)]),
+    "cis_resize_bilinear_rgb_dev": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
+    "cis_fhog_extract_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "cis_fhog_scores_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "cis_exchange_offsets_dev": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cis_rerank_dev": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "cis_idmap_build_dev": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),

@@ -9,10 +9,13 @@ the featurizer's dtype) so that the rows can be pushed to HBase unchanged (extra
 
 Both branches of `process_buffer` are built: `detector_type == "full"` (no detector: the whole image is featurized,
 :249-253) and the detector branch (:236-247: one feature per detection, column ``<extr_str>_<l>_<t>_<r>_<b>_<score>``).
-The detector itself (dlib's HOG face detector, detector/dlib_detector.py) is out of scope for this repo (SURVEY.md
-section 2 row 10): `detector_type == "dlib"` builds it from the `dlib` module when that is importable, and any object
-with the reference's ``detect_from_buffer_noinfos(img_buffer, up_sample=1) -> (img, [bbox dict])`` can be passed as
-``detector=``.
+The detector (dlib's HOG face detector, detector/dlib_detector.py) has two backends, chosen by the configuration key
+``<extr_prefix>detector_backend``: ``"dlib"`` (the default) builds it from the `dlib` module when that is importable;
+``"hip"`` loads the detector file ``<extr_prefix>det_path`` (an .npz, or what dlib's ``detector.save`` writes) into
+detector/hog_detector.py:HOGDetectorHIP, the same scheme as HIP kernels (csrc/hog_detector.hip; parity with dlib itself is
+unpinned), so that the face configuration runs from the image bytes to the rows without dlib.  The column names keep
+``dlib`` either way: `detector_type` is unchanged.  Any object with the reference's
+``detect_from_buffer_noinfos(img_buffer, up_sample=1) -> (img, [bbox dict])`` can still be passed as ``detector=``.
 """
 from ..featurizer.featsio import get_feat_dtype, normfeatB64encode
 from ..featurizer.generic_featurizer import get_featurizer
@@ -73,9 +76,19 @@ class DLibHOGDetector(object):
                      for d, s in zip(dets, scores)]
 
 
-def get_detector(detector_type):
-    """reference: detector/utils.py:100-112"""
+def get_detector(detector_type, global_conf=None, prefix=None):
+    """reference: detector/utils.py:100-112; `<prefix>detector_backend` = "dlib" (default) or "hip" (`<prefix>det_path`)"""
     if detector_type == "dlib":
+        conf = global_conf or {}
+        backend = conf.get((prefix or "") + "detector_backend", "dlib")
+        if backend == "hip":
+            key = (prefix or "") + "det_path"
+            if key not in conf:
+                raise ValueError("[get_detector: error] detector_backend = 'hip' needs the detector file in '{}'.".format(key))
+            from ..detector.hog_detector import HOGDetectorHIP, load_fhog_detector
+            return HOGDetectorHIP(load_fhog_detector(conf[key]))
+        if backend != "dlib":
+            raise ValueError("[get_detector: error] unknown 'detector_backend' {}: 'dlib' or 'hip'.".format(backend))
         return DLibHOGDetector()
     if detector_type == "full":
         return None
@@ -90,7 +103,7 @@ class GenericExtractor(object):
         self.input_type = input_type
         self.extr_column = extr_column
         self.global_conf = global_conf
-        self.detector = detector if detector is not None else get_detector(self.detector_type)
+        self.detector = detector if detector is not None else get_detector(self.detector_type, self.global_conf, extr_prefix)
         self.featurizer = get_featurizer(self.featurizer_type, self.global_conf, prefix=extr_prefix)
         self.extr_str = str(self.extr_column + ":" + build_extr_str(featurizer_type, detector_type, input_type))
         self.extr_str_processed = str(self.extr_column + ":" + build_extr_str_processed(featurizer_type, detector_type, input_type))

@@ -111,3 +111,13 @@ def shape_predictor_model(seed=0, P=68, K=15, T=500, depth=4, F=500):
         leaves=(rs.randn(K, T, S + 1, 2 * P) * (0.01 / T)).astype(np.float32),
         anchor_idx=rs.randint(0, P, size=(K, F)).astype(np.int32),
         deltas=(0.1 * rs.randn(K, F, 2)).astype(np.float32))
+
+
+def fhog_detector_model(seed=0, F=5, fr=10, fc=10, padding=0, pyramid_n=6, thresh=1.0, scale=0.02, **kw):
+    """A seeded HOG detector model (detector/hog_detector.py) with random weights; the defaults are the dimensions of dlib's frontal face
+    detector (5 filters of 10 x 10 cells, pyramid_down<6>).  FHOG features lie in [0, 0.4]: weights of `scale` around zero give saliencies
+    of about scale * sqrt(31 fr fc) * 0.1, so thresh = 1 passes few positions of a random texture.  kw: the other model fields."""
+    from ..detector.hog_detector import FHOGDetectorModel
+    rs = np.random.RandomState(seed)
+    return FHOGDetectorModel(w=(scale * rs.randn(F, 31, fr, fc)).astype(np.float32), thresh=np.full(F, thresh, np.float32), padding=padding,
+                             pyramid_n=pyramid_n, **kw)

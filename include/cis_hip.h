@@ -601,6 +601,51 @@ int cis_shapepred_run_dev(cis_shapepred* sp, const uint8_t* d_img, int nr, int n
                           float* d_shape, void* stream);
 int cis_dlib_decode_reals(const uint8_t* buf, size_t len, size_t* pos, float* out, size_t n);
 
+/* ---- face detection: dlib's get_frontal_face_detector() scheme, object_detector<scan_fhog_pyramid<pyramid_down<N>>> ---------------
+ * (`self.detector.run(img, up_sample, 0)`, cufacesearch/cufacesearch/detector/dlib_detector.py:33).  Restated from dlib's published
+ * fhog.h, scan_fhog_pyramid.h and box_overlap_testing.h as remembered; parity with dlib itself is UNPINNED (no dlib, no detector file
+ * here, and no real detector file has ever met the reader): the yardstick is the numpy model tests/fhog_model.py, which
+ * csrc/hog_detector.hip meets bit for bit.  Known deviations: the saliency is the direct correlation in one stated order (dlib filters
+ * separably after an SVD), and one bilinear resize stands in for pyramid_up and pyramid_down<N>.
+ * cis_fhogdet_create: F filters of filter_rows x filter_cols x 31 float32 weights, w [F][31][filter_rows][filter_cols] (plane-major, the
+ * order of dlib's w vector), and their thresholds [F], HOST arrays copied to the current device.  Checked with CIS_EINVAL before anything
+ * is launched: F <= 16, filter sides <= 16, cell_size = 8, 0 <= 2 padding < filter sides, pyramid_n in 2..16, max_levels and the minimal
+ * layer size >= 1, finite weights and thresholds, overlap thresholds in [0, 1].
+ * cis_fhogdet_workspace_bytes: the workspace one call needs for an nr x nc image (every level's size follows from nr, nc on the host);
+ * a negative CIS_E* code on bad arguments.  One workspace serves one call at a time; calls on different streams take different ones.
+ * cis_fhogdet_run_dev: d_img [nr][nc][3] uint8 RGB; up_sample 0, 1 or 2.  Only enqueues on `stream` (up_sample + levels - 1 resizes, one
+ * 16-byte memset, four kernels), allocates nothing and waits on nothing.  d_rects [max_dets][4] int32 (left, top, right, bottom), the
+ * layout cis_shapepred_run_dev takes, d_scores [max_dets] float32, d_filter [max_dets] int32, in the order dlib's run returns them
+ * (score descending, ties by level, filter, row, column).  At most max_dets rows are written; d_count[0] holds the number KEPT even if
+ * that is larger, so a truncated answer is visible, d_count[1] the number of candidates.  The candidate buffer holds 8192 entries: past
+ * that d_count[1] still counts, nothing is written out of bounds, WHICH 8192 candidates took part is arbitrary and the Python surface
+ * raises.  More than 48 pyramid levels or more than 2047 cells a side (after up-sampling) are CIS_EINVAL.
+ * cis_resize_bilinear_rgb_dev: the resize of the pyramid and of the up-sampling, [nr][nc][3] -> [onr][onc][3] uint8.
+ * cis_fhog_extract_dev: Felzenszwalb's 31-plane HOG (dlib's extract_fhog_features) of one image: d_hist [cells_nr][cells_nc][18] float32
+ * scratch (cells = (int)(n / 8 + 0.5); the cell histograms are left there), d_feat [31][cells_nr - 2 + pad_rows - 1][cells_nc - 2 +
+ * pad_cols - 1] float32 PLANE-MAJOR, the layout the scorer reads, the zero border of (pad - 1) / 2 in front included; pad = 1: none.
+ * Fewer than 3 cells a side: returns CIS_OK and writes nothing.
+ * cis_fhog_scores_dev: a TEST entry (allocates, copies the HOST weights w and waits): the correlation of every filter at every position
+ * of d_feat [31][rows][cols], d_scores [F][rows - filter_rows + 1][cols - filter_cols + 1]; nothing is written where the filter does
+ * not fit. */
+typedef struct cis_fhogdet cis_fhogdet;
+int cis_fhogdet_create(cis_fhogdet** out, int F, int filter_rows, int filter_cols, int cell_size, int padding, int pyramid_n, int max_levels,
+                       int min_layer_w, int min_layer_h, const float* w, const float* thresh, double iou_thresh, double covered_thresh);
+void cis_fhogdet_destroy(cis_fhogdet* h);
+int64_t cis_fhogdet_workspace_bytes(cis_fhogdet* h, int nr, int nc, int up_sample);
+int cis_fhogdet_run_dev(cis_fhogdet* h, const uint8_t* d_img, int nr, int nc, int up_sample, double adjust_threshold, void* d_ws,
+                        int64_t ws_bytes, int32_t* d_rects, float* d_scores, int32_t* d_filter, int max_dets, int32_t* d_count, void* stream);
+/* cis_fhogdet_run_dev with HIP events around its five stages (resizes, cell histograms, features, scores, sort + NMS): WAITS for the call
+ * and writes the stage times in milliseconds to the HOST array stage_ms [5] (tools/bench_hog_detector.py). */
+int cis_fhogdet_profile(cis_fhogdet* h, const uint8_t* d_img, int nr, int nc, int up_sample, double adjust_threshold, void* d_ws,
+                        int64_t ws_bytes, int32_t* d_rects, float* d_scores, int32_t* d_filter, int max_dets, int32_t* d_count, void* stream,
+                        float* stage_ms);
+int cis_resize_bilinear_rgb_dev(const uint8_t* d_in, int nr, int nc, uint8_t* d_out, int onr, int onc, void* stream);
+int cis_fhog_extract_dev(const uint8_t* d_img, int nr, int nc, int cell_size, int pad_rows, int pad_cols, float* d_hist, float* d_feat,
+                         void* stream);
+int cis_fhog_scores_dev(const float* d_feat, int rows, int cols, int F, int filter_rows, int filter_cols, const float* w, float* d_scores,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif
