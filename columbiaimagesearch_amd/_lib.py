@@ -121,7 +121,13 @@ _PROTOS = {
     "cis_rerank_select_dev": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p,
                                       c_void_p, c_int, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p]),
-    "cis_featstore_create": (c_int, [POINTER(c_void_p), c_int, c_int, c_int64]),
+    "cis_merge_packed_src_dev": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cis_rerank_packed_dev": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p,
+                                      c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "cis_rerank_select_merged_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_int, c_int, c_int,
+                                             c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cis_featstore_create":(c_int, [POINTER(c_void_p), c_int, c_int, c_int64]),
     "cis_featstore_destroy": (None, [c_void_p]),
     "cis_featstore_size": (c_int64, [c_void_p]),
     "cis_featstore_reserve": (c_int, [c_void_p, c_int64, c_void_p]),

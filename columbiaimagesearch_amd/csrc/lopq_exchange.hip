@@ -203,7 +203,7 @@ __global__ __launch_bounds__(WPB * 64) void k_merge_packed(const cis_hit* __rest
                                                       const int64_t* __restrict__ off, const int32_t* __restrict__ cnt, int nq,
                                                       int limit, int64_t* __restrict__ out_ids, double* __restrict__ out_dists,
                                                       int* __restrict__ out_n, int32_t* __restrict__ out_cells,
-                                                      uint32_t* __restrict__ out_pos) {
+                                                      uint32_t* __restrict__ out_pos, int64_t* __restrict__ out_src /* or NULL */) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wq = threadIdx.x >> 6;
     const int q = blockIdx.x * WPB + wq;
@@ -237,6 +237,7 @@ __global__ __launch_bounds__(WPB * 64) void k_merge_packed(const cis_hit* __rest
                 out_dists[o1 + x] = dist;
                 if (out_cells) out_cells[o1 + x] = cell;
                 if (out_pos) out_pos[o1 + x] = pos;
+                if (out_src) out_src[o1 + x] = x < nv1 ? base + x : -1;
             }
             if (lane == 0 && out_n) out_n[q] = nv1;
             return;
@@ -298,6 +299,7 @@ __global__ __launch_bounds__(WPB * 64) void k_merge_packed(const cis_hit* __rest
         out_dists[o + x] = dist;
         if (out_cells) out_cells[o + x] = cell;
         if (out_pos) out_pos[o + x] = pos;
+        if (out_src) out_src[o + x] = x < nv ? (int64_t)pay[x] : -1;
     }
     if (lane == 0 && out_n) out_n[q] = nv;
 }
@@ -410,6 +412,22 @@ extern "C" int cis_exchange_offsets_dev(const int32_t* d_cnt_all, int world, int
     return CIS_OK;
 }
 
+// The one-wave merge (limit <= 3072); d_src (or NULL) receives the index in d_parts of every result's record.
+static void launch_merge_packed(const cis_hit* d_parts, int world, int64_t stride, const int64_t* d_off, const int32_t* d_cnt, int nq,
+                                int limit, int64_t* d_ids, double* d_dists, int32_t* d_n_found, int32_t* d_cells, uint32_t* d_pos,
+                                int64_t* d_src, hipStream_t st) {
+    const dim3 g((unsigned)ceil_div(nq, 4));
+    if (limit <= 128)
+        hipLaunchKernelGGL((k_merge_packed<256, 4>), g, dim3(256), (size_t)4 * 3 * 256 * 8, st, d_parts, world, stride, d_off, d_cnt, nq, limit,
+                           d_ids, d_dists, d_n_found, d_cells, d_pos, d_src);
+    else if (limit <= 512)
+        hipLaunchKernelGGL((k_merge_packed<1024, 4>), g, dim3(256), (size_t)4 * 3 * 1024 * 8, st, d_parts, world, stride, d_off, d_cnt, nq,
+                           limit, d_ids, d_dists, d_n_found, d_cells, d_pos, d_src);
+    else  // one wave per workgroup with 96 KB of LDS: 4096 keys per round, `limit` of them carried over
+        hipLaunchKernelGGL((k_merge_packed<4096, 1>), dim3((unsigned)nq), dim3(64), (size_t)3 * 4096 * 8, st, d_parts, world, stride, d_off,
+                           d_cnt, nq, limit, d_ids, d_dists, d_n_found, d_cells, d_pos, d_src);
+}
+
 extern "C" int cis_merge_packed_dev(const cis_hit* d_parts, int world, int64_t stride, const int64_t* d_off,
                                     const int32_t* d_cnt, int nq, int limit, int64_t* d_ids, double* d_dists,
                                     int32_t* d_n_found, int32_t* d_cells, uint32_t* d_pos, void* stream) {
@@ -418,19 +436,24 @@ extern "C" int cis_merge_packed_dev(const cis_hit* d_parts, int world, int64_t s
     CIS_TRY(cis_lazy_init());
     if (nq == 0 || limit == 0) return CIS_OK;
     hipStream_t st = (hipStream_t)stream;
-    const dim3 g((unsigned)ceil_div(nq, 4));
-    if (limit <= 128)
-        hipLaunchKernelGGL((k_merge_packed<256, 4>), g, dim3(256), (size_t)4 * 3 * 256 * 8, st, d_parts, world, stride, d_off, d_cnt, nq, limit,
-                           d_ids, d_dists, d_n_found, d_cells, d_pos);
-    else if (limit <= 512)
-        hipLaunchKernelGGL((k_merge_packed<1024, 4>), g, dim3(256), (size_t)4 * 3 * 1024 * 8, st, d_parts, world, stride, d_off, d_cnt, nq,
-                           limit, d_ids, d_dists, d_n_found, d_cells, d_pos);
-    else if (limit <= 3072)  // one wave per workgroup with 96 KB of LDS: 4096 keys per round, `limit` of them carried over
-        hipLaunchKernelGGL((k_merge_packed<4096, 1>), dim3((unsigned)nq), dim3(64), (size_t)3 * 4096 * 8, st, d_parts, world, stride, d_off,
-                           d_cnt, nq, limit, d_ids, d_dists, d_n_found, d_cells, d_pos);
+    if (limit <= MAX_LDS_LIMIT)
+        launch_merge_packed(d_parts, world, stride, d_off, d_cnt, nq, limit, d_ids, d_dists, d_n_found, d_cells, d_pos, nullptr, st);
     else  // any limit: places by binary search in the other shards' ranked lists
         hipLaunchKernelGGL(k_merge_packed_ranked, dim3((unsigned)nq), dim3(256), 0, st, d_parts, world, stride, d_off, d_cnt, nq, limit,
                            d_ids, d_dists, d_n_found, d_cells, d_pos);
+    CIS_CHECK_HIP(hipGetLastError());
+    return CIS_OK;
+}
+
+extern "C" int cis_merge_packed_src_dev(const cis_hit* d_parts, int world, int64_t stride, const int64_t* d_off, const int32_t* d_cnt,
+                                        int nq, int limit, int64_t* d_ids, double* d_dists, int32_t* d_n_found, int32_t* d_cells,
+                                        uint32_t* d_pos, int64_t* d_src_rec, void* stream) {
+    CIS_REQUIRE(world >= 1 && nq >= 0 && limit >= 0 && stride >= 0, "bad merge arguments");
+    CIS_REQUIRE(limit <= MAX_LDS_LIMIT, "the merge that reports its records holds at most %d results per query (limit = %d)", MAX_LDS_LIMIT, limit);
+    CIS_REQUIRE(nq == 0 || limit == 0 || (d_parts && d_off && d_cnt && d_ids && d_dists && d_src_rec), "NULL buffer");
+    if (nq == 0 || limit == 0) return CIS_OK;
+    CIS_TRY(cis_lazy_init());
+    launch_merge_packed(d_parts, world, stride, d_off, d_cnt, nq, limit, d_ids, d_dists, d_n_found, d_cells, d_pos, d_src_rec, (hipStream_t)stream);
     CIS_CHECK_HIP(hipGetLastError());
     return CIS_OK;
 }

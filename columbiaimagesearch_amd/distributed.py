@@ -9,7 +9,10 @@ The reference has no distributed search; north_star shards the index by LOPQ coa
   ranks its candidates: ``search_partial_dev`` -> [nq, L] hits of 32 bytes;
 * ONE collective per batch: all-gather of the per-rank hit lists (nq x L x 32 B per rank);
 * every rank merges the ``world`` lists by (dist, visit_rank, pos) -- identical to the single-index
-  result because a cell lives wholly on one rank.
+  result because a cell lives wholly on one rank;
+* with a feature store per rank (``ShardedSearcher(..., features=store)``: an item's original feature lives with the rank that
+  owns its cell) the exact re-rank joins the same round: a rank measures the true distances of its own hits before the
+  exchange, they travel beside the records, and the home rank ranks the merged list by them (``search_rerank_dev``).
 
 torch.distributed is only the launcher/collective plumbing; backend "nccl" is RCCL on ROCm.  The same
 functions run on CPU tensors with the "gloo" backend (tests/test_distributed_gloo.py).
@@ -125,6 +128,83 @@ def exchange_packed(packed, cnt, group=None):
     return parts, off, cnt_all
 
 
+def exchange_packed_fixed_pair(packed, extra, cnt, stride, group=None):
+    """exchange_packed_fixed with a second payload that shares the records' layout (the true distances of the sharded re-rank:
+    extra [>= stride], one entry per record of `packed`): it is all-gathered at the same stride, so an index into the gathered
+    records is an index into the gathered payload, and the cut of an overflowing rank is the same for both.  Returns (parts,
+    extra_all [world, stride], off, cnt_all, overflow)."""
+    parts, off, cnt_all, overflow = exchange_packed_fixed(packed, cnt, stride, group)
+    if extra.shape[0] < stride:
+        raise ValueError("the second payload holds %d entries, the exchange stride is %d" % (extra.shape[0], stride))
+    return parts, all_gather_stack(extra[:stride].contiguous(), group), off, cnt_all, overflow
+
+
+def exchange_packed_pair(packed, extra, cnt, group=None):
+    """exchange_packed with the second payload of exchange_packed_fixed_pair, at the exact size (what repeats a fixed-size exchange
+    that overflowed).  Returns (parts, extra_all [world, stride], off, cnt_all)."""
+    import torch
+    parts, off, cnt_all = exchange_packed(packed, cnt, group)
+    stride = int(parts.shape[1])
+    if extra.shape[0] >= stride:
+        mine = extra[:stride]
+    else:
+        mine = torch.full((stride,), float("nan"), dtype=extra.dtype, device=extra.device)
+        mine[:extra.shape[0]] = extra
+    return parts, all_gather_stack(mine.contiguous(), group), off, cnt_all
+
+
+def sharded_rerank_nb(features, L, rerank_nb):
+    """The argument checks of the sharded re-rank, before anything is launched: nb = min(rerank_nb, L).  ValueError without a feature
+    store, for limit > 3072 (the merge that reports its records is the one-wave merge) and for nb > 1024 (what the device ranks)."""
+    if features is None:
+        raise ValueError("this searcher was given no feature store (features=...): it cannot re-rank")
+    L = int(L)
+    if L > 3072:
+        raise ValueError("the sharded re-rank merges at most 3072 results per query (limit = %d)" % L)
+    nb = L if rerank_nb is None else min(int(rerank_nb), L)
+    if nb < 0:
+        raise ValueError("rerank_nb must be >= 0")
+    if nb > 1024:
+        raise ValueError("the device re-ranking holds at most 1024 results per query (nb = %d)" % nb)
+    return nb
+
+
+def route_features_plan(coarse, owner, V, world):
+    """Where the rows of a feature batch go: (order int64 [n] -- the rows grouped by destination rank, in their own order inside a
+    group --, counts int64 [world]).  coarse [n, 2]: the rows' cells (16-bit codes as they come from the encoder, or any integer
+    tensor), owner [V * V]: the owner table of the index.  A row whose cell is out of range goes to rank 0, as its code does
+    (cis_index_route_pack_dev).  Torch on the tensors' device; CPU tensors work."""
+    import torch
+    c = coarse.reshape(-1, 2)
+    if c.dtype == getattr(torch, "uint16", None):
+        c = c.view(torch.int16)
+    c = c.to(torch.int64) & 0xffff if c.dtype == torch.int16 else c.to(torch.int64)
+    own = torch.as_tensor(np.ascontiguousarray(owner, dtype=np.int64)).to(c.device)
+    ok = (c[:, 0] >= 0) & (c[:, 0] < V) & (c[:, 1] >= 0) & (c[:, 1] < V)
+    cell = torch.where(ok, c[:, 0] * V + c[:, 1], torch.zeros_like(c[:, 0]))
+    dst = torch.where(ok, own[cell], torch.zeros_like(cell))
+    return torch.argsort(dst, stable=True), torch.bincount(dst, minlength=world)[:world]
+
+
+def route_features(coarse, ids, feats, owner, V, group=None):
+    """All-to-all routing of original features to the ranks that own their items' cells, beside route_codes: coarse [n, 2], ids [n]
+    int64, feats [n, D] are THIS rank's slice (tensors; on the CPU under gloo).  Returns the (ids, feats) this rank owns, ordered by
+    source rank and, inside a source, in the source's order.  Three collectives: split sizes, ids, rows."""
+    import torch
+    import torch.distributed as dist
+    world = dist.get_world_size(group)
+    order, counts = route_features_plan(coarse, owner, V, world)
+    D = int(feats.shape[1])
+    recv_counts = torch.empty_like(counts)
+    _a2a(recv_counts, counts, group=group)
+    sc, rc = [int(c) for c in counts.tolist()], [int(c) for c in recv_counts.tolist()]
+    got_ids = torch.empty(sum(rc), dtype=torch.int64, device=ids.device)
+    _a2a(got_ids, ids[order].contiguous(), out_splits=rc, in_splits=sc, group=group)
+    got = torch.empty((sum(rc), D), dtype=feats.dtype, device=feats.device)
+    _a2a(got.reshape(-1), feats[order].contiguous().reshape(-1), out_splits=[c * D for c in rc], in_splits=[c * D for c in sc], group=group)
+    return got_ids, got
+
+
 def route_codes(coarse, fine, ids, owner, V, group=None, M=None):
     """All-to-all routing of freshly encoded codes to the ranks that own their cells.
     coarse [n,2] uint16, fine [n,M] uint8, ids [n] int64: THIS rank's slice of the batch (host arrays).  Returns the
@@ -166,9 +246,13 @@ def route_codes(coarse, fine, ids, owner, V, group=None, M=None):
 
 
 class ShardedSearcher(object):
-    """LOPQSearcherHIP sharded by coarse cell over the ranks of a torch.distributed group."""
+    """LOPQSearcherHIP sharded by coarse cell over the ranks of a torch.distributed group.
 
-    def __init__(self, model, owner=None, group=None):
+    features: a rerank.FeatureStore on this rank's device that holds the original features of the items in the cells this rank owns
+    (put_features_routed_dev sends them there).  With it, search_rerank_dev gives the exact re-rank of the single index: every rank
+    measures its own hits before the exchange, and the distances travel beside the records."""
+
+    def __init__(self, model, owner=None, group=None, features=None):
         import torch.distributed as dist
         from .lopq.search import LOPQSearcherHIP
         self.group = group
@@ -177,6 +261,7 @@ class ShardedSearcher(object):
         self.local = LOPQSearcherHIP(model, shard=(self.rank, self.world, owner))
         self._owner = None if owner is None else np.ascontiguousarray(owner, dtype=np.int32)
         self._side = None
+        self.features = features
 
     # -- inserts against searches in flight -----------------------------------------------------------------------------------
     # search_begin runs partial searches on this object's own lane streams over VIEWS of the local index (lanes()); an insert
@@ -346,10 +431,29 @@ class ShardedSearcher(object):
                 dist.all_reduce(delta, group=self.group)
             _lib.check(L.cis_index_sub_remote_counts_dev(self.local._ix, delta.data_ptr(), stream))
             removed = int(delta.sum().item())
+            if self.features is not None:   # the features of this rank's items leave with them (ids stored elsewhere are ignored)
+                self.features.remove_dev(ids)
         finally:
             self._insert_release()
         self.local.nb_indexed = int(L.cis_index_size(self.local._ix))
         return removed
+
+    def put_features_routed_dev(self, coarse, ids, feats):
+        """The original features of THIS rank's slice of a batch (coarse [n, 2] 16-bit as for add_codes_routed_dev, ids int64 [n],
+        feats [n, D] in the store's dtype; tensors in HBM) go to the stores of the ranks that own their cells (route_features) and
+        are put there, ordered against the searches in flight like an insert.  Returns the store's (new, skipped) on this rank."""
+        if self.features is None:
+            raise ValueError("this searcher was given no feature store (features=...)")
+        V = self.local.model.V
+        owner = self._owner if self._owner is not None else np.arange(V * V) % self.world
+        got_ids, got = route_features(coarse, ids, feats, owner, V, self.group)
+        if got_ids.shape[0] == 0:
+            return 0, 0
+        self._insert_fence()
+        try:
+            return self.features.put_dev(got_ids, got)
+        finally:
+            self._insert_release()
 
     def remove_ids(self, ids):
         """remove_ids_dev on caller ids of any kind (mapped through LOPQSearcherHIP.device_ids_of; unknown ids are ignored)."""
@@ -386,24 +490,43 @@ class ShardedSearcher(object):
         self._turn += 1
         return lane
 
-    def search_begin(self, q, quota=10, limit=None):
+    def _partial(self, sv, q, quota, limit, rr):
+        """The packed partial search of `sv`; with rr = (nb, max_returned, near_dup_th) also p["true_d"], the true distances of the
+        first nb records of every list of this rank (float64, parallel to p["packed"])."""
+        p = sv.search_partial_packed_dev(q, quota=quota, limit=limit)
+        if rr is not None:
+            p["true_d"] = self.features.distances_packed_dev(q, p["packed"], p["off"], p["cnt"], rr[0])
+        return p
+
+    def _rerank_setting(self, L, rerank, rerank_nb, max_returned, near_dup_th):
+        """None for a plain search, (nb, max_returned, near_dup_th) for a re-ranked one (any of the keywords given)."""
+        if not (rerank or rerank_nb is not None or max_returned is not None or near_dup_th is not None):
+            return None
+        if (max_returned or 0) < 0:
+            raise ValueError("max_returned must be >= 0")
+        return sharded_rerank_nb(self.features, L, rerank_nb), max_returned, near_dup_th
+
+    def search_begin(self, q, quota=10, limit=None, rerank_nb=None, max_returned=None, near_dup_th=None, rerank=False):
         """This rank's partial search (asynchronous).  Returns a handle for search_end.  Consecutive calls run on different lanes
-        (see _lane): the caller's current stream for the first, side streams that wait for the caller's stream for the others."""
+        (see _lane): the caller's current stream for the first, side streams that wait for the caller's stream for the others.
+        With rerank=True or any of search_rerank_dev's keywords the handle is a re-ranked search: the rank also measures its own
+        hits here, and search_end returns search_rerank_dev's result."""
         import torch
         L = self.local._dev_args(q, quota, limit)[0]
+        rr = self._rerank_setting(L, rerank, rerank_nb, max_returned, near_dup_th)
         sv, stream = self._lane()
         if stream is None:
-            p = sv.search_partial_packed_dev(q, quota=quota, limit=limit)
+            p = self._partial(sv, q, quota, limit, rr)
             ev = torch.cuda.Event()
             ev.record()
         else:
             stream.wait_stream(torch.cuda.current_stream())  # the queries were produced on the caller's stream
             q.record_stream(stream)
             with torch.cuda.stream(stream):
-                p = sv.search_partial_packed_dev(q, quota=quota, limit=limit)
+                p = self._partial(sv, q, quota, limit, rr)
                 ev = torch.cuda.Event()
                 ev.record(stream)
-        return {"p": p, "ev": ev, "nq": int(q.shape[0]), "L": L, "searcher": sv}
+        return {"p": p, "ev": ev, "nq": int(q.shape[0]), "L": L, "searcher": sv, "rr": rr}
 
     def search_end(self, h, check=True):
         """Exchange + merge of a search_begin handle on the side stream; the result tensors are safe to use on the
@@ -417,9 +540,12 @@ class ShardedSearcher(object):
         p = h["p"]
         with torch.cuda.stream(self._side):
             self._side.wait_event(h["ev"])
-            for t in (p["packed"], p["cnt"], p["visited"]):
+            for t in (p["packed"], p["cnt"], p["visited"]) + ((p["true_d"],) if h.get("rr") else ()):
                 t.record_stream(self._side)
-            out = self._exchange_and_merge(p, h["nq"], h["L"], check=check)
+            if h.get("rr"):
+                out = self._exchange_merge_select(p, h["nq"], h["L"], h["rr"], check=check)
+            else:
+                out = self._exchange_and_merge(p, h["nq"], h["L"], check=check)
             done = torch.cuda.Event()
             done.record(self._side)
         for t in out.values():
@@ -448,6 +574,44 @@ class ShardedSearcher(object):
                 return out
         parts, off, cnt_all = exchange_packed(p["packed"], p["cnt"], self.group)  # exact size (one host read)
         return merge_packed_dev(parts, off, cnt_all, nq, L)  # HIP: one wave per query up to 3072, ranked places above
+
+    def _exchange_merge_select(self, p, nq, L, rr, check=True):
+        """_exchange_and_merge for a re-ranked search: the true distances are all-gathered beside the records at the same stride
+        (and repeated with them at the exact size after an overflow), the merge says where each result came from, and the select
+        ranks the first nb by the distance found there.  Returns rerank_dev's dict (+ "overflow" after a fixed-size exchange)."""
+        from .lopq.search import merge_packed_src_dev
+        from .rerank import rerank_select_merged_dev
+
+        def merge_select(parts, true_all, off, cnt_all):
+            m = merge_packed_src_dev(parts, off, cnt_all, nq, L)
+            return rerank_select_merged_dev(m["ids"], m["dists"], m["src_rec"], true_all.reshape(-1), rerank_nb=rr[0], max_returned=rr[1],
+                                            near_dup_th=rr[2])
+
+        if self.fixed_stride and p["packed"].is_cuda and L > 0 and nq > 0:
+            stride = exchange_stride(nq, L, self.world, self.stride_slack)
+            parts, true_all, off, cnt_all, overflow = exchange_packed_fixed_pair(p["packed"], p["true_d"], p["cnt"], stride, self.group)
+            out = merge_select(parts, true_all, off, cnt_all)
+            out["overflow"] = overflow
+            if not check or int(overflow.item()) == 0:
+                return out
+        parts, true_all, off, cnt_all = exchange_packed_pair(p["packed"], p["true_d"], p["cnt"], self.group)  # exact size (one host read)
+        return merge_select(parts, true_all, off, cnt_all)
+
+    def search_rerank_dev(self, q, quota=10, limit=None, rerank_nb=None, max_returned=None, near_dup_th=None):
+        """LOPQSearcherHIP.search_rerank_dev on the sharded index, with the features spread over the ranks' stores: this rank's packed
+        partial search, the true distances of its own hits (cis_rerank_packed_dev), ONE exchange that carries both, the merge by ADC
+        distance and the ranking by true distance.  q in the store's dtype and width.  With every item's feature on the rank that
+        owns its cell the result equals the single index's over one store that holds them all, bit for bit: rerank_dev's dict
+        (ids, dists, src, n_kept) plus ``visited``.  limit > 3072, nb > 1024 or no store: ValueError before anything is launched."""
+        sharded_rerank_nb(self.features, 0, 0)   # (no store: said before the queries are looked at)
+        L = self.local._dev_args(q, quota, limit)[0]
+        rr = self._rerank_setting(L, True, rerank_nb, max_returned, near_dup_th)
+        nq = int(q.shape[0])
+        p = self._partial(self.local, q, quota, limit, rr)
+        out = self._exchange_merge_select(p, nq, L, rr, check=True)
+        out.pop("overflow", None)
+        out["visited"] = p["visited"]
+        return out
 
     @staticmethod
     def overflowed(outs):
@@ -629,15 +793,19 @@ class RoutedSearcher(object):
         self.fallbacks = 0
         self._host = {}   # lane -> pinned record (rows sent / received, overflow) of the lane's batch in flight
 
-    def search_begin(self, q_home, quota=10, limit=None, nq_total=None):
+    def search_begin(self, q_home, quota=10, limit=None, nq_total=None, rerank_nb=None, max_returned=None, near_dup_th=None, rerank=False):
         """q_home: this rank's home slice (home_slice(nq_total, rank, world)) of a batch of nq_total queries.  nq_total sizes the blocks
-        of the query all-to-all, which must be the same on every rank: pass it when the slices are ragged (default: world x this slice)."""
+        of the query all-to-all, which must be the same on every rank: pass it when the slices are ragged (default: world x this slice).
+        With rerank=True or any of search_rerank_dev's keywords, search_end returns the re-ranked result."""
         import torch
         from . import _lib
+        L = self.sh.local._dev_args(q_home, quota, limit)[0]
+        rr = self.sh._rerank_setting(L, rerank, rerank_nb, max_returned, near_dup_th)
+        if rr is not None and not (q_home.dtype == self.sh.features.dtype and int(q_home.shape[1]) == self.sh.features.D):
+            raise ValueError("q_home must have the feature store's dtype and width")
         sv, stream = self.sh._lane()
         cur = torch.cuda.current_stream()
         st = stream if stream is not None else cur
-        L = sv._dev_args(q_home, quota, limit)[0]
         nqh, D = int(q_home.shape[0]), int(q_home.shape[1])
         row_bytes = D * q_home.element_size()
         cap = route_capacity(-(-int(nq_total) // self.world) if nq_total is not None else nqh, row_bytes // 4, self.world, self.slack)
@@ -661,11 +829,13 @@ class RoutedSearcher(object):
             ev = torch.cuda.Event()
             ev.record(st)
         return {"sv": sv, "st": st, "q_home": q_home, "slot": slot, "recv_q": recv_q, "visited": visited, "host": host, "ev": ev,
-                "quota": quota, "limit": limit, "L": L, "nqh": nqh}
+                "quota": quota, "limit": limit, "L": L, "nqh": nqh, "rr": rr}
 
     def search_end(self, h):
         import torch
-        from .lopq.search import merge_packed_dev
+        from .lopq.search import merge_packed_dev, merge_packed_src_dev
+        from .rerank import rerank_select_merged_dev
+        rr = h.get("rr")
         h["ev"].synchronize()  # the one host read of the batch: rows sent / received, overflow
         W = self.world
         host = h["host"].tolist()
@@ -678,8 +848,11 @@ class RoutedSearcher(object):
                 q_all = all_gather_rows(h["q_home"], self.group)
                 sizes = all_gather_stack(torch.tensor([nqh], dtype=torch.int64, device=q_all.device), self.group).reshape(-1).tolist()
                 lo = int(sum(sizes[:self.rank]))
-                p = sv.search_partial_packed_dev(q_all.contiguous(), quota=h["quota"], limit=h["limit"])  # this lane's handle and stream
-                full = self.sh._exchange_and_merge(p, int(q_all.shape[0]), L, check=True)
+                p = self.sh._partial(sv, q_all.contiguous(), h["quota"], h["limit"], rr)  # this lane's handle and stream
+                if rr is not None:
+                    full = self.sh._exchange_merge_select(p, int(q_all.shape[0]), L, rr, check=True)
+                else:
+                    full = self.sh._exchange_and_merge(p, int(q_all.shape[0]), L, check=True)
                 full.pop("overflow", None)
                 out = {k: v[lo:lo + nqh] for k, v in full.items()}
                 out["visited"] = p["visited"][lo:lo + nqh]
@@ -698,7 +871,24 @@ class RoutedSearcher(object):
             if rec.shape[0] == 0:
                 rec = torch.zeros((1, 4), dtype=torch.int64, device=rows.device)
             off, cnt = routed_merge_tables_dev(h["slot"], n_sent, rec, L)
-            out = merge_packed_dev(rec, off, cnt, nqh, L)
+            if rr is not None:
+                # the owner measures the rows it answered (the dense layout: list r = records [r L, r L + L), empty slots give NaN);
+                # the distances go home in a second all-to-all with the hits' splits
+                n_rows = int(rows.shape[0])
+                if n_rows and L > 0:
+                    own = hits.reshape(-1).view(torch.int64).reshape(-1, 4)
+                    true_own = self.sh.features.distances_packed_dev(
+                        rows.contiguous(), own, torch.arange(n_rows, dtype=torch.int64, device=rows.device) * L,
+                        torch.full((n_rows,), L, dtype=torch.int32, device=rows.device), rr[0])
+                else:
+                    true_own = torch.empty(0, dtype=torch.float64, device=rows.device)
+                true_back = torch.empty(int(sum(n_sent)) * L, dtype=torch.float64, device=rows.device)
+                _a2a(true_back, true_own, out_splits=[int(c) * L for c in n_sent], in_splits=[int(c) * L for c in n_recv], group=self.group)
+                m = merge_packed_src_dev(rec, off, cnt, nqh, L)
+                out = rerank_select_merged_dev(m["ids"], m["dists"], m["src_rec"], true_back, rerank_nb=rr[0], max_returned=rr[1],
+                                               near_dup_th=rr[2])
+            else:
+                out = merge_packed_dev(rec, off, cnt, nqh, L)
             out["visited"] = h["visited"]
             done = torch.cuda.Event(); done.record(st)
         for t in out.values():
@@ -709,6 +899,13 @@ class RoutedSearcher(object):
 
     def search_batch_dev(self, q_home, quota=10, limit=None, nq_total=None):
         return self.search_end(self.search_begin(q_home, quota=quota, limit=limit, nq_total=nq_total))
+
+    def search_rerank_dev(self, q_home, quota=10, limit=None, rerank_nb=None, max_returned=None, near_dup_th=None, nq_total=None):
+        """ShardedSearcher.search_rerank_dev for this rank's home slice: the owners measure the rows they answered, the distances
+        return beside the hits, the home rank merges by ADC distance and ranks by true distance.  After an overflow of the query
+        blocks the all-gather protocol answers the batch, re-ranked alike."""
+        return self.search_end(self.search_begin(q_home, quota=quota, limit=limit, nq_total=nq_total, rerank_nb=rerank_nb,
+                                                 max_returned=max_returned, near_dup_th=near_dup_th, rerank=True))
 
 
 def all_gather_rows(x, group=None):

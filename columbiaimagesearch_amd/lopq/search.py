@@ -641,6 +641,19 @@ def merge_packed_dev(parts, off, cnt, nq, L, with_codes=False):
     """Merge packed per-shard hit lists: parts [world, stride, 4] int64 (cis_hit records; or flat [n, 4] with absolute offsets), off [world, nq] int64,
     cnt [world, nq] int32 -> dict like search_batch_dev.  This is what follows the all-gather over xGMI: only valid
     hits travel (about nq*L records in total instead of world*nq*L)."""
+    return _merge_packed(parts, off, cnt, nq, L, with_codes, False)
+
+
+def merge_packed_src_dev(parts, off, cnt, nq, L, with_codes=False):
+    """merge_packed_dev, which also returns ``src_rec`` int64 [nq, L]: the index in `parts` (flattened to records) of every result's
+    record, -1 in the padding (cis_merge_packed_src_dev) -- the way from a merged result to what travelled beside its record, the true
+    distances of the sharded re-rank.  L <= 3072; above that a ValueError, before anything is launched."""
+    if int(L) > 3072:
+        raise ValueError("the merge that reports its records holds at most 3072 results per query (limit = %d)" % int(L))
+    return _merge_packed(parts, off, cnt, nq, L, with_codes, True)
+
+
+def _merge_packed(parts, off, cnt, nq, L, with_codes, src):
     import torch
     if parts.dim() == 2:  # one flat record buffer [n, 4], off holds absolute record offsets (the routed search's return trip)
         world, stride = int(off.shape[0]), 0
@@ -660,11 +673,15 @@ def merge_packed_dev(parts, off, cnt, nq, L, with_codes=False):
     if with_codes:
         out["cells"] = torch.empty((nq, L), dtype=torch.int32, device=dev)
         out["pos"] = torch.empty((nq, L), dtype=torch.int32, device=dev)
-    _lib.check(_lib.lib().cis_merge_packed_dev(parts.data_ptr(), world, stride, off.data_ptr(), cnt.data_ptr(), nq, L,
-                                               out["ids"].data_ptr(), out["dists"].data_ptr(), out["n_found"].data_ptr(),
-                                               out["cells"].data_ptr() if with_codes else None,
-                                               out["pos"].data_ptr() if with_codes else None,
-                                               torch.cuda.current_stream(dev).cuda_stream))
+    args = (parts.data_ptr(), world, stride, off.data_ptr(), cnt.data_ptr(), nq, L,
+            out["ids"].data_ptr(), out["dists"].data_ptr(), out["n_found"].data_ptr(),
+            out["cells"].data_ptr() if with_codes else None, out["pos"].data_ptr() if with_codes else None)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    if src:
+        out["src_rec"] = torch.empty((nq, L), dtype=torch.int64, device=dev)
+        _lib.check(_lib.lib().cis_merge_packed_src_dev(*(args + (out["src_rec"].data_ptr(), stream))))
+    else:
+        _lib.check(_lib.lib().cis_merge_packed_dev(*(args + (stream,))))
     return out
 
 

@@ -379,6 +379,33 @@ class FeatureStore(object):
             torch.cuda.current_stream(dev).cuda_stream))
         return out
 
+    def distances_packed_dev(self, q, recs, off, cnt, rerank_nb):
+        """The sharded re-rank, on the rank that owns the hits (cis_rerank_packed_dev): recs int64 [n, 4] are cis_hit records, list
+        i is recs[off[i] : off[i] + cnt[i]] and belongs to query row q[i] (the packed layout of search_partial_packed_dev, or a
+        dense [rows, L] answer with off = row * L).  Returns float64 [n], parallel to recs: the distance of `rerank` for the first
+        `rerank_nb` records of every list whose id is stored here, NaN for the others.  Entries outside every list are left as
+        they were allocated.  No synchronise.  rerank_nb > 1024 is a ValueError."""
+        import torch
+        if not (q.is_cuda and q.is_contiguous() and q.dim() == 2 and q.dtype == self.dtype and q.shape[1] == self.D):
+            raise ValueError("q must be a contiguous [nq, D] tensor on the GPU with the features' dtype and width")
+        nq = int(q.shape[0])
+        if not (torch.is_tensor(recs) and recs.is_cuda and recs.is_contiguous() and recs.dtype == torch.int64 and recs.dim() == 2
+                and recs.shape[1] == 4):
+            raise ValueError("recs must be a contiguous int64 [n, 4] tensor on the GPU")
+        for t, dt, what in ((off, torch.int64, "off"), (cnt, torch.int32, "cnt")):
+            if not (torch.is_tensor(t) and t.is_cuda and t.is_contiguous() and t.dtype == dt and tuple(t.shape) == (nq,)):
+                raise ValueError("%s must be a contiguous %s [nq] tensor on the GPU" % (what, str(dt).split(".")[-1]))
+        nb = int(rerank_nb)
+        if nb < 0 or nb > 1024:
+            raise ValueError("rerank_nb must be in [0, 1024] on the device (rerank_nb = %d)" % nb)
+        n_rec = int(recs.shape[0])
+        true_d = torch.empty(n_rec, dtype=torch.float64, device=q.device)
+        feats, _, keys, rows, cap, n = self._view()
+        _lib.check(_lib.lib().cis_rerank_packed_dev(feats, self._code, n, self.D, keys, rows, cap, q.data_ptr(), nq, recs.data_ptr(),
+                                                    n_rec, off.data_ptr(), cnt.data_ptr(), nb, true_d.data_ptr(),
+                                                    torch.cuda.current_stream(q.device).cuda_stream))
+        return true_d
+
     def search_exact(self, q, k):
         """ResidentFeatures.search_exact over the rows [0, len): (ids, dists) [nq, k] numpy arrays ranked by (distance, row), ids
         mapped through the store's id column (-1 / NaN padded).  After a removal the rows are not in insertion order: that is
@@ -398,3 +425,33 @@ class FeatureStore(object):
         if table.shape[0] == 0:
             return np.full_like(rows, -1), dists
         return np.where(rows >= 0, table[np.maximum(rows, 0)], -1), dists
+
+
+def rerank_select_merged_dev(ids, adc, src_rec, true_d, rerank_nb=None, max_returned=None, near_dup_th=None):
+    """The sharded re-rank, on the home rank (cis_rerank_select_merged_dev): ids int64 / adc float64 / src_rec int64 [nq, L] from
+    lopq.search.merge_packed_src_dev, true_d float64 [n] the gathered distances of distances_packed_dev in the layout of the merged
+    records.  A result's distance is true_d[src_rec], or its ADC distance where that is NaN.  Returns rerank_dev's dict: ``ids``,
+    ``dists``, ``src`` (the place in the merged ADC list) [nq, nb] and ``n_kept`` [nq], nb = min(rerank_nb, L).  No synchronise;
+    nb > 1024 is a ValueError."""
+    import torch
+    if not (torch.is_tensor(ids) and ids.is_cuda and ids.is_contiguous() and ids.dim() == 2 and ids.dtype == torch.int64):
+        raise ValueError("ids must be a contiguous int64 [nq, L] tensor on the GPU")
+    nq, L = int(ids.shape[0]), int(ids.shape[1])
+    for t, dt, what in ((adc, torch.float64, "adc"), (src_rec, torch.int64, "src_rec")):
+        if not (torch.is_tensor(t) and t.is_cuda and t.is_contiguous() and t.dtype == dt and tuple(t.shape) == (nq, L)):
+            raise ValueError("%s must be a contiguous %s [nq, L] tensor on the GPU" % (what, str(dt).split(".")[-1]))
+    if not (torch.is_tensor(true_d) and true_d.is_cuda and true_d.is_contiguous() and true_d.dtype == torch.float64):
+        raise ValueError("true_d must be a contiguous float64 tensor on the GPU")
+    nb = L if rerank_nb is None else min(int(rerank_nb), L)
+    if nb < 0 or (max_returned or 0) < 0:
+        raise ValueError("rerank_nb and max_returned must be >= 0")
+    if nb > 1024:
+        raise ValueError("the device re-ranking holds at most 1024 results per query (nb = %d): use the host rerank" % nb)
+    dev = ids.device
+    out = {"ids": torch.empty((nq, nb), dtype=torch.int64, device=dev), "dists": torch.empty((nq, nb), dtype=torch.float64, device=dev),
+           "src": torch.empty((nq, nb), dtype=torch.int32, device=dev), "n_kept": torch.empty(nq, dtype=torch.int32, device=dev)}
+    _lib.check(_lib.lib().cis_rerank_select_merged_dev(
+        ids.data_ptr(), adc.data_ptr(), src_rec.data_ptr(), nq, L, true_d.data_ptr(), true_d.numel(), nb, int(max_returned or 0),
+        0 if near_dup_th is None else 1, 0.0 if near_dup_th is None else float(near_dup_th), out["ids"].data_ptr(),
+        out["dists"].data_ptr(), out["src"].data_ptr(), out["n_kept"].data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+    return out

@@ -287,6 +287,14 @@ int cis_merge_hits_dev(const cis_hit* d_parts, int world, int nq, int limit, int
 int cis_merge_packed_dev(const cis_hit* d_parts, int world, int64_t stride, const int64_t* d_off /* [world][nq] */,
                          const int32_t* d_cnt /* [world][nq] */, int nq, int limit, int64_t* d_ids, double* d_dists,
                          int32_t* d_n_found, int32_t* d_cells /* or NULL */, uint32_t* d_pos /* or NULL */, void* stream);
+/* The same merge, which also says where each result came from: everything cis_merge_packed_dev writes, bit for bit (padding
+ * included), and d_src_rec [nq][limit] = the index in d_parts of the result's record (w * stride + d_off + place in the list; never
+ * past what arrived of a list that the fixed exchange cut), -1 in the padding.  An array that shares d_parts' layout -- the true
+ * distances of cis_rerank_packed_dev -- is read through it.  limit <= 3072 (the one-wave merge); above that CIS_EINVAL. */
+int cis_merge_packed_src_dev(const cis_hit* d_parts, int world, int64_t stride, const int64_t* d_off /* [world][nq] */,
+                             const int32_t* d_cnt /* [world][nq] */, int nq, int limit, int64_t* d_ids, double* d_dists,
+                             int32_t* d_n_found, int32_t* d_cells /* or NULL */, uint32_t* d_pos /* or NULL */, int64_t* d_src_rec,
+                             void* stream);
 
 /* Offsets of the packed exchange, on the device ("one collective per query batch" -- no host read in between):
  * d_cnt_all [world][nq] = the all-gathered per-query hit counts -> d_off [world][nq] (exclusive scan per shard), d_totals [world],
@@ -321,6 +329,27 @@ int cis_rerank_select_dev(const void* d_feats, int f_dtype, int64_t n_feats, int
                           const int64_t* d_map_rows, int64_t map_cap, const void* d_q, int nq, const int64_t* d_ids,
                           const double* d_adc, int L, int nb, int max_returned, int use_th, double near_dup_th,
                           int64_t* d_out_ids, double* d_out_dists, int32_t* d_out_src, int32_t* d_n_kept, void* stream);
+
+/* The exact re-rank of the cell-sharded index (distributed.py): the features of an item live with the rank
+ * that owns its cell, so a rank measures its OWN hits before the exchange, the distances travel beside the records, and the home
+ * rank merges by ADC (cis_merge_packed_src_dev) and ranks by true distance (cis_rerank_select_merged_dev).
+ *
+ * cis_rerank_packed_dev: list q of this rank is d_recs[d_off[q] .. + d_cnt[q]) (the packed layout of
+ * cis_index_search_partial_packed_dev, or the rows of a dense [rows][L] answer with d_off[q] = q * L), its query row d_q[q] (f_dtype,
+ * like the features: the view of a feature store or of cis_rerank_select_dev's arguments).  d_true [n_rec] is parallel to d_recs:
+ * for record i < nb of a list, the distance of cis_rerank_dev bit for bit when the record's id has a resident row, NaN when it has
+ * none (or its id is negative); NaN for the records i >= nb, which no merged top-nb can hold.  Entries outside every list are left
+ * alone, and a list that does not lie inside [0, n_rec) is skipped.  nb <= 1024.
+ *
+ * cis_rerank_select_merged_dev: d_ids / d_adc / d_src_rec [nq][L] as cis_merge_packed_src_dev wrote them, d_true [n_true] the
+ * gathered distances in d_parts' layout.  The distance of result i is d_true[d_src_rec[i]], or its ADC distance where that is NaN;
+ * keep, rank, outputs and padding are cis_rerank_select_dev's (d_out_src = the place in the merged ADC list). */
+int cis_rerank_packed_dev(const void* d_feats, int f_dtype, int64_t n_feats, int D, const int64_t* d_map_keys,
+                          const int64_t* d_map_rows, int64_t map_cap, const void* d_q, int nq, const cis_hit* d_recs, int64_t n_rec,
+                          const int64_t* d_off /* [nq] */, const int32_t* d_cnt /* [nq] */, int nb, double* d_true, void* stream);
+int cis_rerank_select_merged_dev(const int64_t* d_ids, const double* d_adc, const int64_t* d_src_rec, int nq, int L,
+                                 const double* d_true, int64_t n_true, int nb, int max_returned, int use_th, double near_dup_th,
+                                 int64_t* d_out_ids, double* d_out_dists, int32_t* d_out_src, int32_t* d_n_kept, void* stream);
 
 /* A feature store that lives in HBM and changes by kernels (csrc/feat_store.hip): the `put` and the fetch of the reference's
  * HBase feature table (hbase_indexer_minimal.py:779-831) for the exact re-rank above, addressed by the index's device ids.  The
