@@ -12,7 +12,7 @@
 //        s <= d * qinv * (1 + 2^-23)        and        d * qinv < (s + M) * (1 + 2^-22).
 //    Integer sums have no accumulation error, so the bracket is tighter than float16 and costs half the LDS bytes
 //    and half the adds of float32: entry (k, j) holds the values of FOUR queries in 8 bytes (tab[k][j][g] uint16),
-//    one ds_read_b64 serves four queries and two v_pk_add_u16 add them.
+//    one ds_read_b64 serves four queries and one 64-bit integer add sums them (no field carries: add16x4).
 //  * Every bound that leaves a wave is an exact-distance upper bound in float64 bits, as in k_adc_scan2 (wt/wl per
 //    wave, `ext` from other cells of the query via qbound[]): "at least `limit` candidates seen so far do not exceed
 //    it".  A bound B becomes the integer threshold thr = floor(B * qinv * (1 + 2^-22)) + 1; s > thr implies
@@ -34,9 +34,6 @@
 
 typedef unsigned short u16x2_t __attribute__((ext_vector_type(2)));
 
-static __device__ __forceinline__ uint32_t pk_add_u16(uint32_t a, uint32_t b) {
-    return __builtin_bit_cast(uint32_t, (u16x2_t)(__builtin_bit_cast(u16x2_t, a) + __builtin_bit_cast(u16x2_t, b)));
-}
 // per 16-bit half: max(a - b, 0)
 static __device__ __forceinline__ uint32_t pk_subsat_u16(uint32_t a, uint32_t b) {
     return __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(__builtin_bit_cast(u16x2_t, a), __builtin_bit_cast(u16x2_t, b)));
@@ -234,18 +231,20 @@ __device__ __forceinline__ void adc16_issue(const uint32_t (&D)[(M + 3) / 4], in
     for (int i = 0; i < OCT; ++i) f[i] = gather_ld<u32x2_t>(a[i]);
 }
 
-// two independent chains (queries 0-1 and 2-3), interleaved: no back-to-back dependent packed adds
+// Four 16-bit fields (one per query) added with ONE 64-bit integer add (v_lshl_add_u64) instead of two packed adds.  No field can carry
+// into its neighbour: every staged table entry is <= CAP = 65535 / M (the staging sites clamp; absent queries hold CAP itself) and a
+// candidate's sum has at most M terms, so every partial sum of a field is <= M * CAP <= 65535 and the plain add gives the bits of the packed
+// add, field for field (the static_asserts next to CAP in scan3_group and k_adc_scan4).  profiles/valu_rate_adds.txt: behind eight
+// ds_read_b64 the seven 64-bit adds cost ~6 cycles per row and SIMD over the reads alone, seven pairs of v_pk_add_u16 or v_add_u32 15 - 20.
+static __device__ __forceinline__ u32x2_t add16x4(u32x2_t a, u32x2_t b) {
+    return __builtin_bit_cast(u32x2_t, __builtin_bit_cast(uint64_t, a) + __builtin_bit_cast(uint64_t, b));
+}
 template <int OCT>
 __device__ __forceinline__ u32x2_t adc16_sum(const u32x2_t (&f)[OCT]) {
-    uint32_t a0 = f[0][0], a1 = f[0][1];
+    u32x2_t a = f[0];
 #pragma unroll
-    for (int i = 1; i < OCT; ++i) {
-        a0 = pk_add_u16(a0, f[i][0]);
-        a1 = pk_add_u16(a1, f[i][1]);
-    }
-    u32x2_t r;
-    r[0] = a0; r[1] = a1;
-    return r;
+    for (int i = 1; i < OCT; ++i) a = add16x4(a, f[i]);
+    return a;
 }
 
 static __device__ __forceinline__ void st16(uint16_t* p, uint32_t v) { *reinterpret_cast<volatile uint16_t*>(p) = (uint16_t)v; }
@@ -263,6 +262,7 @@ __device__ __forceinline__ void scan3_group(const WorkItem* __restrict__ items, 
     constexpr int nf = M / 2;
     constexpr int OCT = M >= 8 ? 8 : 4, NU = M / OCT;
     constexpr uint32_t CAP = 65535u / M;
+    static_assert(M * CAP <= 65535u, "a sum of M staged entries fits its 16-bit field: add16x4 adds four fields with one integer add");
     char* tab = smem;                                                              // [K][M][G] uint16
     uint32_t* rk_all = reinterpret_cast<uint32_t*>(smem + (size_t)K * M * G * 2);  // [G][NW][R] (s << 16 | pos)
     Scan3Shared* sh = reinterpret_cast<Scan3Shared*>(rk_all + G * NW * R);         // [G]
@@ -341,6 +341,7 @@ __device__ __forceinline__ void scan3_group(const WorkItem* __restrict__ items, 
                         qv[g] = (g < ng) ? (uint32_t)(x * qinv[g]) : CAP;  // truncation: a lower bound of x * qinv
                         qv[g] = qv[g] > CAP ? CAP : qv[g];                 // (NaN / garbage guard; never taken for finite tables)
                     }
+                    // every staged entry is <= CAP, the absent queries' (CAP itself) included: add16x4 relies on it
                     u32x2_t pk;
                     pk[0] = qv[0] | (qv[1] << 16);
                     pk[1] = qv[2] | (qv[3] << 16);
@@ -409,8 +410,7 @@ __device__ __forceinline__ void scan3_group(const WorkItem* __restrict__ items, 
                 if (o == 0) {
                     d[u] = part;
                 } else {
-                    d[u][0] = pk_add_u16(d[u][0], part[0]);
-                    d[u][1] = pk_add_u16(d[u][1], part[1]);
+                    d[u] = add16x4(d[u], part);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -627,8 +627,7 @@ __device__ __forceinline__ void scan3_group(const WorkItem* __restrict__ items, 
                 if (o == 0) {
                     d[u] = part;
                 } else {
-                    d[u][0] = pk_add_u16(d[u][0], part[0]);
-                    d[u][1] = pk_add_u16(d[u][1], part[1]);
+                    d[u] = add16x4(d[u], part);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -937,8 +936,7 @@ __device__ __forceinline__ void adc16_rows(const CodeWords<M> (&cur)[UU], const 
         if (o == 0) {
             d[u] = part;
         } else {
-            d[u][0] = pk_add_u16(d[u][0], part[0]);
-            d[u][1] = pk_add_u16(d[u][1], part[1]);
+            d[u] = add16x4(d[u], part);
         }
         __builtin_amdgcn_sched_barrier(0);
     }
@@ -1044,6 +1042,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
     static_assert(M == 4 || M == 8 || M == 16, "float4s of the half tables are dealt to the threads in rounds of 256");
     constexpr int nf = M / 2;
     constexpr uint32_t CAP = 65535u / M;
+    static_assert(M * CAP <= 65535u, "a sum of M staged entries fits its 16-bit field: add16x4 adds four fields with one integer add");
     constexpr int LCAP = LCAPT, NS = S4_NS, NRV = (LCAP + 63) / 64;
     constexpr size_t LIST_B_FULL = (size_t)G * LCAP * 4 > (size_t)G * NS * 64 * 2 ? (size_t)G * LCAP * 4 : (size_t)G * NS * 64 * 2;
     // TWO: two interleaved table copies (scan4_two above).  `lists` is then the region of the recorded positions and of the sample's bucket
@@ -1304,6 +1303,9 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                                 qv[g] = (g < ng) ? (uint32_t)(x * qinv[g]) : CAP;  // truncation: a lower bound of x * qinv
                                 qv[g] = qv[g] > CAP ? CAP : qv[g];
                             }
+                            // every staged entry is <= CAP -- on the tables' own scale by the truncation, on the saturating scale by this
+                            // clamp (far entries sit AT CAP), and the absent queries' entries are CAP itself -- so no 16-bit field of a sum
+                            // of M entries carries: add16x4 relies on it, for both table copies of the TWO form
                             u32x2_t pk;
                             pk[0] = qv[0] | (qv[1] << 16);
                             pk[1] = qv[2] | (qv[3] << 16);
@@ -1603,6 +1605,9 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                     // where the sample was -- and the ~2-3 % recorded candidates are gathered a second time afterwards (the tables are still
                     // in LDS), where the per-query split runs on 64 passing lanes per row instead of one or two.
                     uint16_t* plist = reinterpret_cast<uint16_t*>(lists) + (size_t)w * PCAP_LDS;
+                    // (The append with the cursor as a scalar byte address and a wave-uniform room test -- 4 VALU per passing row instead of 6, for
+                    // 5 more scalar instructions and 2 more branches -- gained nothing on C4 and lost 1.7 % on the short-chunk form:
+                    // profiles/scan_plain_adds_ab.txt section 4.)
                     int pcur = 0;
                     for (int iter0 = w; iter0 < nit; iter0 += NW * PF) {
 #pragma unroll
