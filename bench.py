@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Headline benchmark: LOPQ queries/sec at recall@10 on a 10M-vector index (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3            # the headline alone: index build, timed steps, recall, oracle parity
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full     # ... and every side leg named below
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -16,7 +17,7 @@ Operating point of the reference API: quota=10000, limit=100 (cufacesearch/searc
   c2  the same generator and model at 1M vectors (dlib-descriptor shape)
   c3  1M x 4096-d float32 >= 0 (post-ReLU-like), LOPQModelPCA 4096 -> 256, V=16 M=16 renorm (model fitted by the
       reference on this generator: tests/golden/c3full.npz)
-Without --config, at N = 1, the line also carries "configs": {"c2", "c3", "c5"} -- short runs of the other single-GPU
+With --full and without --config, at N = 1, the line also carries "configs": {"c2", "c3", "c5"} -- short runs of the other single-GPU
 BASELINE configurations (their own ms/step, scan roofline, parity flag against the oracle) and the C5 chain at its true
 shapes (DeepSentibank batch 256 -> L2 normalise -> PCA 4096 -> 256, V=16 M=16 encode -> insert into the resident c3 index).
 
@@ -30,7 +31,9 @@ line as "allgather", and is the headline with --no-routed or when the routed leg
 object "grid" in the same line carries the R x S layout (R query groups, each one copy of the index sharded over S GPUs;
 --cell-shards, default 2 from 4 GPUs on, whole copies at 2): its value counts every group's queries (weak in the query load).
 
-Extra objects in the JSON line: "roofline" for the ADC scan kernel (algorithmic bytes = candidates x M, time from
+Extra objects in the JSON line (at N = 1 those measured by a leg of their own -- "cpu_baseline", "cnn" / "dlib", "ingest",
+"pcie_inclusive", "single_query_quota_10000", "configs" -- are null without --full): "roofline" for the ADC scan kernel
+(algorithmic bytes = candidates x M, time from
 HIP events recorded on the launch stream inside the library; `frac` is SURVEY.md 8(d)'s accounting and can exceed 1 -- see
 `binding` for what the kernel is bound by); "cpu_baseline" = the oracle (numpy restatement of the
 reference) timed on this host on bounded samples of the same workload, rank 0 at N=1 only: `value` is the
@@ -1623,7 +1626,7 @@ def main():
                          "(200 M vectors: batch leg + exhaustive queries)")
     ap.add_argument("--c4x-oracle", action="store_true", help="c4x: also check the exhaustive query against the oracle's blocked exhaustive "
                                                               "search over all 200 M rows (tens of seconds of numpy)")
-    ap.add_argument("--no-c4x", action="store_true", help="skip the c4x sub-run of the default line")
+    ap.add_argument("--no-c4x", action="store_true", help="skip the c4x sub-run of the --full line")
     ap.add_argument("--detail-file", default=os.environ.get("CIS_BENCH_DETAIL_FILE"),
                     help="also write the full detail object (what the `#detail` line carries) to this file")
     ap.add_argument("--n", type=int, default=int(os.environ.get("CIS_BENCH_N", 0)), help="index vectors (default: the config's)")
@@ -1639,7 +1642,12 @@ def main():
     ap.add_argument("--no-routed", action="store_true", help="N > 1: skip the routed protocol (the headline is then the all-gather protocol at 8192 queries per step)")
     ap.add_argument("--pipeline", type=int, default=int(os.environ.get("CIS_BENCH_PIPELINE", 0)),
                     help="N = 1: query batches in flight at once (each through its own view of the index on its own stream; default 4, at N > 1 three partial searches per rank); 1 = one after the other")
-    ap.add_argument("--no-configs", action="store_true", help="skip the c2 / c3 / c5 sub-runs of the default line")
+    ap.add_argument("--full", action="store_true", default=os.environ.get("CIS_BENCH_FULL") == "1",
+                    help="N = 1: after the headline, also run the legs that ride along in the line (host-pointer step, single query, CPU "
+                         "baseline and the oracle parity check on 1024 queries, ingest, the c2 / c3 / c5 / c4x sub-runs, the descriptor networks); "
+                         "the --no-* switches below trim them.  Without it a single-GPU run builds the index, times the headline, measures its "
+                         "recall and checks 64 of its queries and the sampled codes against the oracle.  N > 1 runs all its legs either way")
+    ap.add_argument("--no-configs", action="store_true", help="skip the c2 / c3 / c5 sub-runs of the --full line")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-cnn", action="store_true")
     ap.add_argument("--no-pcie", action="store_true", help="skip the host-pointer leg (profiling runs)")
@@ -1738,20 +1746,22 @@ def main():
         except Exception as e:
             routed_strong = {"error": repr(e)}
             sys.stderr.write("[bench rank %d] routed leg (strong) failed: %r\n" % (rank, e))
-    pcie = pcie_leg(st, head["value"]) if solo and not args.no_pcie else None
+    pcie = pcie_leg(st, head["value"]) if solo and args.full and not args.no_pcie else None
     single = None
-    if solo:
+    if solo and args.full:
         try:
             single = single_query_leg(st)
         except Exception as e:  # a side leg must never cost the headline line
             sys.stderr.write("[bench] single-query leg failed: %r\n" % (e,))
     cpu = parity = None
     if want_oracle:
-        parity, orc = oracle_parity(st, 10.0, 256, 4.0, 1024)
-        cpu = cpu_baseline_leg(ctx, st, orc, not args.no_cnn)
+        # every run checks its timed workload against the oracle; --full spends the time that also makes a CPU baseline of it
+        parity, orc = oracle_parity(st, 10.0, 256, 4.0, 1024) if args.full else oracle_parity(st, 2.0, 8, 3.0, 64)
+        if args.full:
+            cpu = cpu_baseline_leg(ctx, st, orc, not args.no_cnn)
         del orc
     ingest = None
-    if not args.no_cnn and st.sharded is None:
+    if args.full and not args.no_cnn and st.sharded is None:
         try:
             ingest = ingest_leg(ctx, st, "sentibank" if cfg["d_in"] == 4096 else "dlib")
         except Exception as e:  # a side leg must never cost the headline line
@@ -1779,9 +1789,9 @@ def main():
                 grid = {"error": repr(e), "layout": "%d x %d" % (world // S2, S2)}
                 sys.stderr.write("[bench rank %d] grid layout failed: %r\n" % (rank, e))
 
-    # ---- the other single-GPU BASELINE configurations, short (default line only) -------------------------------------------------
+    # ---- the other single-GPU BASELINE configurations, short (--full line only) --------------------------------------------------
     configs = None
-    if solo and not explicit_config and not args.no_configs:
+    if solo and args.full and not explicit_config and not args.no_configs:
         configs = {}
         sub_steps = max(5, min(args.steps, 30))  # (10 steps behind 2 warm-up steps were mostly the ramp of the three batches in flight: C2 17.9 against 19 M q/s)
         for name in ("c2", "c3"):
@@ -1816,7 +1826,7 @@ def main():
             torch.cuda.empty_cache()
 
     cnn = dlib = None
-    if not args.no_cnn:
+    if (args.full or world > 1) and not args.no_cnn:
         try:
             cnn, dlib = cnn_legs(ctx)
         except Exception as e:  # (every rank fails alike or none does: the legs hold no data-dependent branch before their collectives)

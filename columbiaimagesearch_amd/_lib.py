@@ -201,6 +201,21 @@ def _load_hip_runtime():
     raise ImportError("no HIP runtime (libamdhip64.so) found: install ROCm or PyTorch-ROCm")
 
 
+_get_last_error = None
+
+
+def clear_hip_error():
+    """Take (and so reset) the calling thread's last HIP error: after a runtime call whose failure has been handled, so
+    that the next check of hipGetLastError does not report it.  Returns the hipError_t that was pending.  The error is
+    per thread: call this on the thread that made the failed call."""
+    global _get_last_error
+    if _get_last_error is None:
+        fn = _load_hip_runtime().hipGetLastError
+        fn.restype, fn.argtypes = ctypes.c_int, []
+        _get_last_error = fn
+    return _get_last_error()
+
+
 def lib():
     """Load libcis_hip.so once.  Raises ImportError with build instructions if it is absent."""
     global _lib

@@ -1,5 +1,6 @@
 """Host preprocessing pool that can feed the GPU: N worker processes decode and preprocess image buffers straight into
-slots of a shared, page-locked float32 ring; the parent hands whole batches of the ring to the CNN forward.
+slots of a shared float32 ring (page-locked where the machine allows it); the parent hands whole batches of the ring to
+the CNN forward.
 
 Counterpart of the reference's per-image fan-out -- DaemonBatchExtractor.run, one image per call in `nb_threads`
 processes, each with its own network (cufacesearch/cufacesearch/extractor/generic_extractor.py:49-162, spawned by
@@ -76,6 +77,12 @@ class PreprocessPool(object):
             if torch.cuda.is_available() and not os.environ.get("CIS_POOL_NO_PIN"):
                 rc = torch.cuda.cudart().cudaHostRegister(self.ring.ctypes.data, nbytes, 0)
                 self._pinned = int(rc) == 0
+                if not self._pinned:
+                    # not every machine can page-lock memory a process already has (a virtual machine may refuse it); the
+                    # batches are then copied from pageable memory.  The runtime keeps the refusal as the thread's last
+                    # error, which the next caller of hipGetLastError -- a kernel launch's check -- would take for its own.
+                    from .._lib import clear_hip_error
+                    clear_hip_error()
         except Exception:
             self._pinned = False
         ctx = mp.get_context("spawn")

@@ -3,6 +3,7 @@ preprocessing returns (host restatement of sbpycaffe_img_featurizer.py:113-134),
 import io
 
 import numpy as np
+import pytest
 
 
 class _Spec(object):
@@ -68,3 +69,32 @@ def test_table_driven_bytescale_equals_the_plain_formula():
         b = io.BytesIO()
         Image.fromarray(rs.randint(lo, hi, shape).astype(np.uint8)).save(b, format=fmt)
         np.testing.assert_array_equal(sentibank_preprocess(b.getvalue(), mu, 14, 241, 14, 241), plain(b.getvalue()))
+
+
+@pytest.mark.gpu
+def test_refused_page_lock_leaves_no_hip_error(monkeypatch):
+    """A machine may refuse to page-lock the shared ring (hipHostRegister: invalid value).  The pool then runs on the pageable ring,
+    and the refusal must not stay behind as the thread's last HIP error, where the next kernel launch's check would find it.  The
+    refusal is a real one everywhere: the stand-in registers a null range."""
+    import torch
+    from columbiaimagesearch_amd import _lib
+    from columbiaimagesearch_amd.extractor.preprocess_pool import PreprocessPool
+    rt = torch.cuda.cudart()
+    peek = _lib._load_hip_runtime().hipPeekAtLastError
+    seen = []
+
+    class Refusing(object):
+        def cudaHostRegister(self, ptr, nbytes, flags):
+            rc = rt.cudaHostRegister(0, 0, 0)
+            seen.append((int(rc), int(peek())))
+            return rc
+
+    _lib.clear_hip_error()
+    monkeypatch.setattr(torch.cuda, "cudart", lambda: Refusing())
+    pool = PreprocessPool(_Spec(), workers=1, slots=2)
+    try:
+        assert len(seen) == 1 and seen[0][0] != 0 and seen[0][1] != 0, seen   # refused, and the runtime kept the error
+        assert not pool._pinned
+        assert _lib.clear_hip_error() == 0
+    finally:
+        pool.close()

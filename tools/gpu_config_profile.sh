@@ -2,6 +2,7 @@
 # usage (GPU box, repo root): tools/gpu_config_profile.sh <tag> <config> [pmc]
 # bench line of one BASELINE config + rocprofv3 kernel stats of the same command (+ FETCH / WRITE / SQ PMC passes -> scan traffic, binding)
 tag=$1; cfg=$2; pmc=$3
+export CIS_BENCH_FULL=1   # bench.py --full: the line with its side legs (the --no-* switches below trim them)
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
 python bench.py --config $cfg --no-cnn --detail-file gpurun_out/${tag}_${cfg}_bench_detail.json > gpurun_out/${tag}_${cfg}_bench_full.log 2>&1

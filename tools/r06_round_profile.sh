@@ -1,6 +1,7 @@
 #!/bin/bash
 # usage (GPU box, repo root): tools/r06_round_profile.sh <tag> -- the round's evidence run (every file profiles/README.md lists)
 tag=$1
+export CIS_BENCH_FULL=1   # bench.py --full in every bench.py run below: the lines with their side legs
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
 timeout 1800 python -m pytest tests -q -m gpu 2>&1 | tail -3 > gpurun_out/${tag}_pytest_gpu.txt
