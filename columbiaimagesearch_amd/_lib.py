@@ -164,6 +164,10 @@ _PROTOS = {
     "cis_cnn_feat_dim": (c_int, [c_int]),
     "cis_cnn_forward": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "cis_cnn_forward_dev": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "cis_cnn_set_precision": (c_int, [c_void_p, c_int]),
+    "cis_cnn_precision": (c_int, [c_void_p]),
+    "cis_cnn_conv_dev_last_ms": (ctypes.c_float, []),
+    "cis_cnn_conv_dev": (c_int, [c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 11 + [c_void_p, c_void_p]),
     "cis_index_set_profiling": (c_int, [c_void_p, c_int]),
     "cis_index_set_scan_mode": (c_int, [c_void_p, c_int]),
     "cis_index_stream_counters": (c_int, [c_void_p, c_void_p]),

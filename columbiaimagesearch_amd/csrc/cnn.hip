@@ -19,30 +19,10 @@
 #include <thread>
 #include <vector>
 #include "common.h"
+#include "cnn_conv.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-struct ConvDesc {
-    int N, H, W, C;          // input: images, height, width, total channels
-    int OH, OW, OC;          // output
-    int KH, KW, stride, pad, groups;
-    int ICg, OCg, K;         // per group; K = KH*KW*ICg, k = (ky*KW + kx)*ICg + ic
-    int64_t sN, sC, sH, sW;  // input strides in elements (NCHW for the first layer, NHWC afterwards)
-    int relu;
-    int kx_fastest;          // K ordering of the packed weights: 0: k = (ky*KW+kx)*ICg+ic, 1: k = (ic*KH+ky)*KW+kx (NCHW input)
-    int splitk = 1;          // > 1 (groups == 1, vector path only): blockIdx.z owns a K range and writes raw partial sums
-    int64_t part_stride = 0; // elements between the partial outputs of consecutive K ranges
-    int runq = 0;            // > 0: "row-run" gather of the 3-channel first layer (vector path): K is cut per kernel row into runq
-                             // float4 of contiguous NHWC input (KW*C floats, zero-weight padded), k = ky*4*runq + (kx*C + ic)
-    const float* res = nullptr;  // residual input [npix][resC] added before the ReLU (channels >= resC get nothing): dlib add_prev
-    int resC = 0;
-    int run_planes = 0;      // > 0 (with runq): the runs are taken from the caller's NCHW planes directly -- run r = ic * KH + ky is the KW
-                             // contiguous floats of channel plane ic, row iy0 + ky, from column ix0 (runq float4, the tail meets zero
-                             // weights), k = r * 4 * runq + kx; run_planes = ICg * KH runs; in_elems = floats in the input (the last
-                             // float4 of the last run would end past it: it is loaded one to three floats earlier and shifted)
-    int64_t in_elems = 0;
-};
 
 // C[pixel][oc] = sum_k A[pixel][k] * Wp[k][oc] + bias[oc]; block tile BM x BN, 256 threads = 4 waves laid
 // out WAVES_M x WAVES_N, each wave WM x WN MFMA tiles of 32x32.  K advances 16 at a time through two LDS
@@ -986,6 +966,7 @@ struct LayerW {
     float* d_w = nullptr;  // packed [g][K][OCg]
     float* d_b = nullptr;
     float* d_w2 = nullptr; // 3x3 layers with IC == OC == C served by k_conv3x3_direct: [tap][C/2][C][2] (a k pair adjacent)
+    uint16_t* d_wh = nullptr;  // DeepSentibank under a 16-bit precision: the bf16 planes of cnn_bf16_pack (cis_cnn_set_precision)
 };
 
 // activations and split-K partial sums of one forward in flight
@@ -1031,6 +1012,8 @@ struct cis_cnn {
     uint64_t graph_clock = 0;
     hipStream_t gs = nullptr;   // capture stream
     bool graph_off = false;     // a capture failed on this handle: launches from here on
+    int precision = 0;          // CIS_CNN_F32 / CIS_CNN_BF16X3 / CIS_CNN_BF16: which kernels serve the GEMM layers (DeepSentibank)
+    int packed_lo = -1;         // what d_wh of the layers holds: -1 nothing, 0 the hi plane, 1 hi and lo
 };
 
 // dlib anet_type block plan: (in channels, out channels, down-sampling block)
@@ -1065,8 +1048,8 @@ extern "C" void cis_cnn_destroy(cis_cnn* c) {
         for (auto& l : c->fc) l = LayerW();
         c->dl.clear();
     }
-    for (auto& l : c->conv) { if (l.d_w) (void)hipFree(l.d_w); if (l.d_b) (void)hipFree(l.d_b); if (l.d_w2) (void)hipFree(l.d_w2); }
-    for (auto& l : c->fc) { if (l.d_w) (void)hipFree(l.d_w); if (l.d_b) (void)hipFree(l.d_b); }
+    for (auto& l : c->conv) { if (l.d_w) (void)hipFree(l.d_w); if (l.d_b) (void)hipFree(l.d_b); if (l.d_w2) (void)hipFree(l.d_w2); if (l.d_wh) (void)hipFree(l.d_wh); }
+    for (auto& l : c->fc) { if (l.d_w) (void)hipFree(l.d_w); if (l.d_b) (void)hipFree(l.d_b); if (l.d_wh) (void)hipFree(l.d_wh); }
     for (auto& l : c->dl) { if (l.d_w) (void)hipFree(l.d_w); if (l.d_b) (void)hipFree(l.d_b); if (l.d_w2) (void)hipFree(l.d_w2); }
     for (auto& g : c->graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
     if (c->gs) (void)hipStreamDestroy(c->gs);
@@ -1234,6 +1217,7 @@ extern "C" int cis_cnn_create_view(cis_cnn** out, cis_cnn* base) {
     for (int i = 0; i < 5; ++i) c->conv[i] = root->conv[i];
     for (int i = 0; i < 2; ++i) c->fc[i] = root->fc[i];
     c->dl = root->dl;
+    c->precision = root->precision;  // a view runs in the precision its base has now, on the base's packed weights
     c->base = root;
     c->parts_override = 1;
     {
@@ -1393,6 +1377,154 @@ static int conv_fill_chip(CnnWs* ws, ConvDesc d, const float* in, const LayerW& 
     hipLaunchKernelGGL(k_splitk_reduce, dim3((unsigned)ceil_div(n4, 256)), dim3(256), 0, st, part, splitk, dp.part_stride, b, out, n4, d.OC,
                        d.relu, d.res, d.resC);
     return CIS_OK;
+}
+
+
+// ---- precisions of the DeepSentibank GEMM layers (cnn_bf16.hip) ----
+static int conv_by_precision(const cis_cnn* c, const LayerW& L, const ConvDesc& d, const float* in, const float* w32, const float* b, float* out,
+                             hipStream_t st) {
+    if (c->precision == CIS_CNN_F32) { launch_conv(d, in, w32, b, out, st); return CIS_OK; }
+    return launch_conv_bf16(d, in, L.d_wh, b, out, c->precision == CIS_CNN_BF16X3 ? 3 : 1, st);
+}
+
+extern "C" int cis_cnn_precision(const cis_cnn* c) { return c ? c->precision : CIS_EINVAL; }
+
+extern "C" int cis_cnn_set_precision(cis_cnn* c, int precision) {
+    CIS_REQUIRE(c != nullptr, "cnn is NULL");
+    CIS_REQUIRE(!c->orphaned, "this view's base was destroyed: close views before their base");
+    CIS_REQUIRE(precision == CIS_CNN_F32 || precision == CIS_CNN_BF16X3 || precision == CIS_CNN_BF16, "precision %d: CIS_CNN_F32 (0), CIS_CNN_BF16X3 (1) or CIS_CNN_BF16 (2)", precision);
+    CIS_REQUIRE(c->base == nullptr, "a view runs in its base's precision: set it on the base, before the view is made");
+    CIS_REQUIRE(c->arch == 1 || precision == CIS_CNN_F32, "the 16-bit precisions are built for DeepSentibank (CIS_CNN_SENTIBANK) only");
+    {
+        std::lock_guard<std::mutex> lk(g_cnn_views_mu);
+        CIS_REQUIRE(c->views.empty() || precision == c->precision, "this handle has views on its weights: set the precision before making views");
+    }
+    const int want_lo = precision == CIS_CNN_BF16X3 ? 1 : 0;
+    if (precision != CIS_CNN_F32 && c->packed_lo != want_lo) {
+        // the float32 weights are already K-major on the device ([g][K][OCg], the first layer in its plane-run order): read them back,
+        // split and pack on the host.  Once per selection, not per forward.
+        CIS_CHECK_HIP(hipSetDevice(c->device));
+        CIS_CHECK_HIP(hipDeviceSynchronize());  // no forward of this handle reads the planes that are replaced
+        struct Item { LayerW* L; const float* src; int g, K, OCg; };
+        std::vector<Item> items;
+        int C = 3;
+        for (int l = 0; l < 5; ++l) {
+            const int OC = kConvCfg[l][0], k = kConvCfg[l][1], g = kConvCfg[l][4];
+            if (l == 0) items.push_back({&c->conv[0], c->conv[0].d_w2, 1, C * k * ((k + 3) / 4) * 4, OC});
+            else items.push_back({&c->conv[l], c->conv[l].d_w, g, k * k * (C / g), OC / g});
+            C = OC;
+        }
+        items.push_back({&c->fc[0], c->fc[0].d_w, 1, 9216, 4096});
+        items.push_back({&c->fc[1], c->fc[1].d_w, 1, 4096, 4096});
+        c->packed_lo = -1;
+        std::vector<float> host;
+        for (auto& it : items) {
+            if (it.L->d_wh) { (void)hipFree(it.L->d_wh); it.L->d_wh = nullptr; }
+            host.resize((size_t)it.g * it.K * it.OCg);
+            CIS_CHECK_HIP(hipMemcpy(host.data(), it.src, host.size() * sizeof(float), hipMemcpyDeviceToHost));
+            CIS_TRY(cnn_bf16_pack(&it.L->d_wh, host.data(), it.g, it.K, it.OCg, want_lo));
+        }
+        c->packed_lo = want_lo;
+    }
+    c->precision = precision;
+    return CIS_OK;
+}
+
+// One convolution layer on device buffers, in any precision: for tests and per-layer timing, NOT a fast path -- the OIHW weights (HOST
+// arrays, like the tensors of cis_cnn_create) are packed and uploaded by every call, and the call waits for the device before it returns.
+// in_nchw = 0: d_in is [N][H][W][C]; 1: [N][C][H][W] (the first-layer route: pad must be 0).  d_out is [N][OH][OW][OC].
+// A 1 x 1 layer over a 1 x 1 image (the fc form) runs with the forward's K split of 8 and k_splitk_reduce when K allows.
+static thread_local float g_conv_dev_ms = -1.f;
+extern "C" float cis_cnn_conv_dev_last_ms(void) { return g_conv_dev_ms; }
+
+extern "C" int cis_cnn_conv_dev(const float* d_in, int in_nchw, const float* w, const float* bias, int N, int H, int W, int C, int OC, int k,
+                                int stride, int pad, int groups, int relu, int precision, float* d_out, void* stream) {
+    CIS_REQUIRE(d_in && w && d_out, "NULL buffer");
+    CIS_REQUIRE(N >= 1 && H >= 1 && W >= 1 && C >= 1 && OC >= 1 && k >= 1 && stride >= 1 && pad >= 0 && groups >= 1, "bad shape");
+    CIS_REQUIRE(C % groups == 0 && OC % groups == 0, "groups must divide C and OC");
+    CIS_REQUIRE(H + 2 * pad >= k && W + 2 * pad >= k, "the kernel is larger than the padded input");
+    CIS_REQUIRE(precision == CIS_CNN_F32 || precision == CIS_CNN_BF16X3 || precision == CIS_CNN_BF16, "precision %d: CIS_CNN_F32 (0), CIS_CNN_BF16X3 (1) or CIS_CNN_BF16 (2)", precision);
+    CIS_REQUIRE(!in_nchw || (pad == 0 && groups == 1), "NCHW input: the first-layer route needs pad == 0 and groups == 1");
+    CIS_REQUIRE(precision != CIS_CNN_F32 || (OC / groups) % 4 == 0, "float32: the packed weights are read as float4 rows, OC / groups must be a multiple of 4");
+    CIS_REQUIRE((int64_t)N * H * W * C < (1ll << 31) && (int64_t)OC * (C / groups) * k * k < (1ll << 31), "layer too large");
+    CIS_TRY(cis_lazy_init());
+    hipStream_t st = (hipStream_t)stream;
+    ConvDesc d;
+    d.N = N; d.H = H; d.W = W; d.C = C; d.OC = OC; d.KH = d.KW = k; d.stride = stride; d.pad = pad; d.groups = groups;
+    d.OH = (H + 2 * pad - k) / stride + 1;
+    d.OW = (W + 2 * pad - k) / stride + 1;
+    d.ICg = C / groups; d.OCg = OC / groups; d.K = k * k * d.ICg;
+    d.relu = relu; d.kx_fastest = 0;
+    const int64_t npix = (int64_t)N * d.OH * d.OW;
+    const int ICg = d.ICg, OCg = d.OCg;
+    // the plane-run gather of the float32 kernel is built for its 128 x 96 tile; other NCHW shapes take its scalar gather
+    const bool runs = in_nchw && (precision != CIS_CNN_F32 || (OCg > 64 && OCg % 96 == 0 && OCg % 128 != 0 && npix > 2048));
+    const int RW = ((k + 3) / 4) * 4;
+    if (in_nchw) {
+        d.sN = (int64_t)C * H * W; d.sC = (int64_t)H * W; d.sH = W; d.sW = 1;
+        if (runs) { d.runq = RW / 4; d.run_planes = C * k; d.K = d.run_planes * RW; d.in_elems = (int64_t)N * C * H * W; }
+        else d.kx_fastest = 1;
+    } else {
+        d.sN = (int64_t)H * W * C; d.sC = 1; d.sH = (int64_t)W * C; d.sW = C;
+    }
+    std::vector<float> km((size_t)groups * d.K * OCg, 0.f);  // K-major, the order of k as the gather produces it
+    for (int o = 0; o < OC; ++o)
+        for (int ic = 0; ic < ICg; ++ic)
+            for (int ky = 0; ky < k; ++ky)
+                for (int kx = 0; kx < k; ++kx) {
+                    const int kk = runs ? (ic * k + ky) * RW + kx : (in_nchw ? (ic * k + ky) * k + kx : (ky * k + kx) * ICg + ic);
+                    km[((size_t)(o / OCg) * d.K + kk) * OCg + o % OCg] = w[(((size_t)o * ICg + ic) * k + ky) * k + kx];
+                }
+    DevBuf wbuf, bbuf, part;
+    uint16_t* d_wh = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    g_conv_dev_ms = -1.f;
+    auto done = [&](int rc) {
+        (void)hipStreamSynchronize(st);
+        if (rc == CIS_OK && ev[0] && ev[1]) (void)hipEventElapsedTime(&g_conv_dev_ms, ev[0], ev[1]);
+        for (auto& e : ev) if (e) (void)hipEventDestroy(e);
+        if (d_wh) (void)hipFree(d_wh);
+        wbuf.release(); bbuf.release(); part.release();
+        return rc;
+    };
+    if (bias) {
+        int rc = bbuf.reserve((size_t)OC * sizeof(float));
+        if (rc != CIS_OK) return done(rc);
+        if (hipMemcpy(bbuf.p, bias, (size_t)OC * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { cis_set_error("bias upload failed"); return done(CIS_EHIP); }
+    }
+    const float* d_b = bias ? bbuf.as<float>() : nullptr;
+    const int kstage = precision == CIS_CNN_F32 ? 16 : 32;
+    const bool fc_form = npix <= 2048 && d.OH * d.OW == 1 && k == 1 && groups == 1 && !in_nchw && OC % 4 == 0 && OCg > 32 && d.K % kstage == 0 && d.K / kstage >= 8;
+    if (fc_form) {
+        d.splitk = 8;
+        d.part_stride = npix * OC;
+        int rc = part.reserve((size_t)d.splitk * npix * OC * sizeof(float));
+        if (rc != CIS_OK) return done(rc);
+    }
+    float* o = fc_form ? part.as<float>() : d_out;
+    const float* b_conv = fc_form ? nullptr : d_b;
+    if (precision == CIS_CNN_F32) {
+        int rc = wbuf.reserve(km.size() * sizeof(float));
+        if (rc != CIS_OK) return done(rc);
+        if (hipMemcpy(wbuf.p, km.data(), km.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { cis_set_error("weight upload failed"); return done(CIS_EHIP); }
+        if (hipEventCreate(&ev[0]) == hipSuccess) (void)hipEventRecord(ev[0], st);
+        launch_conv(d, d_in, wbuf.as<float>(), b_conv, o, st);
+    } else {
+        if (!in_nchw && ICg % 8 != 0) { cis_set_error("16-bit convolution: channels-last input needs a multiple of 8 channels per group (got %d)", ICg); return done(CIS_EINVAL); }
+        int rc = cnn_bf16_pack(&d_wh, km.data(), groups, d.K, OCg, precision == CIS_CNN_BF16X3);
+        if (rc == CIS_OK && hipEventCreate(&ev[0]) == hipSuccess) (void)hipEventRecord(ev[0], st);
+        if (rc == CIS_OK) rc = launch_conv_bf16(d, d_in, d_wh, b_conv, o, precision == CIS_CNN_BF16X3 ? 3 : 1, st);
+        if (rc != CIS_OK) return done(rc);
+    }
+    if (fc_form) {
+        const int64_t n4 = npix * OC / 4;
+        hipLaunchKernelGGL(k_splitk_reduce, dim3((unsigned)ceil_div(n4, 256)), dim3(256), 0, st, part.as<float>(), d.splitk, d.part_stride, d_b, d_out, n4, OC,
+                           relu, (const float*)nullptr, 0);
+    }
+    if (hipEventCreate(&ev[1]) == hipSuccess) (void)hipEventRecord(ev[1], st);
+    if (hipGetLastError() != hipSuccess) { cis_set_error("convolution launch failed"); return done(CIS_EHIP); }
+    if (hipStreamSynchronize(st) != hipSuccess) { cis_set_error("convolution failed on the device"); return done(CIS_EHIP); }
+    return done(CIS_OK);
 }
 
 // Test hook (tests/test_cnn_hip_parity.py): CIS_CNN_POISON=<mask> fills the workspaces (bit 0..4: act0, act1, act2, act3, part) with
@@ -1724,7 +1856,7 @@ static int cnn_forward_sentibank(cis_cnn* c, CnnWs* ws, const float* d_nchw, int
         d.kx_fastest = 0;
         float* o = bufs[which];
         const float* wl = c->conv[l].d_w;
-        if (l == 0 && !getenv("CIS_CNN_NHWC_FIRST")) {
+        if (l == 0 && (c->precision != CIS_CNN_F32 || !getenv("CIS_CNN_NHWC_FIRST"))) {
             // first layer straight from the caller's NCHW planes (round 5): a (pixel, channel, kernel row) is a run of 11 contiguous
             // floats, gathered as three 16-byte loads (4-byte aligned: the planes' rows are 227 floats); the re-layout pass below
             // (57 us per 256 images, a 158 MB round trip) is gone.  K = 3 * 11 * 12 = 396 as before.
@@ -1746,7 +1878,7 @@ static int cnn_forward_sentibank(cis_cnn* c, CnnWs* ws, const float* d_nchw, int
             d.K = d.KH * d.runq * 4;            // 396
             cur = xt;
         }
-        launch_conv(d, cur, wl, c->conv[l].d_b, o, st);
+        CIS_TRY(conv_by_precision(c, c->conv[l], d, cur, wl, c->conv[l].d_b, o, st));
         cur = o; which ^= 1; nchw = false;
         H = d.OH; W = d.OW; C = d.OC;
         if (kPoolAfter[l] && kLrnAfter[l]) {
@@ -1796,12 +1928,12 @@ static int cnn_forward_sentibank(cis_cnn* c, CnnWs* ws, const float* d_nchw, int
             d.splitk = splitk;
             d.part_stride = (int64_t)n * 4096;
             float* part = ws->act2.as<float>();
-            launch_conv(d, cur, c->fc[l].d_w, nullptr, part, st);
+            CIS_TRY(conv_by_precision(c, c->fc[l], d, cur, c->fc[l].d_w, nullptr, part, st));
             const int64_t n4 = (int64_t)n * 4096 / 4;
             hipLaunchKernelGGL(k_splitk_reduce, dim3((unsigned)ceil_div(n4, 256)), dim3(256), 0, st, part, splitk, d.part_stride,
                                c->fc[l].d_b, o, n4, 4096, 1, (const float*)nullptr, 0);
         } else {
-            launch_conv(d, cur, c->fc[l].d_w, c->fc[l].d_b, o, st);
+            CIS_TRY(conv_by_precision(c, c->fc[l], d, cur, c->fc[l].d_w, c->fc[l].d_b, o, st));
         }
         cur = o; which ^= 1; fin = 4096;
     }

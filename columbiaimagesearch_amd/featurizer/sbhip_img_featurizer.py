@@ -21,6 +21,38 @@ from .generic_featurizer import GenericFeaturizer
 TENSOR_NAMES = ["conv1", "conv2", "conv3", "conv4", "conv5", "fc6", "fc7"]
 INPUT_HW = 227
 FEAT_DIM = 4096
+# arithmetic of the GEMM layers (cis_cnn_set_precision): name -> CIS_CNN_F32 / CIS_CNN_BF16X3 / CIS_CNN_BF16
+PRECISIONS = {"f32": 0, "bf16x3": 1, "bf16": 2}
+
+
+def _precision_code(precision):
+    if precision not in PRECISIONS:
+        raise ValueError("unknown precision %r: one of %s" % (precision, ", ".join(sorted(PRECISIONS))))
+    return PRECISIONS[precision]
+
+
+def conv2d_dev(x, w, b, stride=1, pad=0, groups=1, relu=False, precision="f32", nchw=False):
+    """One convolution layer through cis_cnn_conv_dev, for tests and per-layer timing (not a fast path: the weights are packed per call).
+    x: contiguous float32 CUDA tensor, [N,H,W,C] (or [N,C,H,W] with nchw=True: the first-layer route, pad 0, groups 1); w: OIHW float32
+    [OC, C/groups, k, k] and b: [OC] or None, host arrays -> CUDA tensor [N,OH,OW,OC].  The call returns when the layer has run."""
+    import torch
+    if not (x.is_cuda and x.is_contiguous() and x.dtype == torch.float32 and x.dim() == 4):
+        raise ValueError("x must be a contiguous 4-d float32 tensor on the GPU")
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    N, H, W, C = (x.shape[0], x.shape[2], x.shape[3], x.shape[1]) if nchw else tuple(x.shape)
+    if w.ndim != 4 or w.shape[2] != w.shape[3] or w.shape[1] * groups != C:
+        raise ValueError("w must be [OC, C/groups, k, k], got %r for C = %d, groups = %d" % (w.shape, C, groups))
+    OC, k = w.shape[0], w.shape[2]
+    if b is not None:
+        b = np.ascontiguousarray(b, dtype=np.float32)
+        if b.shape != (OC,):
+            raise ValueError("b must be [OC]")
+    OH, OW = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    out = torch.empty((N, max(OH, 0), max(OW, 0), OC), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().cis_cnn_conv_dev(x.data_ptr(), int(bool(nchw)), _lib.ptr(w), _lib.ptr(b) if b is not None else None, N, H, W, C, OC, k,
+                                           stride, pad, groups, int(bool(relu)), _precision_code(precision), out.data_ptr(),
+                                           torch.cuda.current_stream(x.device).cuda_stream))
+    return out
 
 
 def bytescale(data, low=0, high=255, cmin=None, cmax=None):
@@ -77,7 +109,8 @@ def sentibank_preprocess(img_buffer, mu, w_boff, w_eoff, h_boff, h_eoff, target_
 class SentiBankNet(object):
     """The network alone: float32 NCHW batch in, fc7 (post-ReLU) out.  Owns a cis_cnn handle."""
 
-    def __init__(self, weights):
+    def __init__(self, weights, precision="f32"):
+        code = _precision_code(precision)
         arrs = []
         for n in TENSOR_NAMES:
             arrs.append(np.ascontiguousarray(weights[n + "_w"], dtype=np.float32))
@@ -86,6 +119,14 @@ class SentiBankNet(object):
         out = _lib.c_void_p()
         _lib.check(_lib.lib().cis_cnn_create(_lib.ctypes.byref(out), 1, ptrs, len(arrs)))
         self._h = out.value
+        if code:
+            _lib.check(_lib.lib().cis_cnn_set_precision(self._h, code))
+
+    @property
+    def precision(self):
+        """"f32", "bf16x3" or "bf16": the arithmetic of the convolutions and fc layers (a view reports its base's)"""
+        code = _lib.lib().cis_cnn_precision(self._h)
+        return [k for k, v in PRECISIONS.items() if v == code][0]
 
     def view(self):
         """A second handle on the same weights with its own workspaces and streams (cis_cnn_create_view): run consecutive batches
@@ -150,7 +191,7 @@ class SentiBankHIPImgFeaturizer(GenericFeaturizer):
         self.w_boff = self.h_boff = off
         self.w_eoff = self.h_eoff = off + INPUT_HW
         self.mu = np.ascontiguousarray(imgmean[:, off:off + INPUT_HW, off:off + INPUT_HW], dtype=np.float32)
-        self.net = SentiBankNet(self._load_weights(self.sbcaffe_path))
+        self.net = SentiBankNet(self._load_weights(self.sbcaffe_path), precision=str(self.get_param("precision", "f32")))
 
     @staticmethod
     def _load_weights(path):

@@ -596,6 +596,30 @@ int cis_cnn_forward_dev(cis_cnn* c, const float* d_nchw, int n, float* d_feats, 
  * fill each other's workgroup rounds: consecutive forwards are in different layers at any time.  From the first view on, base and views
  * run a batch as ONE chain (the two-part forward of the dlib net is for a single handle).  Destroy with cis_cnn_destroy. */
 int cis_cnn_create_view(cis_cnn** out, cis_cnn* base);
+/* Arithmetic of the GEMM layers (convolutions, fc) of DeepSentibank.  CIS_CNN_F32, the default: float32 matrix instructions, the bits
+ * every earlier version gave.  CIS_CNN_BF16X3: every float32 operand is split as hi = bf16(x), lo = bf16(x - hi) and every product is
+ * a_hi*b_hi + a_hi*b_lo + a_lo*b_hi on the 16-bit matrix instructions, float32 accumulation (relative error of a product <= 3 * 2^-16).
+ * CIS_CNN_BF16: a_hi*b_hi alone (<= 2^-7).  Activations stay float32 between layers in every precision.  Descriptors of different
+ * precisions are different descriptors: build and query an index with one.
+ * cis_cnn_set_precision packs the 16-bit weights when a precision is first selected (seconds, on the host).  On a base handle only, and
+ * before views are made: a view takes the precision its base has when the view is created, and CIS_EINVAL on a view, on a handle
+ * that has views (unless nothing changes), on the dlib network for anything but CIS_CNN_F32, and for an unknown value. */
+#define CIS_CNN_F32 0
+#define CIS_CNN_BF16X3 1
+#define CIS_CNN_BF16 2
+int cis_cnn_set_precision(cis_cnn* c, int precision);
+int cis_cnn_precision(const cis_cnn* c);
+/* One convolution layer on device buffers, for tests and per-layer timing: NOT a fast path (the weights are packed and uploaded by
+ * every call, and the call returns after the device has finished).  d_in: float32 on the device, [N][H][W][C] (in_nchw = 0) or
+ * [N][C][H][W] (in_nchw = 1: the first-layer route, pad == 0 and groups == 1).  w: OIHW float32 [OC][C / groups][k][k] and bias [OC]
+ * (or NULL) in HOST memory.  d_out: [N][OH][OW][OC] float32 on the device.  precision = CIS_CNN_F32 runs the float32 kernels of the
+ * forward; the 16-bit precisions need C / groups % 8 == 0 on channels-last input.  A 1 x 1 layer over a 1 x 1 image with K >= 256
+ * runs with the K split of the fc layers. */
+int cis_cnn_conv_dev(const float* d_in, int in_nchw, const float* w, const float* bias, int N, int H, int W, int C, int OC, int k,
+                     int stride, int pad, int groups, int relu, int precision, float* d_out, void* stream);
+/* Device time in milliseconds of the layer's launches (the convolution, and the split-K reduction where there is one) in this thread's
+ * last successful cis_cnn_conv_dev, between two events on its stream; -1 before the first call and after a failed one. */
+float cis_cnn_conv_dev_last_ms(void);
 
 /* ---- aligned face chips: the image side of dlib's compute_face_descriptor(img, shape) -------------------------------------
  * (cufacesearch/cufacesearch/featurizer/dlib_featurizer.py:103-105).  The caller supplies the 68 landmarks (the shape predictor is

@@ -1,21 +1,142 @@
-"""Time the DeepSentibank forward at batch 256 on the GPU (descriptors/s, MFMA utilisation vs the f32 peak)."""
-import os, sys, time
+"""Time the DeepSentibank forward at batch 256 on the GPU in the precisions of the network (f32, bf16x3, bf16).
+
+  python tools/bench_cnn.py [BATCH] [--precision P ...] [--layers] [--deviation] [--out profiles/cnn_precision.json]
+
+Every figure is a median of repetitions that add up to >= 0.5 s, timed with device events, three runs of each so that the spread
+is on record.  Reported per precision: one batch at a time; four batches in flight (the net and three views on
+streams.lane_streams, all precisions in this one process, so the float32 forward beside them is the yardstick); with --layers
+the seven GEMM layers one by one through cis_cnn_conv_dev (device time of the layer's launches as the library measures it: the
+call itself packs weights, so each figure is the median of 7 single launches, NOT of half a second of them); with --deviation
+how far the descriptors move: |f_p - f_f32| / max|f_f32| on synthetic weights and images, and the share of LOPQ codes of the
+c3full golden model that change.  "of peak" is useful work (2 * MACs) over the stated peak: 157.3 TFLOP/s for the float32 matrix
+instructions, 2516.6 TFLOP/s (the vendor's dense bf16 figure) for both 16-bit precisions, although bf16x3 issues three products.
+"""
+import argparse, ctypes, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
-from columbiaimagesearch_amd.featurizer.synthetic import sentibank_weights
-from columbiaimagesearch_amd.featurizer import SentiBankNet
-B = int(sys.argv[1]) if len(sys.argv) > 1 else 256
-net = SentiBankNet(sentibank_weights(0))
-x = (torch.randn(B, 3, 227, 227, device="cuda") * 50).contiguous()
-out = torch.empty(B, 4096, device="cuda")
-for _ in range(2):
-    net.forward_dev(x, out)
-torch.cuda.synchronize()
-K = 5
-t = time.perf_counter()
-for _ in range(K):
-    net.forward_dev(x, out)
-torch.cuda.synchronize()
-dt = (time.perf_counter() - t) / K
-flops = 2.0 * 720310816 * B
-print("batch %d: %.3f ms  %.0f descriptors/s  %.1f TFLOP/s  MFMA(f32) util %.3f" % (B, dt * 1e3, B / dt, flops / dt / 1e12, flops / dt / 157.3e12))
+from columbiaimagesearch_amd import _lib
+from columbiaimagesearch_amd.featurizer import SentiBankNet, conv2d_dev
+from columbiaimagesearch_amd.featurizer.synthetic import sentibank_images, sentibank_weights
+from columbiaimagesearch_amd.streams import lane_streams
+
+MACS = 720310816
+PEAK = {"f32": 157.3e12, "bf16x3": 2516.6e12, "bf16": 2516.6e12}
+#          name    H    C     OC    k  s  p  g  nchw
+LAYERS = [("conv1", 227, 3, 96, 11, 4, 0, 1, True), ("conv2", 27, 96, 256, 5, 1, 2, 2, False), ("conv3", 13, 256, 384, 3, 1, 1, 1, False),
+          ("conv4", 13, 384, 384, 3, 1, 1, 2, False), ("conv5", 13, 384, 256, 3, 1, 1, 2, False), ("fc6", 1, 9216, 4096, 1, 1, 0, 1, False),
+          ("fc7", 1, 4096, 4096, 1, 1, 0, 1, False)]
+
+
+def median_ms(step, warmup=3, total=0.5):
+    """step(): enqueue one repetition between the two events it returns"""
+    for _ in range(warmup):
+        step()
+    torch.cuda.synchronize()
+    times = []
+    while sum(times) < total * 1e3 or len(times) < 5:
+        e0, e1 = step()
+        e1.synchronize()
+        times.append(e0.elapsed_time(e1))
+    return float(np.median(times))
+
+
+def one_at_a_time(net, x, out):
+    def step():
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        net.forward_dev(x, out)
+        e1.record()
+        return e0, e1
+    return median_ms(step)
+
+
+def four_in_flight(nets, xs, outs, lanes):
+    main = torch.cuda.current_stream()
+
+    def step():
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(main)
+        for net, x, out, s in zip(nets, xs, outs, lanes):
+            s.wait_stream(main)
+            with torch.cuda.stream(s):
+                net.forward_dev(x, out)
+        for s in lanes:
+            main.wait_stream(s)
+        e1.record(main)
+        return e0, e1
+    return median_ms(step) / len(nets)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("batch", nargs="?", type=int, default=256)
+    ap.add_argument("--precision", action="append", choices=sorted(PEAK))
+    ap.add_argument("--layers", action="store_true")
+    ap.add_argument("--deviation", action="store_true")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    B, precs = a.batch, a.precision or ["f32", "bf16x3", "bf16"]
+    w = sentibank_weights(0)
+    res = {"batch": B, "forward": {}, "layers": {}, "deviation": {}}
+    nets = {p: SentiBankNet(w, precision=p) for p in precs}
+    x = (torch.randn(B, 3, 227, 227, device="cuda") * 50).contiguous()
+    out = torch.empty(B, 4096, device="cuda")
+    for run in range(3):   # the precisions alternate inside a run
+        for p in precs:
+            res["forward"].setdefault(p, {"one_ms": [], "four_ms": []})["one_ms"].append(one_at_a_time(nets[p], x, out))
+    lanes = lane_streams(4)
+    xs, outs = [x] + [x.clone() for _ in range(3)], [out] + [torch.empty_like(out) for _ in range(3)]
+    groups = {p: [nets[p]] + [nets[p].view() for _ in range(3)] for p in precs}
+    for run in range(3):
+        for p in precs:
+            res["forward"][p]["four_ms"].append(four_in_flight(groups[p], xs, outs, lanes))
+    for p in precs:
+        f = res["forward"][p]
+        for key in ("one_ms", "four_ms"):
+            ms = float(np.median(f[key]))
+            f[key[:-3] + "_of_peak"] = 2.0 * MACS * B / (ms * 1e-3) / PEAK[p]
+            print("%-7s batch %d, %-4s: %.3f ms per batch (runs %s)  %.0f descriptors/s  %.3f of the %s peak" % (
+                p, B, key[:-3], ms, " ".join("%.3f" % t for t in f[key]), B / ms * 1e3, f[key[:-3] + "_of_peak"], "f32" if p == "f32" else "bf16"))
+    if a.layers:
+        L = _lib.lib()
+        L.cis_cnn_conv_dev_last_ms.restype = ctypes.c_float
+        rs = np.random.RandomState(0)
+        for name, H, C, OC, k, s, pad, g, nchw in LAYERS:
+            xin = torch.randn((B, C, H, H) if nchw else (B, H, H, C), device="cuda")
+            wl = (rs.randn(OC, C // g, k, k) / np.sqrt(C // g * k * k)).astype(np.float32)
+            bl = np.zeros(OC, dtype=np.float32)
+            oh = (H + 2 * pad - k) // s + 1
+            macs = B * oh * oh * OC * (C // g) * k * k
+            for p in precs:
+                t = []
+                for _ in range(8):
+                    conv2d_dev(xin, wl, bl, s, pad, g, True, p, nchw=nchw)
+                    t.append(float(L.cis_cnn_conv_dev_last_ms()))
+                ms = float(np.median(t[1:]))
+                res["layers"].setdefault(name, {})[p] = {"ms": ms, "of_peak": 2.0 * macs / (ms * 1e-3) / PEAK[p]}
+                print("%-6s %-7s %.4f ms  %.3f of peak" % (name, p, ms, res["layers"][name][p]["of_peak"]))
+    if a.deviation:
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+        from conftest import load_golden
+        from test_lopq_hip_parity import hip_model
+        model = hip_model(load_golden("c3full")[0])
+        imgs = sentibank_images(256)
+        base = SentiBankNet(w).forward(imgs)
+        c0, f0 = model.predict_batch(base / np.linalg.norm(base, axis=1, keepdims=True))
+        for p in precs:
+            if p == "f32":
+                continue
+            f = nets[p].forward(imgs)
+            dev = np.abs(f.astype(np.float64) - base) / np.abs(base).max()
+            c1, f1 = model.predict_batch(f / np.linalg.norm(f, axis=1, keepdims=True))
+            res["deviation"][p] = {"max": float(dev.max()), "median": float(np.median(dev)), "fine_codes_changed": float((f1 != f0).mean()),
+                                   "coarse_pairs_changed": float((c1 != c0).any(axis=1).mean())}
+            print("%-7s deviation %s" % (p, res["deviation"][p]))
+    if a.out:
+        with open(a.out, "w") as fh:
+            json.dump(res, fh, indent=1, sort_keys=True)
+            fh.write("\n")
+
+
+if __name__ == "__main__":
+    main()
