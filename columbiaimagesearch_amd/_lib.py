@@ -159,6 +159,7 @@ _PROTOS = {
     "cis_index_last_stats": (c_int, [c_void_p, c_void_p]),
     "cis_index_last_scan_kernel": (c_int, [c_void_p]),
     "cis_cnn_create": (c_int, [POINTER(c_void_p), c_int, c_void_p, c_int]),
+    "cis_cnn_create_precision": (c_int, [POINTER(c_void_p), c_int, c_void_p, c_int, c_int]),
     "cis_cnn_destroy": (None, [c_void_p]),
     "cis_cnn_create_view": (c_int, [POINTER(c_void_p), c_void_p]),
     "cis_cnn_feat_dim": (c_int, [c_int]),
@@ -168,6 +169,7 @@ _PROTOS = {
     "cis_cnn_precision": (c_int, [c_void_p]),
     "cis_cnn_conv_dev_last_ms": (ctypes.c_float, []),
     "cis_cnn_conv_dev": (c_int, [c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 11 + [c_void_p, c_void_p]),
+    "cis_cnn_conv3x3_dev": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 7 + [c_void_p] + [c_int] * 3 + [c_void_p, c_void_p]),
     "cis_index_set_profiling": (c_int, [c_void_p, c_int]),
     "cis_index_set_scan_mode": (c_int, [c_void_p, c_int]),
     "cis_index_stream_counters": (c_int, [c_void_p, c_void_p]),

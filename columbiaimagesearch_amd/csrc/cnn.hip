@@ -966,7 +966,7 @@ struct LayerW {
     float* d_w = nullptr;  // packed [g][K][OCg]
     float* d_b = nullptr;
     float* d_w2 = nullptr; // 3x3 layers with IC == OC == C served by k_conv3x3_direct: [tap][C/2][C][2] (a k pair adjacent)
-    uint16_t* d_wh = nullptr;  // DeepSentibank under a 16-bit precision: the bf16 planes of cnn_bf16_pack (cis_cnn_set_precision)
+    uint16_t* d_wh = nullptr;  // under a 16-bit precision: the bf16 planes of cnn_bf16_pack (DeepSentibank: cis_cnn_set_precision; dlib: at creation)
 };
 
 // activations and split-K partial sums of one forward in flight
@@ -1012,7 +1012,7 @@ struct cis_cnn {
     uint64_t graph_clock = 0;
     hipStream_t gs = nullptr;   // capture stream
     bool graph_off = false;     // a capture failed on this handle: launches from here on
-    int precision = 0;          // CIS_CNN_F32 / CIS_CNN_BF16X3 / CIS_CNN_BF16: which kernels serve the GEMM layers (DeepSentibank)
+    int precision = 0;          // CIS_CNN_F32 / CIS_CNN_BF16X3 / CIS_CNN_BF16: which kernels serve the GEMM layers (dlib: its 3x3 layers but the tail's)
     int packed_lo = -1;         // what d_wh of the layers holds: -1 nothing, 0 the hi plane, 1 hi and lo
 };
 
@@ -1050,7 +1050,7 @@ extern "C" void cis_cnn_destroy(cis_cnn* c) {
     }
     for (auto& l : c->conv) { if (l.d_w) (void)hipFree(l.d_w); if (l.d_b) (void)hipFree(l.d_b); if (l.d_w2) (void)hipFree(l.d_w2); if (l.d_wh) (void)hipFree(l.d_wh); }
     for (auto& l : c->fc) { if (l.d_w) (void)hipFree(l.d_w); if (l.d_b) (void)hipFree(l.d_b); if (l.d_wh) (void)hipFree(l.d_wh); }
-    for (auto& l : c->dl) { if (l.d_w) (void)hipFree(l.d_w); if (l.d_b) (void)hipFree(l.d_b); if (l.d_w2) (void)hipFree(l.d_w2); }
+    for (auto& l : c->dl) { if (l.d_w) (void)hipFree(l.d_w); if (l.d_b) (void)hipFree(l.d_b); if (l.d_w2) (void)hipFree(l.d_w2); if (l.d_wh) (void)hipFree(l.d_wh); }
     for (auto& g : c->graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
     if (c->gs) (void)hipStreamDestroy(c->gs);
     for (auto& w : c->ws) w.release();
@@ -1094,7 +1094,14 @@ static int pack_conv_affine(LayerW* L, const float* w, const float* b, const flo
     return CIS_OK;
 }
 
-static int cnn_create_dlib(cis_cnn** out, const float* const* tensors, int n_tensors) {
+// the 16-bit planes of a layer whose K-major float32 weights [K][OC] are on the device already (affine folded): read back, split, packed
+static int pack_wh(LayerW* L, int K, int OC, int with_lo) {
+    std::vector<float> host((size_t)K * OC);
+    CIS_CHECK_HIP(hipMemcpy(host.data(), L->d_w, host.size() * sizeof(float), hipMemcpyDeviceToHost));
+    return cnn_bf16_pack(&L->d_wh, host.data(), 1, K, OC, with_lo);
+}
+
+static int cnn_create_dlib(cis_cnn** out, const float* const* tensors, int n_tensors, int precision) {
     CIS_REQUIRE(tensors != nullptr && n_tensors == 117, "the dlib face ResNet needs 117 tensors (conv0 w,b,gamma,beta; 14 blocks x 2 x (w,b,gamma,beta); fc)");
     for (int i = 0; i < 117; ++i) CIS_REQUIRE(tensors[i] != nullptr, "tensor %d is NULL", i);
     CIS_TRY(cis_lazy_init());
@@ -1114,15 +1121,39 @@ static int cnn_create_dlib(cis_cnn** out, const float* const* tensors, int n_ten
             for (int k = 0; k < 256; ++k) packed[(size_t)k * 128 + o] = tensors[116][(size_t)o * 256 + k];
         rc = upload_f(&c->dl[29].d_w, packed.data(), packed.size());
     }
+    if (precision != CIS_CNN_F32) {
+        // every 3x3 layer but the last block's second one (k_dlib_tail runs it in float32): packed once, views share the planes
+        const int with_lo = precision == CIS_CNN_BF16X3 ? 1 : 0;
+        for (int i = 0; i < 14 && rc == CIS_OK; ++i) {
+            rc = pack_wh(&c->dl[1 + 2 * i], 9 * kDlibBlocks[i].cin, kDlibBlocks[i].cout, with_lo);
+            if (rc == CIS_OK && i < 13) rc = pack_wh(&c->dl[2 + 2 * i], 9 * kDlibBlocks[i].cout, kDlibBlocks[i].cout, with_lo);
+        }
+        c->precision = precision;
+        c->packed_lo = with_lo;
+    }
     if (rc != CIS_OK) { cis_cnn_destroy(c); return rc; }
     *out = c;
     return CIS_OK;
 }
 
 extern "C" int cis_cnn_create(cis_cnn** out, int arch, const float* const* tensors, int n_tensors) {
+    return cis_cnn_create_precision(out, arch, tensors, n_tensors, CIS_CNN_F32);
+}
+
+static int cnn_create_sentibank(cis_cnn** out, int arch, const float* const* tensors, int n_tensors);
+
+extern "C" int cis_cnn_create_precision(cis_cnn** out, int arch, const float* const* tensors, int n_tensors, int precision) {
     CIS_REQUIRE(out != nullptr, "out is NULL");
     *out = nullptr;
-    if (arch == 2) return cnn_create_dlib(out, tensors, n_tensors);
+    CIS_REQUIRE(precision == CIS_CNN_F32 || precision == CIS_CNN_BF16X3 || precision == CIS_CNN_BF16, "precision %d: CIS_CNN_F32 (0), CIS_CNN_BF16X3 (1) or CIS_CNN_BF16 (2)", precision);
+    if (arch == 2) return cnn_create_dlib(out, tensors, n_tensors, precision);
+    CIS_TRY(cnn_create_sentibank(out, arch, tensors, n_tensors));
+    const int rc = precision == CIS_CNN_F32 ? CIS_OK : cis_cnn_set_precision(*out, precision);
+    if (rc != CIS_OK) { cis_cnn_destroy(*out); *out = nullptr; }
+    return rc;
+}
+
+static int cnn_create_sentibank(cis_cnn** out, int arch, const float* const* tensors, int n_tensors) {
     if (arch != 1) {
         cis_set_error("arch %d: CIS_CNN_SENTIBANK (1) and CIS_CNN_DLIB_RESNET (2) are built", arch);
         return CIS_EUNSUPPORTED;
@@ -1323,7 +1354,11 @@ static ConvDesc nhwc_conv(int n, int H, int W, int C, int OC, int k, int stride,
 // A convolution whose output has too few tiles to fill the chip (the deep, spatially small layers of the dlib net: 16-256
 // workgroups walking K = 1152 ... 2304 serially) splits K over blockIdx.z and adds the partial sums in a fixed order,
 // together with bias, residual branch and ReLU (k_splitk_reduce).
-static int conv_fill_chip(CnnWs* ws, ConvDesc d, const float* in, const LayerW& L, float* out, hipStream_t st) {
+// precision != CIS_CNN_F32 (L.d_wh packed): the 16-bit direct kernel for its two shapes, else k_conv_igemm_bf16 with its own K split.
+static int conv_fill_chip_bf16(CnnWs* ws, ConvDesc d, const float* in, const LayerW& L, float* out, int ns, hipStream_t st);
+
+static int conv_fill_chip(CnnWs* ws, ConvDesc d, const float* in, const LayerW& L, float* out, hipStream_t st, int precision = CIS_CNN_F32) {
+    if (precision != CIS_CNN_F32) return conv_fill_chip_bf16(ws, d, in, L, out, precision == CIS_CNN_BF16X3 ? 3 : 1, st);
     const float* w = L.d_w;
     const float* b = L.d_b;
     const int64_t npix = (int64_t)d.N * d.OH * d.OW;
@@ -1375,6 +1410,40 @@ static int conv_fill_chip(CnnWs* ws, ConvDesc d, const float* in, const LayerW& 
     launch_conv(dp, in, w, nullptr, part, st);
     const int64_t n4 = npix * d.OC / 4;
     hipLaunchKernelGGL(k_splitk_reduce, dim3((unsigned)ceil_div(n4, 256)), dim3(256), 0, st, part, splitk, dp.part_stride, b, out, n4, d.OC,
+                       d.relu, d.res, d.resC);
+    return CIS_OK;
+}
+
+static int conv_fill_chip_bf16(CnnWs* ws, ConvDesc d, const float* in, const LayerW& L, float* out, int ns, hipStream_t st) {
+    CIS_REQUIRE(L.d_wh != nullptr && L.d_b != nullptr, "16-bit convolution: this layer's 16-bit weights were not packed");
+    CIS_REQUIRE(d.groups == 1 && d.sC == 1 && d.runq == 0 && d.splitk == 1 && d.ICg % 8 == 0 && d.OC % 4 == 0,
+                "16-bit convolution: channels-last, one group, channels a multiple of 8 (got %d -> %d)", d.C, d.OC);
+    const int64_t npix = (int64_t)d.N * d.OH * d.OW;
+    if (!getenv("CIS_CNN_NO_DIRECT") && d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1 && d.C == d.OC && conv3x3_direct_bf16_serves(d.C, d.H, d.W))
+        return launch_conv3x3_direct_bf16(d.C, d.H, d.W, in, L.d_wh, L.d_b, out, d.N, d.res, d.resC, d.relu, ns, st);
+    // K split as for the float32 kernel, counted in this kernel's stages of 32 k: while the tiles leave CUs idle and every K range keeps
+    // at least 4 stages (128 k; floors of 2 and 9 stages moved the forward at batch 256 by no more than two processes of one setting
+    // differ: DESIGN.md section 5.4); the 128- and 256-channel maps take 128 x 128 tiles under the split
+    const int nkt = (d.K + 31) / 32, min_stages = 4;
+    const int64_t tiles = npix <= 2048 ? ceil_div(npix, npix >= 64 ? 64 : 32) * ceil_div((int64_t)d.OCg, 128) : ceil_div(npix, 64) * ceil_div((int64_t)d.OCg, 64);
+    int splitk = 1;
+    while (d.OCg > 32 && tiles * splitk < 512 && splitk < 32 && nkt / (splitk * 2) >= min_stages) splitk *= 2;
+    if (d.OCg % 128 == 0 && npix > 2048) {
+        const int64_t t128 = ceil_div(npix, 128) * (d.OCg / 128);
+        int s = 1;
+        while (t128 * s < 512 && s < 32 && nkt / (s * 2) >= min_stages) s *= 2;
+        if (t128 * s >= 512) splitk = s;
+    }
+    if (splitk == 1) return launch_conv_bf16(d, in, L.d_wh, L.d_b, out, ns, st);
+    CIS_TRY(ws->part.reserve((size_t)splitk * npix * d.OC * sizeof(float)));
+    float* part = ws->part.as<float>();
+    ConvDesc dp = d;
+    dp.splitk = splitk;
+    dp.part_stride = npix * d.OC;
+    dp.res = nullptr; dp.resC = 0;
+    CIS_TRY(launch_conv_bf16(dp, in, L.d_wh, nullptr, part, ns, st));
+    const int64_t n4 = npix * d.OC / 4;
+    hipLaunchKernelGGL(k_splitk_reduce, dim3((unsigned)ceil_div(n4, 256)), dim3(256), 0, st, part, splitk, dp.part_stride, L.d_b, out, n4, d.OC,
                        d.relu, d.res, d.resC);
     return CIS_OK;
 }
@@ -1527,6 +1596,51 @@ extern "C" int cis_cnn_conv_dev(const float* d_in, int in_nchw, const float* w, 
     return done(CIS_OK);
 }
 
+// One 3x3 layer of the dlib net's form on device buffers, in any precision, routed exactly as the forward routes it (conv_fill_chip: the
+// direct kernels for their two shapes, the implicit GEMM with its K split elsewhere): for tests and per-layer timing, NOT a fast path --
+// the OIHW weights are packed and uploaded by every call, and the call waits for the device.  Sets cis_cnn_conv_dev_last_ms.
+extern "C" int cis_cnn_conv3x3_dev(const float* d_in, const float* w, const float* bias, int N, int H, int W, int C, int OC, int stride, int pad,
+                                   const float* d_res, int resC, int relu, int precision, float* d_out, void* stream) {
+    CIS_REQUIRE(d_in && w && d_out, "NULL buffer");
+    CIS_REQUIRE(N >= 1 && H >= 1 && W >= 1 && C >= 1 && OC >= 1 && stride >= 1 && pad >= 0, "bad shape");
+    CIS_REQUIRE(H + 2 * pad >= 3 && W + 2 * pad >= 3, "the kernel is larger than the padded input");
+    CIS_REQUIRE(precision == CIS_CNN_F32 || precision == CIS_CNN_BF16X3 || precision == CIS_CNN_BF16, "precision %d: CIS_CNN_F32 (0), CIS_CNN_BF16X3 (1) or CIS_CNN_BF16 (2)", precision);
+    CIS_REQUIRE(OC % 4 == 0 && (precision == CIS_CNN_F32 || C % 8 == 0), "OC must be a multiple of 4, and C a multiple of 8 in the 16-bit precisions");
+    CIS_REQUIRE(d_res == nullptr || (resC >= 4 && resC <= OC && resC % 4 == 0), "resC: a multiple of 4, at most OC");
+    CIS_REQUIRE((int64_t)N * H * W * C < (1ll << 31) && (int64_t)OC * C * 9 < (1ll << 31), "layer too large");
+    CIS_TRY(cis_lazy_init());
+    hipStream_t st = (hipStream_t)stream;
+    LayerW L;
+    CnnWs ws;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    g_conv_dev_ms = -1.f;
+    auto done = [&](int rc) {
+        (void)hipStreamSynchronize(st);
+        if (rc == CIS_OK && ev[0] && ev[1]) (void)hipEventElapsedTime(&g_conv_dev_ms, ev[0], ev[1]);
+        for (auto& e : ev) if (e) (void)hipEventDestroy(e);
+        if (L.d_w) (void)hipFree(L.d_w);
+        if (L.d_b) (void)hipFree(L.d_b);
+        if (L.d_w2) (void)hipFree(L.d_w2);
+        if (L.d_wh) (void)hipFree(L.d_wh);
+        ws.release();
+        return rc;
+    };
+    int rc = pack_conv_affine(&L, w, bias, nullptr, nullptr, OC, C, 3);
+    if (rc == CIS_OK && precision != CIS_CNN_F32) rc = pack_wh(&L, 9 * C, OC, precision == CIS_CNN_BF16X3);
+    if (rc != CIS_OK) return done(rc);
+    ConvDesc d = nhwc_conv(N, H, W, C, OC, 3, stride, pad, relu);
+    if (d_res) { d.res = d_res; d.resC = resC; }
+    rc = conv_fill_chip(&ws, d, d_in, L, d_out, st, precision);  // untimed: it sizes the split-K workspace (an allocation)
+    if (rc != CIS_OK) return done(rc);
+    if (hipEventCreate(&ev[0]) == hipSuccess) (void)hipEventRecord(ev[0], st);
+    rc = conv_fill_chip(&ws, d, d_in, L, d_out, st, precision);
+    if (rc != CIS_OK) return done(rc);
+    if (hipEventCreate(&ev[1]) == hipSuccess) (void)hipEventRecord(ev[1], st);
+    if (hipGetLastError() != hipSuccess) { cis_set_error("convolution launch failed"); return done(CIS_EHIP); }
+    if (hipStreamSynchronize(st) != hipSuccess) { cis_set_error("convolution failed on the device"); return done(CIS_EHIP); }
+    return done(CIS_OK);
+}
+
 // Test hook (tests/test_cnn_hip_parity.py): CIS_CNN_POISON=<mask> fills the workspaces (bit 0..4: act0, act1, act2, act3, part) with
 // 0xff bytes (NaN) before a forward.  A forward must not read what it has not written: results do not change under any mask.
 static int cnn_poison(CnnWs* ws, hipStream_t st) {
@@ -1593,14 +1707,15 @@ static int cnn_forward_dlib(cis_cnn* c, CnnWs* ws, const float* d_in, int n, flo
             // the last block's second convolution, skip branch, add_prev, ReLU, global average and the fully connected layer: one launch
             // (k_dlib_tail; CIS_CNN_NO_TAIL=1 keeps the six launches it replaces)
             ConvDesc da = nhwc_conv(n, 4, 4, 256, 256, 3, 2, 0, 1);
-            CIS_TRY(conv_fill_chip(ws, da, x, c->dl[27], T1, st));  // [n][1][1][256]
+            CIS_TRY(conv_fill_chip(ws, da, x, c->dl[27], T1, st, c->precision));  // [n][1][1][256]
             hipLaunchKernelGGL(k_dlib_tail<2>, dim3((unsigned)ceil_div(n, 2)), dim3(256), 0, st, (const float*)T1, (const float*)x, (const float*)c->dl[28].d_w,
                                (const float*)c->dl[28].d_b, (const float*)c->dl[29].d_w, d_feats, n);
             CIS_CHECK_HIP(hipGetLastError());
             return CIS_OK;
         }
         ConvDesc da = nhwc_conv(n, H, W, C, b.cout, 3, s, p, 1);
-        CIS_TRY(conv_fill_chip(ws, da, x, c->dl[1 + 2 * i], T1, st));
+        CIS_TRY(conv_fill_chip(ws, da, x, c->dl[1 + 2 * i], T1, st, c->precision));
+        const int prec_b = i < 13 ? c->precision : CIS_CNN_F32;  // the last block's second convolution stays float32 (as in k_dlib_tail)
         ConvDesc db = nhwc_conv(n, da.OH, da.OW, b.cout, b.cout, 3, 1, 1, 0);
         int SH = H, SW = W, SC = C;
         if (b.down) { SH = (H - 2) / 2 + 1; SW = (W - 2) / 2 + 1; }
@@ -1618,9 +1733,9 @@ static int cnn_forward_dlib(cis_cnn* c, CnnWs* ws, const float* d_in, int n, flo
         }
         if (fuse) {
             db.res = skip; db.resC = SC; db.relu = 1;
-            CIS_TRY(conv_fill_chip(ws, db, T1, c->dl[2 + 2 * i], other, st));
+            CIS_TRY(conv_fill_chip(ws, db, T1, c->dl[2 + 2 * i], other, st, prec_b));
         } else {
-            CIS_TRY(conv_fill_chip(ws, db, T1, c->dl[2 + 2 * i], T2, st));
+            CIS_TRY(conv_fill_chip(ws, db, T1, c->dl[2 + 2 * i], T2, st, prec_b));
             if (b.down) {
                 hipLaunchKernelGGL(k_avgpool2_nhwc, grid((int64_t)n * SH * SW * C), dim3(256), 0, st, x, T1, n, H, W, C, SH, SW);
                 skip = T1;  // T1 is free again: conv b has consumed it (same stream)

@@ -31,30 +31,15 @@
 // Order of a sum (fixed, the same for every pixel, tile shape and batch position): k ascending in steps of 16; inside a step hi*hi,
 // then hi*lo (activation hi, weight lo), then lo*hi, all into the one float32 accumulator; under split-K the partial sums of the K ranges
 // are added in ascending order by k_splitk_reduce.
-// Epilogue as the float32 kernel: bias, optional ReLU, or raw partial sums under split-K.  Not a fast path for anything but the shapes of
-// DeepSentibank; shapes it does not serve are refused by launch_conv_bf16.
+// Epilogue as the float32 kernel: bias, the residual d.res[pixel][d.resC] for output channels below d.resC (the dlib net's add_prev),
+// optional ReLU, or raw partial sums under split-K.  Tuned for the shapes of DeepSentibank; it also serves the dlib net's 3x3 layers
+// that the direct kernel of cnn_bf16_direct.hip does not.  Shapes it does not serve are refused by launch_conv_bf16.
 #include <vector>
 #include "common.h"
 #include "cnn_conv.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-// round-to-nearest-even on the float32 bits; Inf stays Inf, NaN stays a (quiet) NaN
-static __host__ __device__ __forceinline__ uint32_t bf16_rne(float x) {
-    uint32_t u;
-    __builtin_memcpy(&u, &x, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-// x = hi + lo + residue, |residue| <= 2^-16 |x|.  hi not finite: lo = 0 (Inf - Inf would turn an Inf into a NaN)
-static __host__ __device__ __forceinline__ void bf16_split(float x, uint32_t& hi, uint32_t& lo) {
-    hi = bf16_rne(x);
-    const uint32_t hb = hi << 16;
-    float hf;
-    __builtin_memcpy(&hf, &hb, 4);
-    lo = (hi & 0x7f80u) == 0x7f80u ? 0u : bf16_rne(x - hf);
-}
 
 template <int WM, int WN, int WAVES_M, int WAVES_N, bool PLANES, int NS>
 __global__ __launch_bounds__(256, 2) void k_conv_igemm_bf16(const float* __restrict__ in, const uint16_t* __restrict__ Wp,
@@ -269,6 +254,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_igemm_bf16(const float* __restr
                         out[(int64_t)ksplit * d.part_stride + p * d.OC + ocl] = acc[i][j][r];  // raw partial sum
                     } else {
                         float v = acc[i][j][r] + bv;
+                        if (d.res && ocl < d.resC) v += d.res[p * d.resC + ocl];  // (groups == 1: launch_conv_bf16)
                         if (d.relu) v = v > 0.f ? v : 0.f;
                         out[p * d.OC + g * d.OCg + ocl] = v;
                     }
@@ -319,7 +305,7 @@ static void launch_bf16_cfg(const ConvDesc& d, const float* in, const uint16_t* 
 int launch_conv_bf16(const ConvDesc& d, const float* in, const uint16_t* w, const float* b, float* out, int ns, hipStream_t st) {
     CIS_REQUIRE(ns == 1 || ns == 3, "16-bit convolution: ns must be 1 or 3");
     CIS_REQUIRE(d.splitk <= 1 || d.groups == 1, "16-bit convolution: a K split needs groups == 1");
-    CIS_REQUIRE(d.res == nullptr, "16-bit convolution: no residual input");
+    CIS_REQUIRE(d.res == nullptr || (d.groups == 1 && d.resC >= 1), "16-bit convolution: a residual input needs groups == 1");
     if (d.run_planes > 0) {
         CIS_REQUIRE(d.pad == 0 && d.groups == 1 && d.sW == 1 && d.runq * 4 >= d.KW && d.run_planes == d.ICg * d.KH && d.K == d.run_planes * d.runq * 4 &&
                         d.in_elems >= 4,

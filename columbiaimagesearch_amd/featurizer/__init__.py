@@ -2,7 +2,7 @@
 reference: cufacesearch/cufacesearch/featurizer/generic_featurizer.py, featsio.py"""
 from .generic_featurizer import GenericFeaturizer, get_feat_size, get_featurizer
 from .featsio import featB64decode, featB64encode, get_feat_dtype, normfeatB64encode
-from .sbhip_img_featurizer import SentiBankHIPImgFeaturizer, SentiBankNet, conv2d_dev
+from .sbhip_img_featurizer import SentiBankHIPImgFeaturizer, SentiBankNet, conv2d_dev, conv3x3_dev
 from .dlibhip_featurizer import DLibFaceNet, DLibHIPFeaturizer
 
 # Version of the forward kernels' float32 SUMMATION ORDER (csrc/cnn.hip).  Descriptors of different versions agree to ~1e-6 relative but
@@ -12,4 +12,4 @@ from .dlibhip_featurizer import DLibFaceNet, DLibHIPFeaturizer
 FEATURE_KERNEL_VERSION = 2
 
 __all__ = ["FEATURE_KERNEL_VERSION", "GenericFeaturizer", "get_featurizer", "get_feat_size", "get_feat_dtype", "featB64encode", "featB64decode",
-           "normfeatB64encode", "SentiBankHIPImgFeaturizer", "SentiBankNet", "conv2d_dev", "DLibHIPFeaturizer", "DLibFaceNet"]
+           "normfeatB64encode", "SentiBankHIPImgFeaturizer", "SentiBankNet", "conv2d_dev", "conv3x3_dev", "DLibHIPFeaturizer", "DLibFaceNet"]

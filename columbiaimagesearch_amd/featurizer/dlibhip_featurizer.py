@@ -2,7 +2,8 @@
 
 Mirror of DLibFeaturizer (cufacesearch/cufacesearch/featurizer/dlib_featurizer.py:50-105): constructor
 ``(global_conf_in, prefix)`` reading ``<prefix>pred_path`` (68-landmark shape predictor) and ``<prefix>rec_path``
-(recognition network weights), ``featurize(img, bbox)`` -> 128 float64 values.  The landmark predictor (:103) is chosen by the config
+(recognition network weights) and, as an addition, ``<prefix>precision`` ("f32", "bf16x3" or "bf16": the arithmetic of the network's 3x3
+convolutions), ``featurize(img, bbox)`` -> 128 float64 values.  The landmark predictor (:103) is chosen by the config
 key ``<prefix>landmark_backend``: ``"dlib"`` (the default) is dlib's host code, as in the reference, unless the landmarks come through
 ``landmark_fn`` or ``landmarks=``; ``"hip"`` reads ``pred_path`` (dlib's ``.dat`` or an ``.npz``: featurizer/shape_predictor.py, parity
 with dlib UNPINNED) on first use and runs the regression trees in libcis_hip.so (csrc/shape_predictor.hip), all detections of an image
@@ -17,6 +18,7 @@ import numpy as np
 
 from .. import _lib
 from .generic_featurizer import GenericFeaturizer
+from .sbhip_img_featurizer import PRECISIONS, _precision_code
 
 INPUT_HW = 150
 FEAT_DIM = 128
@@ -32,14 +34,22 @@ def tensor_names():
 
 
 class DLibFaceNet(object):
-    """The network alone: chips [n,150,150,3] (uint8 or float, RGB 0..255) -> [n,128] float32."""
+    """The network alone: chips [n,150,150,3] (uint8 or float, RGB 0..255) -> [n,128] float32.  precision "f32" (the default),
+    "bf16x3" or "bf16": the arithmetic of the 3x3 convolutions (cis_cnn_create_precision); fixed at creation."""
 
-    def __init__(self, weights):
+    def __init__(self, weights, precision="f32"):
+        code = _precision_code(precision)
         arrs = [np.ascontiguousarray(weights[n], dtype=np.float32) for n in tensor_names()]
         ptrs = (_lib.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
         out = _lib.c_void_p()
-        _lib.check(_lib.lib().cis_cnn_create(_lib.ctypes.byref(out), 2, ptrs, len(arrs)))
+        _lib.check(_lib.lib().cis_cnn_create_precision(_lib.ctypes.byref(out), 2, ptrs, len(arrs), code))
         self._h = out.value
+
+    @property
+    def precision(self):
+        """"f32", "bf16x3" or "bf16" (a view reports its base's)"""
+        code = _lib.lib().cis_cnn_precision(self._h)
+        return [k for k, v in PRECISIONS.items() if v == code][0]
 
     def view(self):
         """A second handle on the same weights with its own workspaces and streams (cis_cnn_create_view): run consecutive batches
@@ -111,7 +121,7 @@ class DLibHIPFeaturizer(GenericFeaturizer):
         else:
             raise NotImplementedError("rec_path must be dlib's .dat, its net_to_xml export (.xml), or an .npz with the "
                                       "117 network tensors -- see INTEGRATION.md section 4")
-        self.net = DLibFaceNet(weights)
+        self.net = DLibFaceNet(weights, precision=str(self.get_param("precision", "f32")))
         self._sp = None
         self._sp_hip = None      # landmark_backend "hip": loaded from pred_path on first use
         self.chip_fn = None      # (img, bbox) -> aligned 150x150x3 chip

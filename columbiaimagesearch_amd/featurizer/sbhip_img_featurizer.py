@@ -55,6 +55,34 @@ def conv2d_dev(x, w, b, stride=1, pad=0, groups=1, relu=False, precision="f32", 
     return out
 
 
+def conv3x3_dev(x, w, b, stride=1, pad=1, relu=False, precision="f32", res=None):
+    """One 3x3 layer of the dlib network's form through cis_cnn_conv3x3_dev, routed as the forward routes it in `precision` (direct
+    kernels for 35x35x32 and 17x17x64 at stride 1 / pad 1, the implicit GEMM with its K split elsewhere); for tests and per-layer timing.
+    x: contiguous float32 CUDA tensor [N,H,W,C]; w: OIHW [OC,C,3,3] and b: [OC] or None, host arrays; res: None or a contiguous float32
+    CUDA tensor [N,OH,OW,resC], added to output channels below resC before the ReLU -> CUDA tensor [N,OH,OW,OC]."""
+    import torch
+    if not (x.is_cuda and x.is_contiguous() and x.dtype == torch.float32 and x.dim() == 4):
+        raise ValueError("x must be a contiguous 4-d float32 tensor on the GPU")
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    N, H, W, C = tuple(x.shape)
+    if w.ndim != 4 or tuple(w.shape[1:]) != (C, 3, 3):
+        raise ValueError("w must be [OC, %d, 3, 3], got %r" % (C, w.shape))
+    OC = w.shape[0]
+    if b is not None:
+        b = np.ascontiguousarray(b, dtype=np.float32)
+        if b.shape != (OC,):
+            raise ValueError("b must be [OC]")
+    OH, OW = (H + 2 * pad - 3) // stride + 1, (W + 2 * pad - 3) // stride + 1
+    if res is not None and not (res.is_cuda and res.is_contiguous() and res.dtype == torch.float32 and tuple(res.shape[:3]) == (N, OH, OW)):
+        raise ValueError("res must be a contiguous float32 [N,OH,OW,resC] tensor on the GPU")
+    out = torch.empty((N, max(OH, 0), max(OW, 0), OC), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().cis_cnn_conv3x3_dev(x.data_ptr(), _lib.ptr(w), _lib.ptr(b) if b is not None else None, N, H, W, C, OC, stride, pad,
+                                              res.data_ptr() if res is not None else None, res.shape[3] if res is not None else 0,
+                                              int(bool(relu)), _precision_code(precision), out.data_ptr(),
+                                              torch.cuda.current_stream(x.device).cuda_stream))
+    return out
+
+
 def bytescale(data, low=0, high=255, cmin=None, cmax=None):
     """scipy.misc.bytescale as imresize -> toimage applies it to the float image caffe.io.load_image returns:
     the image's own min..max is stretched to 0..255 before the resize (so a low-contrast image is NOT resized

@@ -609,6 +609,13 @@ int cis_cnn_create_view(cis_cnn** out, cis_cnn* base);
 #define CIS_CNN_BF16 2
 int cis_cnn_set_precision(cis_cnn* c, int precision);
 int cis_cnn_precision(const cis_cnn* c);
+/* cis_cnn_create with the precision chosen at creation.  CIS_CNN_SENTIBANK: cis_cnn_create followed by cis_cnn_set_precision.
+ * CIS_CNN_DLIB_RESNET: the only way to a 16-bit dlib handle (cis_cnn_set_precision refuses that network) -- the 3x3 convolutions run on
+ * the 16-bit matrix instructions (the two large stride-1 shapes in a direct kernel, csrc/cnn_bf16_direct.hip; the rest in the implicit
+ * GEMM of csrc/cnn_bf16.hip); the first layer, the fused tail (the last block's second convolution, skip, average, fc), the pools and
+ * the separate add stay float32.  The 16-bit weights are packed here, once, from the affine-folded float32 weights; views share them
+ * and report the same cis_cnn_precision.  cis_cnn_create is this call with CIS_CNN_F32. */
+int cis_cnn_create_precision(cis_cnn** out, int arch, const float* const* tensors, int n_tensors, int precision);
 /* One convolution layer on device buffers, for tests and per-layer timing: NOT a fast path (the weights are packed and uploaded by
  * every call, and the call returns after the device has finished).  d_in: float32 on the device, [N][H][W][C] (in_nchw = 0) or
  * [N][C][H][W] (in_nchw = 1: the first-layer route, pad == 0 and groups == 1).  w: OIHW float32 [OC][C / groups][k][k] and bias [OC]
@@ -620,6 +627,14 @@ int cis_cnn_conv_dev(const float* d_in, int in_nchw, const float* w, const float
 /* Device time in milliseconds of the layer's launches (the convolution, and the split-K reduction where there is one) in this thread's
  * last successful cis_cnn_conv_dev, between two events on its stream; -1 before the first call and after a failed one. */
 float cis_cnn_conv_dev_last_ms(void);
+/* One 3 x 3 convolution of the dlib network's form on device buffers, routed exactly as the forward routes it in `precision` (the
+ * direct kernels for 35 x 35 x 32 and 17 x 17 x 64 at stride 1 / pad 1, the implicit GEMM with its K split elsewhere): for tests and
+ * per-layer timing, NOT a fast path (weights packed per call, the layer runs twice -- once untimed --, the call waits for the device).
+ * d_in [N][H][W][C] float32 on the device; w OIHW [OC][C][3][3] and bias [OC] (or NULL) in HOST memory; d_res NULL or [N][OH][OW][resC]
+ * on the device, added to output channels below resC before the ReLU; d_out [N][OH][OW][OC].  OC % 4 == 0; 16-bit: C % 8 == 0.
+ * Sets cis_cnn_conv_dev_last_ms. */
+int cis_cnn_conv3x3_dev(const float* d_in, const float* w, const float* bias, int N, int H, int W, int C, int OC, int stride, int pad,
+                        const float* d_res, int resC, int relu, int precision, float* d_out, void* stream);
 
 /* ---- aligned face chips: the image side of dlib's compute_face_descriptor(img, shape) -------------------------------------
  * (cufacesearch/cufacesearch/featurizer/dlib_featurizer.py:103-105).  The caller supplies the 68 landmarks (the shape predictor is
