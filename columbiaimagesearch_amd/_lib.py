@@ -127,7 +127,12 @@ _PROTOS = {
                                       c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "cis_rerank_select_merged_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_int, c_int, c_int,
                                              c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cis_rerank_select_half_dev": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p,
+                                           c_int, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cis_rerank_packed_half_dev": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int64,
+                                           c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "cis_featstore_create":(c_int, [POINTER(c_void_p), c_int, c_int, c_int64]),
+    "cis_featstore_create_half": (c_int, [POINTER(c_void_p), c_int, c_int64]),
     "cis_featstore_destroy": (None, [c_void_p]),
     "cis_featstore_size": (c_int64, [c_void_p]),
     "cis_featstore_reserve": (c_int, [c_void_p, c_int64, c_void_p]),
@@ -139,6 +144,7 @@ _PROTOS = {
                                    POINTER(c_int64), POINTER(c_int64)]),
     "cis_exact_knn_dev": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_int, c_int64, c_int, c_void_p, c_void_p,
                                   c_void_p]),
+    "cis_exact_knn_half_dev": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "cis_exact_knn": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_int, c_int64, c_int, c_void_p, c_void_p]),
     "cis_exact_knn_set_mode": (c_int, [c_int]),
     "cis_exact_knn_stats": (c_int, [c_void_p]),

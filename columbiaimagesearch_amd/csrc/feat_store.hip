@@ -1,7 +1,9 @@
 // A device-resident feature store that grows and shrinks by kernels: the HBase `put` / fetch of the reference's features
 // (hbase_indexer_minimal.py:779-831) for the exact re-rank of lopq_rerank.hip, addressed by the index's device ids.
 //
-// A cis_featstore owns a feature matrix [cap_rows][D] (float32 or float64), the row -> id column row_ids [cap_rows], the id -> row
+// A cis_featstore owns a feature matrix [cap_rows][D] (float32 or float64; or float16 behind a float32 interface,
+// cis_featstore_create_half: put converts on the way in, get and rows on the way out, with the kernels of feat_half.hip, and remove
+// moves the 2 D-byte rows with k_fs_copy as they are), the row -> id column row_ids [cap_rows], the id -> row
 // table keys / rows [cap] (layout, hash, linear probing and -1 = empty of lopq_rerank.hip: row_of_id reads it unchanged) and the live
 // row count n.  Rows [0, n) are always dense, so cis_exact_knn_dev and cis_rerank_select_dev read the matrix directly
 // (cis_featstore_view).
@@ -49,10 +51,13 @@
 
 int cis_seg_sort_u64(void* temp, size_t* temp_bytes, const uint64_t* keys_in, uint64_t* keys_out, const uint64_t* vals_in,
                      uint64_t* vals_out, int64_t n, int nseg, const int64_t* seg_begin, const int64_t* seg_end, hipStream_t st);
+// feat_half.hip: k_fs_copy's jobs with a conversion, float32 -> float16 rows (put) and float16 -> float32 rows (get; src == NULL: row j)
+int cis_fs_half_scatter(const void* from_f32, void* to_f16, int D, const int64_t* src, const int64_t* dst, int64_t njobs, hipStream_t st);
+int cis_fs_half_gather(const void* from_f16, void* to_f32, int D, const int64_t* src, int64_t njobs, hipStream_t st);
 
 struct cis_featstore {
     int device = 0;
-    int D = 0, f_dtype = 0;
+    int D = 0, f_dtype = 0;       // f_dtype: bytes per stored element (FS_F16 = 2: float16 rows, float32 at the interface)
     void* feats = nullptr;        // [cap_rows][D]
     int64_t* row_ids = nullptr;   // [cap_rows]
     int64_t cap_rows = 0, n = 0;
@@ -68,6 +73,7 @@ struct cis_featstore {
 namespace {
 
 constexpr int64_t FS_EMPTY = -1, FS_TOMB = -2;
+constexpr int FS_F16 = 2;                          // f_dtype of a store made by cis_featstore_create_half
 constexpr int64_t FS_MAX_CAP = (int64_t)1 << 36;   // lopq_rerank.hip's IDMAP_MAX_CAP
 constexpr int64_t FS_MAX_BATCH = (int64_t)1 << 30;
 constexpr int FS_CNT_A = 0, FS_CNT_NEW = 1, FS_CNT_ERR = 2, FS_WORDS = 4;  // A: skipped (put) or removed (remove)
@@ -440,12 +446,8 @@ int fs_ready(cis_featstore* fs) {
 
 }  // namespace
 
-extern "C" int cis_featstore_create(cis_featstore** out, int D, int f_dtype, int64_t reserve_rows) {
-    CIS_REQUIRE(out != nullptr, "out is NULL");
-    *out = nullptr;
-    CIS_REQUIRE(D > 0 && D <= (1 << 24), "the feature width must be in [1, 2^24] (D = %d)", D);
-    CIS_REQUIRE(f_dtype == CIS_F32 || f_dtype == CIS_F64, "f_dtype must be 4 or 8");
-    CIS_REQUIRE(reserve_rows >= 0 && reserve_rows <= FS_MAX_CAP / 8, "bad reserve_rows");
+// the store behind both create calls, their arguments checked
+static int fs_create(cis_featstore** out, int D, int f_dtype, int64_t reserve_rows) {
     CIS_TRY(cis_lazy_init());
     cis_featstore* fs = new cis_featstore();
     fs->device = cis_current_device();
@@ -467,6 +469,23 @@ extern "C" int cis_featstore_create(cis_featstore** out, int D, int f_dtype, int
     }
     *out = fs;
     return CIS_OK;
+}
+
+extern "C" int cis_featstore_create(cis_featstore** out, int D, int f_dtype, int64_t reserve_rows) {
+    CIS_REQUIRE(out != nullptr, "out is NULL");
+    *out = nullptr;
+    CIS_REQUIRE(D > 0 && D <= (1 << 24), "the feature width must be in [1, 2^24] (D = %d)", D);
+    CIS_REQUIRE(f_dtype == CIS_F32 || f_dtype == CIS_F64, "f_dtype must be 4 or 8");
+    CIS_REQUIRE(reserve_rows >= 0 && reserve_rows <= FS_MAX_CAP / 8, "bad reserve_rows");
+    return fs_create(out, D, f_dtype, reserve_rows);
+}
+
+extern "C" int cis_featstore_create_half(cis_featstore** out, int D, int64_t reserve_rows) {
+    CIS_REQUIRE(out != nullptr, "out is NULL");
+    *out = nullptr;
+    CIS_REQUIRE(D > 0 && D <= (1 << 24) && D % 8 == 0, "the width of float16 rows must be a multiple of 8 in [8, 2^24] (D = %d)", D);
+    CIS_REQUIRE(reserve_rows >= 0 && reserve_rows <= FS_MAX_CAP / 8, "bad reserve_rows");
+    return fs_create(out, D, FS_F16, reserve_rows);
 }
 
 extern "C" void cis_featstore_destroy(cis_featstore* fs) {
@@ -523,7 +542,10 @@ extern "C" int cis_featstore_put_dev(cis_featstore* fs, const int64_t* d_ids, co
     dev_exclusive_scan<uint32_t, uint32_t>(s.flag, s.rank, n, s.sums, nullptr, cnt + FS_CNT_NEW, st);
     hipLaunchKernelGGL(k_fs_assign, g, b, 0, st, d_ids, (const int64_t*)s.slot, (const int64_t*)s.old, (const int32_t*)s.last,
                        (const uint32_t*)s.rank, nb, fs->n, fs->cap_rows, rows, fs->row_ids, s.job_src, s.job_dst, cnt);
-    launch_copy<false>(d_feats, fs->feats, (int64_t)fs->D * fs->f_dtype, s.job_src, s.job_dst, n, st);
+    if (fs->f_dtype == FS_F16)
+        CIS_TRY(cis_fs_half_scatter(d_feats, fs->feats, fs->D, s.job_src, s.job_dst, n, st));
+    else
+        launch_copy<false>(d_feats, fs->feats, (int64_t)fs->D * fs->f_dtype, s.job_src, s.job_dst, n, st);
     CIS_CHECK_HIP(hipGetLastError());
     CIS_TRY(fs_read_counters(fs, st));
     const int64_t added = fs->h_cnt[FS_CNT_NEW];
@@ -581,7 +603,10 @@ extern "C" int cis_featstore_get_dev(cis_featstore* fs, const int64_t* d_ids, in
     }
     CIS_REQUIRE(fs->cap > 0, "feature store: no id table");  // (cis_featstore_create builds one)
     CIS_TRY(cis_idmap_lookup_dev(fs->keys.as<int64_t>(), fs->rows.as<int64_t>(), fs->cap, fs->n, d_ids, m, out_rows, st));
-    launch_copy<true>(fs->feats, d_out_feats, (int64_t)fs->D * fs->f_dtype, out_rows, nullptr, m, st);
+    if (fs->f_dtype == FS_F16)
+        CIS_TRY(cis_fs_half_gather(fs->feats, d_out_feats, fs->D, out_rows, m, st));
+    else
+        launch_copy<true>(fs->feats, d_out_feats, (int64_t)fs->D * fs->f_dtype, out_rows, nullptr, m, st);
     CIS_CHECK_HIP(hipGetLastError());
     return CIS_OK;
 }
@@ -593,7 +618,10 @@ extern "C" int cis_featstore_rows_dev(cis_featstore* fs, int64_t first, int64_t 
     if (count == 0) return CIS_OK;
     CIS_TRY(fs_ready(fs));
     const size_t row_bytes = (size_t)fs->D * (size_t)fs->f_dtype;
-    if (d_out_feats)
+    if (d_out_feats && fs->f_dtype == FS_F16) {
+        CIS_TRY(cis_fs_half_gather((const unsigned char*)fs->feats + (size_t)first * row_bytes, d_out_feats, fs->D, nullptr, count, (hipStream_t)stream));
+        CIS_CHECK_HIP(hipGetLastError());
+    } else if (d_out_feats)
         CIS_CHECK_HIP(hipMemcpyAsync(d_out_feats, (const unsigned char*)fs->feats + (size_t)first * row_bytes, (size_t)count * row_bytes,
                                      hipMemcpyDeviceToDevice, (hipStream_t)stream));
     if (d_out_ids)

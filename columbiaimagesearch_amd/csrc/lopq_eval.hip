@@ -31,6 +31,10 @@
 // path: k_exact, one workgroup per flagged query, one row per lane with the sequential chain, survivors of a running
 // (dist, index) threshold collected and compacted by a lexicographic rank.  Small chunks (fewer than 128 S_min rows) and
 // cis_exact_knn_set_mode(1) take that path for every query.
+//
+// float16 data (cis_exact_knn_half_dev: the rows of a half feature store) runs through the same kernels with TD = _Float16: float16 ->
+// float32 and -> float64 are exact, so the data is widened while it is staged into sA and while the chain reads it, the matrix-core
+// product stays the float32 one and the bound E holds unchanged ("inputs rounded to float32" costs nothing for such data).
 #include <algorithm>
 #include <mutex>
 
@@ -440,9 +444,10 @@ extern "C" int cis_exact_knn_stats(int64_t stats[3]) {
     return CIS_OK;
 }
 
-extern "C" int cis_exact_knn_dev(const void* d_data, int data_dtype, int64_t m2, int d, const void* d_q, int q_dtype, int m1, int k,
-                                 int64_t base, int accumulate, int64_t* d_idx, double* d_dist, void* stream) {
-    CIS_TRY(knn_validate(data_dtype, m2, d, q_dtype, m1, k));
+// The driver of both device entry points, their dtypes checked.  data_dtype: bytes per element, KNN_F16 = 2 for float16.
+constexpr int KNN_F16 = 2;
+static int knn_run(const void* d_data, int data_dtype, int64_t m2, int d, const void* d_q, int q_dtype, int m1, int k, int64_t base,
+                   int accumulate, int64_t* d_idx, double* d_dist, void* stream) {
     CIS_REQUIRE(m1 == 0 || (d_q && d_idx && d_dist), "NULL query or result buffer");
     CIS_REQUIRE(m2 == 0 || d_data, "NULL data buffer");
     CIS_TRY(cis_lazy_init());
@@ -455,10 +460,26 @@ extern "C" int cis_exact_knn_dev(const void* d_data, int data_dtype, int64_t m2,
         CIS_CHECK_HIP(hipGetLastError());
     }
     if (m2 == 0) return CIS_OK;
+    if (data_dtype == KNN_F16 && q_dtype == CIS_F32) return knn_all((const _Float16*)d_data, m2, d, (const float*)d_q, m1, k, base, d_idx, d_dist, st);
+    if (data_dtype == KNN_F16) return knn_all((const _Float16*)d_data, m2, d, (const double*)d_q, m1, k, base, d_idx, d_dist, st);
     if (data_dtype == CIS_F32 && q_dtype == CIS_F32) return knn_all((const float*)d_data, m2, d, (const float*)d_q, m1, k, base, d_idx, d_dist, st);
     if (data_dtype == CIS_F32) return knn_all((const float*)d_data, m2, d, (const double*)d_q, m1, k, base, d_idx, d_dist, st);
     if (q_dtype == CIS_F32) return knn_all((const double*)d_data, m2, d, (const float*)d_q, m1, k, base, d_idx, d_dist, st);
     return knn_all((const double*)d_data, m2, d, (const double*)d_q, m1, k, base, d_idx, d_dist, st);
+}
+
+extern "C" int cis_exact_knn_dev(const void* d_data, int data_dtype, int64_t m2, int d, const void* d_q, int q_dtype, int m1, int k,
+                                 int64_t base, int accumulate, int64_t* d_idx, double* d_dist, void* stream) {
+    CIS_TRY(knn_validate(data_dtype, m2, d, q_dtype, m1, k));
+    return knn_run(d_data, data_dtype, m2, d, d_q, q_dtype, m1, k, base, accumulate, d_idx, d_dist, stream);
+}
+
+extern "C" int cis_exact_knn_half_dev(const void* d_data, int64_t m2, int d, const void* d_q, int q_dtype, int m1, int k, int64_t base,
+                                      int accumulate, int64_t* d_idx, double* d_dist, void* stream) {
+    CIS_TRY(knn_validate(CIS_F32, m2, d, q_dtype, m1, k));  // (the data's type is this entry point's)
+    CIS_REQUIRE(m2 == 0 || d_data, "NULL data buffer");
+    if (m1 == 0) return CIS_OK;  // nothing to do: the device is not touched
+    return knn_run(d_data, KNN_F16, m2, d, d_q, q_dtype, m1, k, base, accumulate, d_idx, d_dist, stream);
 }
 
 extern "C" int cis_exact_knn(const void* data, int data_dtype, int64_t m2, int d, const void* q, int q_dtype, int m1, int k, int64_t base,

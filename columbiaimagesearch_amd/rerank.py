@@ -208,18 +208,31 @@ class FeatureStore(object):
 
     Rows [0, len) are dense.  A removal fills the holes below the new length with the rows from the tail, so after a removal
     the row order is not the insertion order, and `search_exact` breaks exact distance ties by row.  One store per device;
-    calls on a store must be ordered by the caller's streams.  Nothing is persisted."""
+    calls on a store must be ordered by the caller's streams.  Nothing is persisted.
 
-    def __init__(self, D, dtype, reserve=0, device=None):
+    `dtype` is the type at the interface: what put_dev takes, what get_dev / rows_dev return, and the type of the queries.
+    `storage` is what a row occupies in HBM: None (the same as dtype) or torch.float16 with dtype float32 and D % 8 == 0
+    (cis_featstore_create_half; csrc/feat_half.hip).  A float16 store rounds every row to nearest even on the way in, so get_dev
+    hands back the ROUNDED row, widened; 1M x 4096 features are 8 GB instead of 16, and the re-rank reads half the bytes."""
+
+    def __init__(self, D, dtype, reserve=0, device=None, storage=None):
         import torch
         if dtype not in (torch.float32, torch.float64):
             raise ValueError("dtype must be torch.float32 or torch.float64")
+        if storage is not None and storage != dtype:
+            if storage != torch.float16 or dtype != torch.float32 or int(D) % 8 != 0:
+                raise ValueError("storage must be None, the dtype itself, or torch.float16 with dtype torch.float32 and D % 8 == 0")
         self.D, self.dtype = int(D), dtype
+        self.storage = dtype if storage is None else storage
+        self._half = self.storage == torch.float16
         self._code = _lib.CIS_F32 if dtype == torch.float32 else _lib.CIS_F64
         self._fs = None
         h = _lib.ctypes.c_void_p()
         # (the library comes first: without a GPU this is its loud failure, not torch's)
-        _lib.check(_lib.lib().cis_featstore_create(_lib.ctypes.byref(h), self.D, self._code, int(reserve)))
+        if self._half:
+            _lib.check(_lib.lib().cis_featstore_create_half(_lib.ctypes.byref(h), self.D, int(reserve)))
+        else:
+            _lib.check(_lib.lib().cis_featstore_create(_lib.ctypes.byref(h), self.D, self._code, int(reserve)))
         self._fs = h
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
 
@@ -372,8 +385,10 @@ class FeatureStore(object):
             if not (t.is_cuda and t.is_contiguous() and t.dtype == dt and tuple(t.shape) == shp):
                 raise ValueError("out[%r] must be a contiguous %s tensor of shape %r on the GPU" % (k, str(dt).split(".")[-1], shp))
         feats, _, keys, rows, cap, n = self._view()
-        _lib.check(_lib.lib().cis_rerank_select_dev(
-            feats, self._code, n, self.D, keys, rows, cap, q.data_ptr(), nq, ids.data_ptr(), adc.data_ptr(), L, nb,
+        L_ = _lib.lib()
+        select = (lambda f, *a: L_.cis_rerank_select_half_dev(f, *a)) if self._half else (lambda f, *a: L_.cis_rerank_select_dev(f, self._code, *a))
+        _lib.check(select(
+            feats, n, self.D, keys, rows, cap, q.data_ptr(), nq, ids.data_ptr(), adc.data_ptr(), L, nb,
             int(max_returned or 0), 0 if near_dup_th is None else 1, 0.0 if near_dup_th is None else float(near_dup_th),
             out["ids"].data_ptr(), out["dists"].data_ptr(), out["src"].data_ptr(), out["n_kept"].data_ptr(),
             torch.cuda.current_stream(dev).cuda_stream))
@@ -401,9 +416,10 @@ class FeatureStore(object):
         n_rec = int(recs.shape[0])
         true_d = torch.empty(n_rec, dtype=torch.float64, device=q.device)
         feats, _, keys, rows, cap, n = self._view()
-        _lib.check(_lib.lib().cis_rerank_packed_dev(feats, self._code, n, self.D, keys, rows, cap, q.data_ptr(), nq, recs.data_ptr(),
-                                                    n_rec, off.data_ptr(), cnt.data_ptr(), nb, true_d.data_ptr(),
-                                                    torch.cuda.current_stream(q.device).cuda_stream))
+        L_ = _lib.lib()
+        packed = (lambda f, *a: L_.cis_rerank_packed_half_dev(f, *a)) if self._half else (lambda f, *a: L_.cis_rerank_packed_dev(f, self._code, *a))
+        _lib.check(packed(feats, n, self.D, keys, rows, cap, q.data_ptr(), nq, recs.data_ptr(), n_rec, off.data_ptr(), cnt.data_ptr(),
+                          nb, true_d.data_ptr(), torch.cuda.current_stream(q.device).cuda_stream))
         return true_d
 
     def search_exact(self, q, k):
@@ -417,9 +433,10 @@ class FeatureStore(object):
         rows = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=q.device)
         dists = torch.empty((nq, max(k, 0)), dtype=torch.float64, device=q.device)
         feats, _, _, _, _, n = self._view()
-        _lib.check(_lib.lib().cis_exact_knn_dev(feats, self._code, n, self.D, q.data_ptr(),
-                                                _lib.CIS_F32 if q.dtype == torch.float32 else _lib.CIS_F64, nq, k, 0, 0,
-                                                rows.data_ptr(), dists.data_ptr(), torch.cuda.current_stream(q.device).cuda_stream))
+        L_ = _lib.lib()
+        knn = (lambda f, *a: L_.cis_exact_knn_half_dev(f, *a)) if self._half else (lambda f, *a: L_.cis_exact_knn_dev(f, self._code, *a))
+        _lib.check(knn(feats, n, self.D, q.data_ptr(), _lib.CIS_F32 if q.dtype == torch.float32 else _lib.CIS_F64, nq, k, 0, 0,
+                       rows.data_ptr(), dists.data_ptr(), torch.cuda.current_stream(q.device).cuda_stream))
         table = self.row_ids().cpu().numpy()
         rows, dists = rows.cpu().numpy(), dists.cpu().numpy()
         if table.shape[0] == 0:

@@ -351,6 +351,21 @@ int cis_rerank_select_merged_dev(const int64_t* d_ids, const double* d_adc, cons
                                  const double* d_true, int64_t n_true, int nb, int max_returned, int use_th, double near_dup_th,
                                  int64_t* d_out_ids, double* d_out_dists, int32_t* d_out_src, int32_t* d_n_kept, void* stream);
 
+/* The two re-rank calls above on float16 feature rows (csrc/feat_half.hip; searcher_lopqhbase.py:864-912, :975-1017): d_feats is
+ * float16 [n_feats][D] (the view of a store made by cis_featstore_create_half), d_q stays float32 [nq][D]; D % 8 == 0 and both
+ * 16-byte aligned (anything else: CIS_EINVAL).  Every other argument, every check, the outputs and the padding are the sibling's.
+ * The distance: y = (float)h (exact), df = q - y and acc = fma(df, df, acc) in float32 (lane l of one wave owns the halves
+ * 8 (l + 64 t) .. + 7, t = 0, 1, ..., with one accumulator for its even and one for its odd elements, added at the end), the lanes
+ * fold with the __shfl_xor butterfly 32 ... 1, and the result is (double) of the correctly rounded float32 square root.  A NaN
+ * result and a result without a stored row keep the ADC distance (select) / are NaN (packed). */
+int cis_rerank_select_half_dev(const void* d_feats, int64_t n_feats, int D, const int64_t* d_map_keys, const int64_t* d_map_rows,
+                               int64_t map_cap, const void* d_q, int nq, const int64_t* d_ids, const double* d_adc, int L, int nb,
+                               int max_returned, int use_th, double near_dup_th, int64_t* d_out_ids, double* d_out_dists,
+                               int32_t* d_out_src, int32_t* d_n_kept, void* stream);
+int cis_rerank_packed_half_dev(const void* d_feats, int64_t n_feats, int D, const int64_t* d_map_keys, const int64_t* d_map_rows,
+                               int64_t map_cap, const void* d_q, int nq, const cis_hit* d_recs, int64_t n_rec,
+                               const int64_t* d_off /* [nq] */, const int32_t* d_cnt /* [nq] */, int nb, double* d_true, void* stream);
+
 /* A feature store that lives in HBM and changes by kernels (csrc/feat_store.hip): the `put` and the fetch of the reference's
  * HBase feature table (hbase_indexer_minimal.py:779-831) for the exact re-rank above, addressed by the index's device ids.  The
  * store owns a feature matrix [rows][D] in f_dtype (4 = float32, 8 = float64), the row -> id column, and an id -> row table with
@@ -383,9 +398,17 @@ int cis_rerank_select_merged_dev(const int64_t* d_ids, const double* d_adc, cons
  * gives row -1 and a zero-filled feature row.
  *
  * cis_featstore_view: borrowed device pointers for cis_rerank_select_dev, cis_idmap_lookup_dev and cis_exact_knn_dev (any output may
- * be NULL): the matrix, the id column [n], the table (keys, rows, cap) and n.  Any later put or reserve invalidates them. */
+ * be NULL): the matrix, the id column [n], the table (keys, rows, cap) and n.  Any later put or reserve invalidates them.
+ *
+ * cis_featstore_create_half (hbase_indexer_minimal.py:779-831 as well): a store whose rows are float16 in HBM, 2 D bytes each, behind a
+ * float32 interface; D % 8 == 0 (anything else: CIS_EINVAL; cis_featstore_create with f_dtype = 2 stays CIS_EINVAL too).  Every call
+ * above works on such a handle: put reads float32 rows and rounds them to nearest even on the way in (subnormals kept, overflow to
+ * +-inf, NaN to NaN: numpy's astype(float16) bit for bit), get and rows write float32, the stored halves widened (so a row read back
+ * is the ROUNDED row), remove moves the float16 rows, and the view hands out the float16 matrix: for cis_rerank_select_half_dev,
+ * cis_rerank_packed_half_dev and cis_exact_knn_half_dev. */
 typedef struct cis_featstore cis_featstore;
 int cis_featstore_create(cis_featstore** out, int D, int f_dtype, int64_t reserve_rows);
+int cis_featstore_create_half(cis_featstore** out, int D, int64_t reserve_rows);
 void cis_featstore_destroy(cis_featstore* fs);
 int64_t cis_featstore_size(cis_featstore* fs);
 int cis_featstore_reserve(cis_featstore* fs, int64_t rows, void* stream);
@@ -408,9 +431,13 @@ int cis_featstore_view(cis_featstore* fs, const void** d_feats, const int64_t** 
  * base = first row of the chunk.  k <= 1024 (CIS_EUNSUPPORTED above).  m1 == 0 or m2 == 0 is CIS_OK.  A NaN distance ranks after
  * every number.  The calls share one process-wide workspace: they must not overlap on two streams or threads.
  * cis_exact_knn_set_mode: 0 = float32 matrix-core prefilter with exact re-check (default), 1 = the exact-only path for every query
- * (tests; both give the same answer). */
+ * (tests; both give the same answer).
+ * cis_exact_knn_half_dev (lopq/lopq/eval.py:7-38 as well): cis_exact_knn_dev on float16 data [m2][d] (the view of a half feature
+ * store); the chain runs on the data widened to float64, i.e. scipy's value for data.astype(float64).  Same kernels, same bound. */
 int cis_exact_knn_dev(const void* d_data, int data_dtype, int64_t m2, int d, const void* d_q, int q_dtype, int m1, int k,
                       int64_t base, int accumulate, int64_t* d_idx, double* d_dist, void* stream);
+int cis_exact_knn_half_dev(const void* d_data /* f16 [m2][d] */, int64_t m2, int d, const void* d_q, int q_dtype, int m1, int k,
+                           int64_t base, int accumulate, int64_t* idx, double* dist, void* stream);
 int cis_exact_knn(const void* data, int data_dtype, int64_t m2, int d, const void* q, int q_dtype, int m1, int k, int64_t base,
                   int accumulate, int64_t* idx, double* dist);
 int cis_exact_knn_set_mode(int mode);

@@ -16,6 +16,13 @@ search result; `gathered_over_peak` is nq x nb x D x 4 bytes over that time as a
 gathers, not a bound: rows repeat across queries and may come from cache.
 
     python tools/bench_rerank.py [--out profiles/rerank_dev.txt] [--commit ID] [--small]
+
+--storage f16: the fused kernel alone on float16 rows (csrc/feat_half.hip, k_rerank_select_half) beside the float32 kernel, on the
+same search result: a float32 FeatureStore and a FeatureStore(storage=torch.float16) hold the same rows (rounded to float16), the two
+kernels alternate in one process, and five such runs are reported, each figure the median of repetitions adding up to >= 0.5 s.
+Exit status 1 unless every float16 run at D = 4096 lies below every float32 run.
+
+    python tools/bench_rerank.py --storage f16 [--out profiles/rerank_half.txt]
 """
 import argparse
 import json
@@ -83,6 +90,55 @@ def same(host, dev, nq):
     return True
 
 
+def storage_leg(args, dev, commit):
+    import torch
+    from columbiaimagesearch_amd.rerank import FeatureStore
+    lines, ok = [], True
+    for fixture, gen, n, chunk_n in (("c4", "descriptor", 1_000_000, 125_000), ("c3full", "relu_mixture", 200_000, 25_000)):
+        if args.small:
+            n, chunk_n = n // 8, chunk_n // 8
+        s, feats, q = build(fixture, gen, n, chunk_n, dev)
+        D = int(feats.shape[1])
+        stores = (FeatureStore(D, torch.float32, reserve=n), FeatureStore(D, torch.float32, reserve=n, storage=torch.float16))
+        for a in range(0, n, chunk_n):
+            ids = torch.arange(a, a + chunk_n, dtype=torch.int64, device=dev)
+            rounded = feats[a:a + chunk_n].half().float()
+            for st in stores:
+                st.put_dev(ids, rounded)
+        del feats
+        r = s.search_batch_dev(q, quota=QUOTA, limit=LIMIT)
+        outs = [st.rerank_dev(q, r["ids"], r["dists"], rerank_nb=LIMIT) for st in stores]
+        same_ids = bool((outs[0]["ids"] == outs[1]["ids"]).all().item())
+        worst = float(((outs[0]["dists"] - outs[1]["dists"]).abs() / outs[0]["dists"].clamp_min(1e-30)).nan_to_num(0.0).max().item())
+        fns = [lambda st=st, o=o: st.rerank_dev(q, r["ids"], r["dists"], rerank_nb=LIMIT, out=o) for st, o in zip(stores, outs)]
+        runs = [timed_alternating(fns, max_reps=20000) for _ in range(5)]  # (a 0.2 ms kernel needs 2500 repetitions for 0.5 s)
+        t32, t16 = [run[0][0] for run in runs], [run[1][0] for run in runs]
+        gathered = float(NQ) * LIMIT * D
+        line = {"features": [n, D], "nq": NQ, "rerank_nb": LIMIT, "float32_kernel_s": t32, "float16_kernel_s": t16,
+                "float32_over_float16_medians": sorted(t32)[2] / sorted(t16)[2], "every_float16_run_below_every_float32_run": max(t16) < min(t32),
+                "float32_gathered_bytes_per_s": gathered * 4 / sorted(t32)[2], "float16_gathered_bytes_per_s": gathered * 2 / sorted(t16)[2],
+                "float32_gathered_over_peak_8TBs": gathered * 4 / sorted(t32)[2] / HBM_PEAK,
+                "float16_gathered_over_peak_8TBs": gathered * 2 / sorted(t16)[2] / HBM_PEAK, "reps_per_run": [runs[0][0][1], runs[0][1][1]],
+                "same_order": same_ids, "largest_relative_distance_difference": worst, "commit": commit, "device": torch.cuda.get_device_name(0)}
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+        ok = ok and (D != 4096 or line["every_float16_run_below_every_float32_run"])
+        for st in stores:
+            st.close()
+        s.close()
+        del s, q, stores
+        torch.cuda.empty_cache()
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("# tools/bench_rerank.py --storage f16: the fused re-rank kernel alone on one search result of %d queries, rerank_nb = %d, on\n"
+                    "# float32 rows (k_rerank_select) and on the same rows as float16 (k_rerank_select_half), alternating in one process; five\n"
+                    "# runs, each figure the median of repetitions adding up to >= 0.5 s, HIP events; gathered = nq x nb x D x 4 or 2 bytes.\n"
+                    % (NQ, LIMIT))
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
+    return 0 if ok else 1
+
+
 def main():
     import torch
     from columbiaimagesearch_amd.rerank import ResidentFeatures
@@ -90,6 +146,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--commit", default=None)
     ap.add_argument("--small", action="store_true", help="1/8 of the rows (a quick look)")
+    ap.add_argument("--storage", default=None, choices=["f16"], help="time the re-rank kernel on float16 rows beside the float32 kernel")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     commit = args.commit
@@ -99,6 +156,8 @@ def main():
             commit = subprocess.check_output(["git", "-C", REPO, "rev-parse", "--short", "HEAD"], stderr=subprocess.DEVNULL).decode().strip()
         except Exception:
             commit = "unknown"
+    if args.storage:
+        return storage_leg(args, dev, commit)
     lines = []
     for fixture, gen, n, chunk_n in (("c4", "descriptor", 1_000_000, 125_000), ("c3full", "relu_mixture", 200_000, 25_000)):
         if args.small:

@@ -13,6 +13,7 @@ KEYS = ("vgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_f
 def demangle(names):
     try:
         out = subprocess.run(["c++filt"] + names, capture_output=True, text=True, check=True).stdout.split("\n")[:len(names)]
+        out = [n.replace("(anonymous namespace)::", "") for n in out]  # (its bracket is no argument list)
         return [re.sub(r"^void ", "", re.sub(r"\(.*", "", n)) for n in out]  # template arguments tell the instantiations apart
     except (OSError, subprocess.CalledProcessError):
         return names
