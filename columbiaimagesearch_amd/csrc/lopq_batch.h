@@ -15,6 +15,19 @@ static const int GRP_SUB = 32;
 
 static const int PLAN_PAR_STAGE = 4096; // d0 / d1 staged in LDS: the kernel takes V <= 4096
 
+// What the counting pass of the small-V front end (k_front_small) leaves for the emit pass (k_emit_rec): the visited cells that hold
+// candidates, in visit order, so that the frontier is walked once.  VIS_CAP: at V = 16 and quota 10000 the queries of C4 / C2 / C3
+// visit one to three cells (C4: 40 834 candidates per query in cells of ~39 000), and a walk over V <= 64 that needs more than eight
+// non-empty cells is an index of small cells; such a query is flagged and k_emit_rec walks it again, which costs what it cost before.
+// Eight records are 256 bytes per query: 2 MB for a batch of 8192.
+static const int VIS_CAP = 8;
+struct VisRec {
+    int rank;         // visit rank of the cell (empty cells count)
+    uint16_t bi, bj;  // its ranks in the two coarse lists
+    int cell, nch;    // c0 * V + c1; chunks of seg_max candidates
+    int64_t ls, ll;   // [ls, ls + ll): its candidates on this shard
+};
+
 // ---- front end: LOPQ-space queries, coarse type, the rank workspaces (the batch search and the owner walk of the routed search) ----
 struct Front {
     const void* xc;  // the queries as the coarse quantizers read them
@@ -63,7 +76,8 @@ struct Batch {
     int64_t *item_off, *tab_off, *totals;
     unsigned long long* qbound;  // per query: cross-cell bound of the scan
     int *grp_cur, *grp_base;     // cursors and exclusive scan of the table groups
-    int* plan_fb;                // k_plan_par: per-query fall-back flags
+    int* plan_fb;                // k_plan_par, k_front_small: [nq] flags (the emit pass walks this query again), then [nq] listed cells
+    VisRec* vis_rec;             // k_front_small: [nq][VIS_CAP]
     uint64_t* vis_list;
     int vis_cap;
     unsigned long long* plan_hint;
@@ -108,7 +122,7 @@ int front_prepare(cis_index* ix, const void* dQ, int q_dtype, int nq, hipStream_
 // coarse distances, rank and the counting pass of the multisequence walk (CT: float or double, by Front::ct)
 template <typename CT>
 int front_count(Batch& b, const Route& r);
-// CIS_DEBUG_PLAN: how many queries of the batch the sort-based plan handed to the frontier walk
+// CIS_DEBUG_PLAN: how many queries of the batch the counting pass (k_plan_par, k_front_small) handed to the emitting frontier walk
 int dump_plan_fallbacks(const Batch& b);
 // exclusive scan of the plan; then the totals that size the rest of the batch
 int plan_totals(Batch& b, const Route& r);

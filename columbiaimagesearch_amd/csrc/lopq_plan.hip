@@ -35,7 +35,7 @@ __global__ void k_rank(const CT* __restrict__ dist /* [2][nq][V] */, int nq, int
 }
 
 // ---- the frontier walk, written once ---------------------------------------------------------------------------------------------
-// One wave per query walks the multi-index exactly like lopq/lopq/search.py:58-82.  With two
+// One wave per query (a part of a wave in k_front_small) walks the multi-index exactly like lopq/lopq/search.py:58-82.  With two
 // splits the traversed set is a Young diagram: t[i] cells taken in rank-row i; the reference's heap
 // holds (i, t[i]) for rows with t[i] < V and (i == 0 or t[i-1] > t[i]) and pops the smallest
 // (dist, i, j) with dist = d0[i] + d1[j] rounded in the coarse compute type.
@@ -44,13 +44,13 @@ __global__ void k_rank(const CT* __restrict__ dist /* [2][nq][V] */, int nq, int
 static const uint32_t WALK_NONE = ~0u;
 
 // One step: the frontier's minimum over rows [0, rows), key = (dist bits, i, j) -> i << 16 | j, the same in every lane; WALK_NONE
-// when the frontier is empty (cannot happen before all cells are visited).  FIRST_ALONE: skip the reduction while rows == 1 -- only
-// lane 0 holds a candidate then, so the result is the same (k_front_small, whose walks are a few steps long, is compiled with it).
-template <typename CT, bool FIRST_ALONE>
-static __device__ __forceinline__ uint32_t walk_step(const CT* d0, const CT* d1, const int* t, int rows, int V, int lane) {
+// when the frontier is empty (cannot happen before all cells are visited).  `width` lanes walk one query (a power of two; `lane` is
+// the lane's index among them): the whole wave in the one-wave kernels, a part of it in k_front_small (rows <= V <= width there).
+template <typename CT>
+static __device__ __forceinline__ uint32_t walk_step(const CT* d0, const CT* d1, const int* t, int rows, int V, int lane, int width) {
     uint64_t bk = ~0ull;
     uint32_t bij = WALK_NONE;
-    for (int i = lane; i < rows; i += 64) {
+    for (int i = lane; i < rows; i += width) {
         const int j = t[i];
         if (j >= V) continue;
         if (i > 0 && t[i - 1] <= j) continue;
@@ -59,39 +59,38 @@ static __device__ __forceinline__ uint32_t walk_step(const CT* d0, const CT* d1,
         const uint32_t ij = ((uint32_t)i << 16) | (uint32_t)j;
         if (kb < bk || (kb == bk && ij < bij)) { bk = kb; bij = ij; }
     }
-    if (!FIRST_ALONE || rows > 1) {  // wave-uniform
 #pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const uint64_t ok = __shfl_xor(bk, off);
-            const uint32_t oij = __shfl_xor(bij, off);
-            if (ok < bk || (ok == bk && oij < bij)) { bk = ok; bij = oij; }
-        }
-    } else {
-        bij = (uint32_t)__builtin_amdgcn_readfirstlane((int)bij);
+    for (int off = width >> 1; off > 0; off >>= 1) {
+        const uint64_t ok = __shfl_xor(bk, off);
+        const uint32_t oij = __shfl_xor(bij, off);
+        if (ok < bk || (ok == bk && oij < bij)) { bk = ok; bij = oij; }
     }
     return bij;
 }
 
-// The cell (bi, bj) leaves the frontier; rows [0, rows) can be on it.
+// The cell (bi, bj) leaves the frontier; rows [0, rows) can be on it.  SUB: the walkers of a query are part of one wave of a larger
+// workgroup (k_front_small) -- the wave's LDS accesses are in program order, and no barrier may sit in a loop whose trip count differs
+// from query to query.
+template <bool SUB>
 static __device__ __forceinline__ void walk_advance(int* t, int& rows, int V, int lane, int bi, int bj) {
-    __syncthreads();
+    if constexpr (SUB) wave_lds_sync(); else __syncthreads();
     if (lane == 0) t[bi] = bj + 1;
     if (bi + 2 > rows) rows = (bi + 2 < V) ? bi + 2 : V;
-    __syncthreads();
+    if constexpr (SUB) wave_lds_sync(); else __syncthreads();
 }
 
 // The walk up to the quota (search.py:128-133: the test follows the append, so one cell is always visited): visit(rank, bi, bj, cell,
 // gc, ls, ll) for every cell in visit order -- gc its size over all shards, [ls, ls + ll) its candidates on this shard (LISTS; else
 // only gcount is read and both are 0).  Returns the number of visited cells.
-template <typename CT, bool FIRST_ALONE, bool LISTS, typename Visit>
-static __device__ __forceinline__ int walk_quota(const CT* d0, const CT* d1, const uint16_t* o0, const uint16_t* o1, int* t, int V, int lane,
+template <typename CT, bool SUB, bool LISTS, typename Visit>
+static __device__ __forceinline__ int walk_quota(const CT* d0, const CT* d1, const uint16_t* o0, const uint16_t* o1, int* t, int V, int lane, int width,
                                                  const int64_t* __restrict__ gcount, const int64_t* __restrict__ loff, int64_t quota, Visit visit) {
     int visited = 0;
     int64_t retrieved = 0;
     int rows = 1;
     const int64_t total_cells = (int64_t)V * V;
     while ((int64_t)visited < total_cells) {
-        const uint32_t bij = walk_step<CT, FIRST_ALONE>(d0, d1, t, rows, V, lane);
+        const uint32_t bij = walk_step<CT>(d0, d1, t, rows, V, lane, width);
         if (bij == WALK_NONE) break;
         const int bi = (int)(bij >> 16), bj = (int)(bij & 0xffff);
         const int c0 = o0[bi], c1 = o1[bj];
@@ -105,7 +104,7 @@ static __device__ __forceinline__ int walk_quota(const CT* d0, const CT* d1, con
         visit(visited, bi, bj, cell, gc, ls, ll);
         visited += 1;
         retrieved += gc;
-        walk_advance(t, rows, V, lane, bi, bj);
+        walk_advance<SUB>(t, rows, V, lane, bi, bj);
         if (retrieved >= quota) break;
     }
     return visited;
@@ -118,13 +117,13 @@ static __device__ __forceinline__ void count_table_group(int* __restrict__ grp_c
 
 // What a counting pass of the walk leaves: the query's PlanOut and its table groups (ranks [0, max_i] and [0, max_j] of the two lists).
 static __device__ __forceinline__ void walk_count_out(PlanOut* __restrict__ plan, int* __restrict__ grp_cnt, const uint16_t* o0, const uint16_t* o1,
-                                                      int V, int q, int lane, int visited, int n_items, int max_i, int max_j, int64_t ncand) {
+                                                      int V, int q, int lane, int width, int visited, int n_items, int max_i, int max_j, int64_t ncand) {
     if (lane == 0) {
         PlanOut p;
         p.visited = visited; p.n_items = n_items; p.ntab0 = max_i + 1; p.ntab1 = max_j + 1; p.ncand = ncand;
         plan[q] = p;
     }
-    for (int i = lane; i < max_i + 1 + max_j + 1; i += 64)
+    for (int i = lane; i < max_i + 1 + max_j + 1; i += width)
         count_table_group(grp_cnt, i <= max_i ? (int)o0[i] : V + (int)o1[i - (max_i + 1)], q);
 }
 
@@ -142,6 +141,21 @@ static __device__ __forceinline__ void emit_chunks(WorkItem* __restrict__ dst, i
         const int64_t rem = ll - (int64_t)ch * seg_max;
         it.len = (int)(rem < seg_max ? rem : seg_max);
         dst[ch] = it;
+    }
+}
+
+// The table descriptors of one query, ranks [0, nt0) and [0, nt1) of the two lists, and their places in the groups' lists.
+static __device__ __forceinline__ void emit_tabs(TabDesc* __restrict__ tabs, int* __restrict__ tab_order, const int* __restrict__ grp_base,
+                                                 int* __restrict__ grp_cur, const uint16_t* o0, const uint16_t* o1, int V, int q, int64_t tbase,
+                                                 int nt0, int nt1, int lane, int step) {
+    for (int i = lane; i < nt0 + nt1; i += step) {
+        TabDesc td;
+        td.q = q; td.pad = 0;
+        if (i < nt0) { td.split = 0; td.cluster = o0[i]; }
+        else { td.split = 1; td.cluster = o1[i - nt0]; }
+        tabs[tbase + i] = td;
+        const int g = (td.split * V + td.cluster) * GRP_SUB + (q % GRP_SUB);
+        tab_order[grp_base[g] + atomicAdd(&grp_cur[g], 1)] = (int)(tbase + i);  // order inside a group does not matter
     }
 }
 
@@ -175,7 +189,7 @@ __global__ __launch_bounds__(64) void k_plan(const CT* __restrict__ sorted, cons
         tbase = tab_off[q];
         ntab0 = plan[q].ntab0;
     }
-    const int visited = walk_quota<CT, false, true>(d0, d1, o0, o1, t, V, lane, gcount, loff, quota,
+    const int visited = walk_quota<CT, false, true>(d0, d1, o0, o1, t, V, lane, 64, gcount, loff, quota,
                                                     [&](int rank, int bi, int bj, int64_t cell, int64_t, int64_t ls, int64_t ll) {
         if (ll > 0) {
             const int nch = (int)((ll + seg_max - 1) / seg_max);
@@ -186,51 +200,120 @@ __global__ __launch_bounds__(64) void k_plan(const CT* __restrict__ sorted, cons
             max_j = bj > max_j ? bj : max_j;
         }
     });
-    if (!EMIT) {
-        walk_count_out(plan, grp_cnt, o0, o1, V, q, lane, visited, n_items, max_i, max_j, ncand);
-    } else {
-        const int nt0 = plan[q].ntab0, nt1 = plan[q].ntab1;
-        for (int i = lane; i < nt0 + nt1; i += 64) {
-            TabDesc td;
-            td.q = q; td.pad = 0;
-            if (i < nt0) { td.split = 0; td.cluster = o0[i]; }
-            else { td.split = 1; td.cluster = o1[i - nt0]; }
-            tabs[tbase + i] = td;
-            const int g = (td.split * V + td.cluster) * GRP_SUB + (q % GRP_SUB);
-            tab_order[grp_base[g] + atomicAdd(&grp_cur[g], 1)] = (int)(tbase + i);  // order inside a group does not matter
+    if (!EMIT) walk_count_out(plan, grp_cnt, o0, o1, V, q, lane, 64, visited, n_items, max_i, max_j, ncand);
+    else emit_tabs(tabs, tab_order, grp_base, grp_cur, o0, o1, V, q, tbase, ntab0, plan[q].ntab1, lane, 64);
+}
+
+// The emit pass of the small-V front end, from the cells k_front_small recorded: no second walk.  EMIT_LPQ lanes per query, a lane
+// per chunk of a cell (a C4 query has ~40 work items in one to three cells and two to four tables: one wave per query, as k_plan<CT,
+// true> runs, stores from a few lanes behind a serial walk).  All VIS_CAP records are requested at once, before the count says how
+// many hold something: one round trip, not one per cell.  A flagged query (more cells than a record holds) is walked again here, by
+// its EMIT_LPQ lanes, as k_plan<CT, true> would: the common batch has none, and pays no launch for them.
+static const int EMIT_LPQ = 16;
+template <typename CT>
+__global__ __launch_bounds__(256) void k_emit_rec(const VisRec* __restrict__ vis, const int* __restrict__ vis_fb /* [nq] flags, [nq] records */,
+                                                  const CT* __restrict__ sorted, const uint16_t* __restrict__ order,
+                                                  const int64_t* __restrict__ gcount, const int64_t* __restrict__ loff, int nq, int V,
+                                                  int64_t quota, int seg_max, const PlanOut* __restrict__ plan,
+                                                  const int64_t* __restrict__ item_off, const int64_t* __restrict__ tab_off,
+                                                  WorkItem* __restrict__ items, TabDesc* __restrict__ tabs, const int* __restrict__ grp_base,
+                                                  int* __restrict__ grp_cur, int* __restrict__ tab_order) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];  // [256 / EMIT_LPQ][V]: frontiers of the queries walked again
+    const int slot = (int)(threadIdx.x / EMIT_LPQ), l = (int)(threadIdx.x % EMIT_LPQ);
+    const int q = (int)blockIdx.x * (256 / EMIT_LPQ) + slot;
+    if (q >= nq) return;
+    const int flagged = vis_fb[q], n_rec = vis_fb[nq + q];
+    const PlanOut pl = plan[q];
+    const int64_t ibase = item_off[q], tbase = tab_off[q];
+    const uint16_t* o0 = order + ((int64_t)q * 2 + 0) * V;
+    const uint16_t* o1 = order + ((int64_t)q * 2 + 1) * V;
+    if (!flagged) {
+        VisRec v[VIS_CAP];
+#pragma unroll
+        for (int r = 0; r < VIS_CAP; ++r) v[r] = vis[(int64_t)q * VIS_CAP + r];
+        int first = 0;
+#pragma unroll
+        for (int r = 0; r < VIS_CAP; ++r) {
+            if (r < n_rec) {
+                emit_chunks(items + ibase + first, q, v[r].rank, (int)(tbase + v[r].bi), (int)(tbase + pl.ntab0 + v[r].bj), v[r].cell, v[r].ls, v[r].ll,
+                            seg_max, v[r].nch, l, EMIT_LPQ);
+                first += v[r].nch;
+            }
         }
+    } else {
+        int* t = reinterpret_cast<int*>(smem) + slot * V;
+        for (int i = l; i < V; i += EMIT_LPQ) t[i] = 0;
+        wave_lds_sync();
+        int n_items = 0;
+        walk_quota<CT, true, true>(sorted + ((int64_t)q * 2 + 0) * V, sorted + ((int64_t)q * 2 + 1) * V, o0, o1, t, V, l, EMIT_LPQ, gcount, loff, quota,
+                                   [&](int rank, int bi, int bj, int64_t cell, int64_t, int64_t ls, int64_t ll) {
+            if (ll > 0) {
+                const int nch = (int)((ll + seg_max - 1) / seg_max);
+                emit_chunks(items + ibase + n_items, q, rank, (int)(tbase + bi), (int)(tbase + pl.ntab0 + bj), cell, ls, ll, seg_max, nch, l, EMIT_LPQ);
+                n_items += nch;
+            }
+        });
     }
+    emit_tabs(tabs, tab_order, grp_base, grp_cur, o0, o1, V, q, tbase, pl.ntab0, pl.ntab1, l, EMIT_LPQ);
 }
 
 // Fused front end for small coarse codebooks (V <= 64: BASELINE configs C1-C5): the exact coarse distances of k_sqdist_rows2
 // (lopq/lopq/search.py:39 -> lopq/lopq/utils.py:33-53 arithmetic: numpy's pairwise order, compute type CT), the ascending rank of
-// k_rank (np.argsort, ties to the lower index) and the counting pass of the multisequence walk (k_plan<CT, false>) in ONE launch, one
-// wave per query: the 2 V distances never leave the CU between the three steps (three launches and two round trips through L2 of
-// the [2][nq][V] arrays before).  `sorted` / `order` still go to global memory for the emit pass and the tables.
-template <typename CT>
-__global__ __launch_bounds__(64) void k_front_small(const CT* __restrict__ X /* [nq][D] */, int D, int h, const CT* __restrict__ Cs /* [2][V][h] */,
-                                                    PwProg prog, const int64_t* __restrict__ gcount, const int64_t* __restrict__ loff,
-                                                    int nq, int V, int64_t quota, int seg_max, uint16_t* __restrict__ order /* [nq][2][V] */,
-                                                    CT* __restrict__ sorted /* [nq][2][V] */, PlanOut* __restrict__ plan,
-                                                    int* __restrict__ grp_cnt /* zeroed by the previous batch's k_plan_scan */) {
+// k_rank (np.argsort, ties to the lower index) and the counting pass of the multisequence walk (k_plan<CT, false>) in ONE launch: the
+// 2 V distances never leave the CU between the three steps.  `sorted` / `order` still go to global memory for the tables and the
+// re-walk; the visited cells that hold candidates go to `vis` for the emit pass (k_emit_rec), which then walks nothing it has a list for.
+// G lanes per query (the power of two >= 2 V, at most 64: every lane computes a distance at V = 16, where one wave per query kept 32
+// idle), 64 / G queries per wave, four waves per workgroup.  STAGE: the workgroup copies the 2 V centroid rows to LDS once, rows
+// padded to h + 1 values so that the lanes' rows start in different banks (each lane read its own row from global memory before, at
+// a stride of h values, and every one-query workgroup fetched all 2 V h values again).  After the staging barrier the lanes of a
+// query only meet each other: their LDS traffic is ordered inside the wave (wave_lds_sync), and a query past nq just leaves.
+static const int FRONT_STAGE_MAX = 17 * 1024;  // staged bytes: float32 and float64 centroids of V = 16, h = 64 (8.1 / 16.3 KB)
+template <typename CT, bool STAGE>
+__global__ __launch_bounds__(256) void k_front_small(const CT* __restrict__ X /* [nq][D] */, int D, int h, const CT* __restrict__ Cs /* [2][V][h] */,
+                                                     PwProg prog, const int64_t* __restrict__ gcount, const int64_t* __restrict__ loff,
+                                                     int nq, int V, int G, int64_t quota, int seg_max, uint16_t* __restrict__ order /* [nq][2][V] */,
+                                                     CT* __restrict__ sorted /* [nq][2][V] */, PlanOut* __restrict__ plan,
+                                                     int* __restrict__ grp_cnt /* zeroed by the previous batch's k_plan_scan */,
+                                                     VisRec* __restrict__ vis /* [nq][VIS_CAP] */, int* __restrict__ vis_fb /* [nq] flags, [nq] records */) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    uint64_t* sb = reinterpret_cast<uint64_t*>(smem);            // [2V] distance bits
+    const int hs = h + 1;
+    CT* sc = reinterpret_cast<CT*>(smem);  // STAGE: [2 V][h + 1]
+    const size_t sc_bytes = STAGE ? (((size_t)2 * V * hs * sizeof(CT) + 15) & ~(size_t)15) : 0;
+    if constexpr (STAGE) {
+        for (int i = threadIdx.x; i < 2 * V * h; i += 256) {
+            const int r = i / h;
+            sc[r * hs + (i - r * h)] = Cs[i];
+        }
+        __syncthreads();
+    }
+    const int QW = 64 / G;
+    const int wlane = threadIdx.x & 63, grp = wlane / G, lane = wlane & (G - 1);
+    const int slot = (threadIdx.x >> 6) * QW + grp;
+    const int q = blockIdx.x * 4 * QW + slot;
+    if (q >= nq) return;
+    uint64_t* sb = reinterpret_cast<uint64_t*>(smem + sc_bytes + (size_t)slot * V * 40);  // [2V] distance bits
     CT* sd = reinterpret_cast<CT*>(sb + 2 * V);                  // [2][V] ascending distances
     uint16_t* so = reinterpret_cast<uint16_t*>(sb + 4 * V);      // [2][V] cluster of every rank (8 bytes reserved per value of sd)
     int* t = reinterpret_cast<int*>(so + 2 * V);                 // [V] frontier
-    const int q = blockIdx.x, lane = threadIdx.x;
     const CT* xr = X + (int64_t)q * D;
-    for (int e = lane; e < 2 * V; e += 64) {
+    for (int e = lane; e < 2 * V; e += G) {
         const int s = e / V, c = e - s * V;
         const CT* x = xr + s * h;
-        const CT* cc = Cs + ((int64_t)s * V + c) * h;
-        auto elem = [&](int i) -> CT { const CT df = x[i] - cc[i]; return df * df; };
-        const CT d = pw_sum<CT>(prog, elem);
+        CT d;
+        if constexpr (STAGE) {
+            const CT* cc = sc + e * hs;
+            auto elem = [&](int i) -> CT { const CT df = x[i] - cc[i]; return df * df; };
+            d = pw_sum<CT>(prog, elem);
+        } else {
+            const CT* cc = Cs + ((int64_t)s * V + c) * h;
+            auto elem = [&](int i) -> CT { const CT df = x[i] - cc[i]; return df * df; };
+            d = pw_sum<CT>(prog, elem);
+        }
         sb[e] = f2bits(d);
     }
-    for (int i = lane; i < V; i += 64) t[i] = 0;
-    __syncthreads();
-    for (int e = lane; e < 2 * V; e += 64) {
+    for (int i = lane; i < V; i += G) t[i] = 0;
+    wave_lds_sync();
+    for (int e = lane; e < 2 * V; e += G) {
         const int s = e / V, v = e - s * V;
         const uint64_t mine = sb[e];
         int r = 0;
@@ -246,24 +329,36 @@ __global__ __launch_bounds__(64) void k_front_small(const CT* __restrict__ X /* 
         order[((int64_t)q * 2 + s) * V + r] = (uint16_t)v;
         sorted[((int64_t)q * 2 + s) * V + r] = d;
     }
-    __syncthreads();
+    wave_lds_sync();
     const CT* d0 = sd;
     const CT* d1 = sd + V;
     const uint16_t* o0 = so;
     const uint16_t* o1 = so + V;
-    // the counting pass of k_plan (same frontier walk, inputs in LDS)
-    int n_items = 0, max_i = -1, max_j = -1;
+    // the counting pass of k_plan (same frontier walk, inputs in LDS; rows <= V <= G), which also lists what the emit pass needs
+    int n_items = 0, max_i = -1, max_j = -1, n_rec = 0;
     int64_t ncand = 0;
-    const int visited = walk_quota<CT, true, true>(d0, d1, o0, o1, t, V, lane, gcount, loff, quota,
-                                                   [&](int, int bi, int bj, int64_t, int64_t, int64_t, int64_t ll) {
+    VisRec* vr = vis + (int64_t)q * VIS_CAP;
+    const int visited = walk_quota<CT, true, true>(d0, d1, o0, o1, t, V, lane, G, gcount, loff, quota,
+                                                   [&](int rank, int bi, int bj, int64_t cell, int64_t, int64_t ls, int64_t ll) {
         if (ll > 0) {
-            n_items += (int)((ll + seg_max - 1) / seg_max);
+            const int nch = (int)((ll + seg_max - 1) / seg_max);
+            if (lane == 0 && n_rec < VIS_CAP) {
+                VisRec v;
+                v.rank = rank; v.bi = (uint16_t)bi; v.bj = (uint16_t)bj; v.cell = (int)cell; v.nch = nch; v.ls = ls; v.ll = ll;
+                vr[n_rec] = v;
+            }
+            n_rec += 1;
+            n_items += nch;
             ncand += ll;
             max_i = bi > max_i ? bi : max_i;
             max_j = bj > max_j ? bj : max_j;
         }
     });
-    walk_count_out(plan, grp_cnt, o0, o1, V, q, lane, visited, n_items, max_i, max_j, ncand);
+    if (lane == 0) {
+        vis_fb[q] = n_rec > VIS_CAP ? 1 : 0;  // more cells than the record holds: k_emit_rec walks this query again
+        vis_fb[nq + q] = n_rec;
+    }
+    walk_count_out(plan, grp_cnt, o0, o1, V, q, lane, G, visited, n_items, max_i, max_j, ncand);
 }
 
 // The same plan for indexes with thousands of coarse clusters (the reference's release configurations use V = 2048 / 4096:
@@ -856,7 +951,7 @@ __global__ __launch_bounds__(64) void k_multiseq_list(const CT* __restrict__ sor
     __syncthreads();
     int rows = 1;
     for (int n = 0; n < max_cells; ++n) {
-        const uint32_t bij = walk_step<CT, false>(d0, d1, t, rows, V, lane);
+        const uint32_t bij = walk_step<CT>(d0, d1, t, rows, V, lane, 64);
         if (bij == WALK_NONE) break;
         const int bi = (int)(bij >> 16), bj = (int)(bij & 0xffff);
         if (lane == 0) {
@@ -864,7 +959,7 @@ __global__ __launch_bounds__(64) void k_multiseq_list(const CT* __restrict__ sor
             cells[((int64_t)q * max_cells + n) * 2 + 1] = o1[bj];
             dists[(int64_t)q * max_cells + n] = (double)(CT)(d0[bi] + d1[bj]);
         }
-        walk_advance(t, rows, V, lane, bi, bj);
+        walk_advance<false>(t, rows, V, lane, bi, bj);
     }
 }
 
@@ -1322,14 +1417,14 @@ static void dump_plan_dbg(int nq) {
 }
 #endif
 
-// CIS_DEBUG_PLAN: how many queries of the batch the sort-based plan handed to the frontier walk
+// CIS_DEBUG_PLAN: how many queries of the batch the counting pass (k_plan_par, k_front_small) handed to the emitting frontier walk
 int dump_plan_fallbacks(const Batch& b) {
     std::vector<int> fbh(b.nq);
     CIS_CHECK_HIP(hipMemcpyAsync(fbh.data(), b.plan_fb, (size_t)b.nq * sizeof(int), hipMemcpyDeviceToHost, b.st));
     CIS_CHECK_HIP(hipStreamSynchronize(b.st));
     int nfb = 0;
     for (int i = 0; i < b.nq; ++i) nfb += fbh[i] != 0;
-    fprintf(stderr, "[cis] k_plan_par: %d of %d queries fall back to the frontier walk (quota %lld)\n", nfb, b.nq, (long long)b.quota);
+    fprintf(stderr, "[cis] %s: %d of %d queries fall back to the frontier walk (quota %lld)\n", b.vis_rec ? "k_front_small" : "k_plan_par", nfb, b.nq, (long long)b.quota);
     return CIS_OK;
 }
 
@@ -1357,9 +1452,19 @@ int front_count(Batch& b, const Route& r) {
     CT* sorted = ix->w_sorted.as<CT>();
     if (r.fused_front) {
         // coarse distances + rank + counting pass of the multisequence walk in one launch (k_front_small)
-        const size_t flds = (size_t)V * (32 + 4 + 4);
-        hipLaunchKernelGGL(k_front_small<CT>, dim3(nq), dim3(64), flds, st, (const CT*)b.f.xc, m->D, m->h, coarse_centroids(m, CT()), m->prog_h,
-                           ix->gcount_ptr(), ix->loff_ptr(), nq, V, b.quota, r.seg_max, order, sorted, b.plan, b.f.grp_cnt);
+        int G = 2;  // lanes per query
+        while (G < 2 * V && G < 64) G <<= 1;
+        const int qpb = 4 * (64 / G);  // queries per workgroup
+        const size_t staged = (((size_t)2 * V * (m->h + 1) * sizeof(CT) + 15) & ~(size_t)15);
+        const bool stage = staged <= (size_t)FRONT_STAGE_MAX;
+        const size_t flds = (stage ? staged : 0) + (size_t)qpb * V * (32 + 4 + 4);
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3((unsigned)ceil_div(nq, qpb)), dim3(256), flds, st, (const CT*)b.f.xc, m->D, m->h, coarse_centroids(m, CT()),
+                               m->prog_h, ix->gcount_ptr(), ix->loff_ptr(), nq, V, G, b.quota, r.seg_max, order, sorted, b.plan, b.f.grp_cnt, b.vis_rec,
+                               b.plan_fb);
+        };
+        if (stage) launch(k_front_small<CT, true>);
+        else launch(k_front_small<CT, false>);
         return CIS_OK;
     }
     CIS_TRY(cis_launch_sqdist_both(m, b.f.xc, b.f.ct, nq, ix->w_cd.p, st));
@@ -1388,6 +1493,13 @@ void emit_plan(Batch& b, const Route& r) {
     const int V = m->V, nq = b.nq;
     const uint16_t* order = ix->w_order.as<uint16_t>();
     const CT* sorted = ix->w_sorted.as<CT>();
+    if (r.fused_front) {  // k_front_small listed the cells; a query whose list overflowed is walked again inside the same launch
+        const int qpb = 256 / EMIT_LPQ;
+        hipLaunchKernelGGL(k_emit_rec<CT>, dim3((unsigned)ceil_div(nq, qpb)), dim3(256), (size_t)qpb * V * sizeof(int), st, b.vis_rec, b.plan_fb, sorted, order,
+                           ix->gcount_ptr(), ix->loff_ptr(), nq, V, b.quota, r.seg_max, b.plan, b.item_off, b.tab_off, b.items, b.tabs, b.grp_base,
+                           b.grp_cur, b.tab_order);
+        return;
+    }
     if (r.par_plan)
         hipLaunchKernelGGL((k_plan_par<CT, true>), dim3(nq), dim3(256), 0, st, sorted, order, ix->gcount_ptr(), ix->loff_ptr(), nq, V, b.quota,
                            r.seg_max, b.plan, b.item_off, b.tab_off, b.items, b.tabs, nullptr, b.grp_base, b.grp_cur, b.tab_order, b.vis_list,
@@ -1583,7 +1695,7 @@ __global__ __launch_bounds__(64) void k_plan_owners(const CT* __restrict__ sorte
     for (int i = lane; i < V; i += 64) t[i] = 0;
     __syncthreads();
     unsigned long long mk = 0ull;
-    const int visited = walk_quota<CT, false, false>(d0, d1, o0, o1, t, V, lane, gcount, nullptr, quota,
+    const int visited = walk_quota<CT, false, false>(d0, d1, o0, o1, t, V, lane, 64, gcount, nullptr, quota,
                                                      [&](int, int, int, int64_t cell, int64_t gc, int64_t, int64_t) {
         if (gc > 0) mk |= 1ull << (owner ? owner[cell] : (int)(cell % world));
     });

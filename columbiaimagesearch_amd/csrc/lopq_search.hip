@@ -3761,10 +3761,15 @@ static int search_batch(cis_index* ix, const void* dQ, int q_dtype, int nq, int6
         CIS_TRY(ix->w_vis.reserve((size_t)nq * b.vis_cap * 2 * sizeof(uint64_t)));
         b.plan_fb = ix->w_planfb.as<int>();
         b.vis_list = ix->w_vis.as<uint64_t>();
+    } else if (r.fused_front) {  // the cells k_front_small lists for k_emit_rec
+        CIS_TRY(ix->w_planfb.reserve((size_t)2 * nq * sizeof(int)));
+        CIS_TRY(ix->w_vis.reserve((size_t)nq * VIS_CAP * sizeof(VisRec)));
+        b.plan_fb = ix->w_planfb.as<int>();
+        b.vis_rec = ix->w_vis.as<VisRec>();
     }
     const bool f32 = b.f.ct == CIS_F32;
     CIS_TRY(f32 ? front_count<float>(b, r) : front_count<double>(b, r));
-    if (r.par_plan && getenv("CIS_DEBUG_PLAN")) CIS_TRY(dump_plan_fallbacks(b));
+    if ((r.par_plan || r.fused_front) && getenv("CIS_DEBUG_PLAN")) CIS_TRY(dump_plan_fallbacks(b));
     CIS_TRY(plan_totals(b, r));
     CIS_TRY(route_decide(b, &r));
     // 3. emit items + table list
