@@ -1323,8 +1323,7 @@ static void launch_conv(const ConvDesc& d, const float* in, const float* w, cons
     else if (npix <= 2048) {
         // fc layers.  32 x 128 tiles fill the chip at any batch, but every 32 rows stream the whole weight matrix again (batch 256: 8 x
         // 151 MB for fc6); from 64 rows up 64 x 128 tiles halve that (the tile shape does not change a sum's order: same bits)
-        const char* e = getenv("CIS_CNN_FC_TILE");
-        const int t = e ? atoi(e) : (npix >= 64 ? 1 : 0);
+        const int t = envsw::call<envsw::cnn_fc_tile>(npix >= 64 ? 1 : 0);
         if (t == 1) launch_conv_cfg<1, 2, 2, 2>(d, in, w, b, out, st);
         else if (t == 2) launch_conv_cfg<2, 2, 2, 2>(d, in, w, b, out, st);
         else if (t == 3) launch_conv_cfg<1, 1, 2, 2>(d, in, w, b, out, st);
@@ -1363,11 +1362,10 @@ static int conv_fill_chip(CnnWs* ws, ConvDesc d, const float* in, const LayerW& 
     const float* b = L.d_b;
     const int64_t npix = (int64_t)d.N * d.OH * d.OW;
     // the 3x3 / stride 1 / pad 1 layers with as many output as input channels at the two large spatial sizes: direct kernel
-    const bool no_direct = getenv("CIS_CNN_NO_DIRECT") != nullptr;  // read per call: A/B runs in one process
+    const bool no_direct = envsw::call<envsw::cnn_no_direct>();  // read per call: A/B runs in one process
     if (!no_direct && d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1 && d.groups == 1 && d.C == d.OC && d.sC == 1 && b != nullptr && L.d_w2 != nullptr &&
         d.runq == 0 && d.splitk == 1) {
-        const char* cfg_s = getenv("CIS_CNN_DIRECT_CFG");  // tile sweep (tools/check_dlib_direct.py)
-        const int cfg = cfg_s ? atoi(cfg_s) : 0;
+        const int cfg = envsw::call<envsw::cnn_direct_cfg>();  // tile sweep (tools/check_dlib_direct.py)
 #define CIS_DIRECT(C_, H_, W_, WM_, NWM_, NWN_) return launch_conv3x3_direct<C_, H_, W_, WM_, NWM_, NWN_>(in, L.d_w2, b, out, d.N, d.res, d.resC, d.relu, st)
         if (d.C == 32 && d.H == 35 && d.W == 35) {
             if (cfg == 1) CIS_DIRECT(32, 35, 35, 1, 8, 1);
@@ -1385,14 +1383,13 @@ static int conv_fill_chip(CnnWs* ws, ConvDesc d, const float* in, const LayerW& 
     const int64_t tiles = npix <= 2048 ? ceil_div(npix, 32) * ceil_div((int64_t)d.OCg, 128) : ceil_div(npix, 64) * ceil_div((int64_t)d.OCg, 64);
     const int nkt = d.K / 16;
     int splitk = 1;
-    static const bool off = getenv("CIS_CNN_NO_SPLITK") != nullptr;
+    const bool off = envsw::once<envsw::cnn_no_splitk>();
     while (!off && vec && d.OCg > 32 && tiles * splitk < 512 && splitk < 32 && nkt / (splitk * 2) >= 6) splitk *= 2;
     // the 128- and 256-channel maps (8x8 ... 3x3 per chip): 128 x 128 tiles (the kernel's most efficient shape) with K split until
     // the chip is full, instead of 64 x 64 tiles: 70 -> 66 us and 74 -> 64 us per layer at batch 256 (CIS_CNN_NO_BIGTILE: old choice)
-    if (!off && vec && !getenv("CIS_CNN_NO_BIGTILE") && d.OCg >= 128 && d.OCg % 128 == 0 && npix > 2048) {
+    if (!off && vec && !envsw::call<envsw::cnn_no_bigtile>() && d.OCg >= 128 && d.OCg % 128 == 0 && npix > 2048) {
         const int64_t t128 = ceil_div(npix, 128) * (d.OCg / 128);
-        const char* te = getenv("CIS_CNN_SPLIT_TARGET");
-        const int64_t target = te ? atoi(te) : 512;
+        const int64_t target = (int)envsw::call<envsw::cnn_split_target>();
         int s = 1;
         while (t128 * s < target && s < 32 && nkt / (s * 2) >= 6) s *= 2;
         if (t128 * s >= 512) splitk = s;
@@ -1419,7 +1416,7 @@ static int conv_fill_chip_bf16(CnnWs* ws, ConvDesc d, const float* in, const Lay
     CIS_REQUIRE(d.groups == 1 && d.sC == 1 && d.runq == 0 && d.splitk == 1 && d.ICg % 8 == 0 && d.OC % 4 == 0,
                 "16-bit convolution: channels-last, one group, channels a multiple of 8 (got %d -> %d)", d.C, d.OC);
     const int64_t npix = (int64_t)d.N * d.OH * d.OW;
-    if (!getenv("CIS_CNN_NO_DIRECT") && d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1 && d.C == d.OC && conv3x3_direct_bf16_serves(d.C, d.H, d.W))
+    if (!envsw::call<envsw::cnn_no_direct>() && d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1 && d.C == d.OC && conv3x3_direct_bf16_serves(d.C, d.H, d.W))
         return launch_conv3x3_direct_bf16(d.C, d.H, d.W, in, L.d_wh, L.d_b, out, d.N, d.res, d.resC, d.relu, ns, st);
     // K split as for the float32 kernel, counted in this kernel's stages of 32 k: while the tiles leave CUs idle and every K range keeps
     // at least 4 stages (128 k; floors of 2 and 9 stages moved the forward at batch 256 by no more than two processes of one setting
@@ -1644,9 +1641,8 @@ extern "C" int cis_cnn_conv3x3_dev(const float* d_in, const float* w, const floa
 // Test hook (tests/test_cnn_hip_parity.py): CIS_CNN_POISON=<mask> fills the workspaces (bit 0..4: act0, act1, act2, act3, part) with
 // 0xff bytes (NaN) before a forward.  A forward must not read what it has not written: results do not change under any mask.
 static int cnn_poison(CnnWs* ws, hipStream_t st) {
-    const char* e = getenv("CIS_CNN_POISON");
-    if (!e) return CIS_OK;
-    const int mask = atoi(e);
+    const int mask = envsw::call<envsw::cnn_poison>();
+    if (!mask) return CIS_OK;
     DevBuf* b[5] = {&ws->act0, &ws->act1, &ws->act2, &ws->act3, &ws->part};
     for (int i = 0; i < 5; ++i)
         if (((mask >> i) & 1) && b[i]->p) CIS_CHECK_HIP(hipMemsetAsync(b[i]->p, 0xff, b[i]->cap, st));
@@ -1667,16 +1663,16 @@ static int cnn_forward_dlib(cis_cnn* c, CnnWs* ws, const float* d_in, int n, flo
     float* T2 = ws->act3.as<float>();
     auto grid = [](int64_t total) { return dim3((unsigned)ceil_div(total, 256)); };
     bool pooled = false;
-    if (!getenv("CIS_CNN_NO_DIRECT7") && !getenv("CIS_CNN_NO_POOL7")) {
+    if (!envsw::call<envsw::cnn_no_direct7>() && !envsw::call<envsw::cnn_no_pool7>()) {
         // first layer AND the max pool behind it in one kernel (k_conv7x7s2_pool, round 5): the pooled 35 x 35 x 32 map goes to A
         hipLaunchKernelGGL(k_conv7x7s2_pool, dim3((unsigned)n * 12), dim3(256), 0, st, d_in, (const float*)c->dl[0].d_w, (const float*)c->dl[0].d_b, A, n,
                            122.782f, 117.001f, 104.298f);
         pooled = true;
     } else
-    if (!getenv("CIS_CNN_NO_DIRECT7")) {
+    if (!envsw::call<envsw::cnn_no_direct7>()) {
         // first layer: direct 7 x 7 / 2 convolution, normalisation + bias + ReLU fused (k_conv7x7s2_direct)
         // tiles per wave (the staged window and the weight registers serve 4 x that many tiles): 1 / 2 / 4 -> 161 / 141 / 133 us per 256 chips, forward 1.97 / 1.92 / 1.90 ms (profiles/r03r_dlib_first_layer.txt)
-        const int tpw = getenv("CIS_CNN_D7_TPW") ? atoi(getenv("CIS_CNN_D7_TPW")) : 4;
+        const int tpw = envsw::call<envsw::cnn_d7_tpw>();
         if (tpw == 1)
             hipLaunchKernelGGL(k_conv7x7s2_direct<1>, dim3((unsigned)n * 41), dim3(256), 0, st, d_in, (const float*)c->dl[0].d_w,
                                (const float*)c->dl[0].d_b, B, n, 122.782f, 117.001f, 104.298f);
@@ -1703,7 +1699,7 @@ static int cnn_forward_dlib(cis_cnn* c, CnnWs* ws, const float* d_in, int n, flo
     for (int i = 0; i < 14; ++i) {
         const DlibBlock& b = kDlibBlocks[i];
         const int s = b.down ? 2 : 1, p = b.down ? 0 : 1;
-        if (i == 13 && H == 4 && W == 4 && C == 256 && b.cout == 256 && b.down && !getenv("CIS_CNN_NO_TAIL")) {
+        if (i == 13 && H == 4 && W == 4 && C == 256 && b.cout == 256 && b.down && !envsw::call<envsw::cnn_no_tail>()) {
             // the last block's second convolution, skip branch, add_prev, ReLU, global average and the fully connected layer: one launch
             // (k_dlib_tail; CIS_CNN_NO_TAIL=1 keeps the six launches it replaces)
             ConvDesc da = nhwc_conv(n, 4, 4, 256, 256, 3, 2, 0, 1);
@@ -1856,15 +1852,14 @@ extern "C" int cis_cnn_forward_dev(cis_cnn* c, const float* d_nchw, int n, float
     CIS_REQUIRE(!c->orphaned, "this view's base was destroyed: close views before their base");
     int parts = (c->arch == 2 && n >= 128 && n <= 512) ? 2 : 1;
     if (c->parts_override > 0) parts = c->parts_override;
-    if (const char* e = getenv("CIS_CNN_PARTS")) parts = atoi(e);
+    parts = envsw::call<envsw::cnn_parts>(parts);
     if (parts > kMaxParts) parts = kMaxParts;
     if (parts > n) parts = n;
     const size_t in_item = c->arch == 2 ? (size_t)150 * 150 * 3 : (size_t)3 * 227 * 227, out_item = c->arch == 2 ? 128 : 4096;
-    static const bool threaded = getenv("CIS_CNN_THREADS") && atoi(getenv("CIS_CNN_THREADS")) != 0;
+    const bool threaded = envsw::once<envsw::cnn_threads>();
     // CIS_CNN_GRAPH=1: the dlib forward as a captured graph.  Off by default -- measured on ROCm 7.2 (profiles/r06_cnn_graph_ab.txt): the two
     // half-batch chains of a graph do not overlap (2.15 ms against 1.71 ms as launches), three views in flight 1.58 against 1.44 ms.
-    const char* ge = getenv("CIS_CNN_GRAPH");
-    const bool graphs_on = ge && atoi(ge) != 0;
+    const bool graphs_on = envsw::call<envsw::cnn_graph>();
     if (graphs_on && c->arch == 2 && !c->graph_off && !threaded && parts >= 1) {
         bool handled = false;
         const int rc = cnn_forward_graph(c, d_nchw, n, d_feats, parts, in_item, out_item, st, &handled);
@@ -1947,8 +1942,7 @@ static int cnn_forward_sentibank(cis_cnn* c, CnnWs* ws, const float* d_nchw, int
     const size_t act_elems = (size_t)n * 55 * 55 * 96;
     CIS_TRY(ws->act0.reserve(act_elems * sizeof(float)));
     CIS_TRY(ws->act1.reserve(act_elems * sizeof(float)));
-    const char* sk_e = getenv("CIS_CNN_FC_SPLITK");  // measurement switch: the order of a sum depends on it
-    const int fc_splitk = sk_e ? atoi(sk_e) : 8;
+    const int fc_splitk = envsw::call<envsw::cnn_fc_splitk>();  // measurement switch: the order of a sum depends on it
     CIS_REQUIRE(fc_splitk >= 1 && fc_splitk <= 32, "CIS_CNN_FC_SPLITK out of range");
     CIS_TRY(ws->act2.reserve((size_t)fc_splitk * n * 4096 * sizeof(float)));  // split-K partial sums of the fc layers
     CIS_TRY(cnn_poison(ws, st));
@@ -1971,7 +1965,7 @@ static int cnn_forward_sentibank(cis_cnn* c, CnnWs* ws, const float* d_nchw, int
         d.kx_fastest = 0;
         float* o = bufs[which];
         const float* wl = c->conv[l].d_w;
-        if (l == 0 && (c->precision != CIS_CNN_F32 || !getenv("CIS_CNN_NHWC_FIRST"))) {
+        if (l == 0 && (c->precision != CIS_CNN_F32 || !envsw::call<envsw::cnn_nhwc_first>())) {
             // first layer straight from the caller's NCHW planes (round 5): a (pixel, channel, kernel row) is a run of 11 contiguous
             // floats, gathered as three 16-byte loads (4-byte aligned: the planes' rows are 227 floats); the re-layout pass below
             // (57 us per 256 images, a 158 MB round trip) is gone.  K = 3 * 11 * 12 = 396 as before.
@@ -2001,7 +1995,7 @@ static int cnn_forward_sentibank(cis_cnn* c, CnnWs* ws, const float* d_nchw, int
             float* po = bufs[which];
             if (C % 4 == 0 && C <= 1024) {
                 const int tpp = C / 4, ppb = 256 / tpp;
-                const int remap = getenv("CIS_CNN_NO_XCD_REMAP") ? 0 : 1;
+                const int remap = envsw::call<envsw::cnn_no_xcd_remap>() ? 0 : 1;
                 const int64_t tiles = ceil_div((int64_t)n * OH * OW, ppb);
                 hipLaunchKernelGGL(k_maxpool_lrn_nhwc_v4, dim3((unsigned)(remap ? ceil_div(tiles, 8) * 8 : tiles)), dim3(256),
                                    (size_t)ppb * C * sizeof(float), st, cur, po, n, H, W, C, OH, OW, 5, 1e-4f, 0.75f, ppb, remap);

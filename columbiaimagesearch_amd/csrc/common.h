@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/cis_hip.h"
+#include "env_switches.h"
 
 // ---- error plumbing: nothing throws or aborts across the C ABI --------------------------------
 void cis_set_error(const char* fmt, ...);
@@ -63,7 +64,7 @@ struct DevBuf {
         __atomic_add_fetch(&g_cis_alloc_bytes, (long long)want, __ATOMIC_RELAXED);
         // Test hook: CIS_POISON_ALLOC=1 fills every new workspace with 0xff bytes (NaN / -1): nothing may rely on what fresh memory
         // holds (the runtime hands back blocks this process freed earlier, with their contents -- see k_nchw3_to_nhwc).
-        static const bool poison = getenv("CIS_POISON_ALLOC") != nullptr && atoi(getenv("CIS_POISON_ALLOC")) != 0;
+        const bool poison = envsw::once<envsw::poison_alloc>();
         // (the fill runs on the null stream; the library's own streams are non-blocking: wait for it before anybody writes the block)
         if (poison && (hipMemset(p, 0xff, want) != hipSuccess || hipDeviceSynchronize() != hipSuccess)) { cis_set_error("hipMemset (poison) failed"); return CIS_ENOMEM; }
         return CIS_OK;

@@ -758,7 +758,7 @@ static int radix_sort_pairs(cis_index* ix, int64_t n, int bits, hipStream_t st, 
 // slack items behind a rebuilt cell, next to an eighth of its size (few cells: room for several batches; thousands of coarse
 // clusters: millions of tiny cells, two items each are already 32 B x 16 M); CIS_INSERT_SLACK=-1: tight packing (rounds 1-3)
 static int slack_const(const cis_index* ix) {
-    static const int env = getenv("CIS_INSERT_SLACK") ? atoi(getenv("CIS_INSERT_SLACK")) : -2;
+    const int env = envsw::once<envsw::insert_slack>();
     if (env != -2) return env;
     return ix->ncells <= 65536 ? 32 : 2;
 }
@@ -784,7 +784,7 @@ static int store_merge(cis_index* ix, CellStore& s, int sel, const int64_t* d_id
     const int32_t* d_owner = ix->d_owner.as<int32_t>();
     int64_t* stats = ix->d_stats.as<int64_t>();
     int64_t* gcount = ix->d_gcount.as<int64_t>();
-    static const bool no_small = getenv("CIS_INS_NO_SMALL") != nullptr;  // A/B and tests: the general path for every batch size
+    const bool no_small = envsw::once<envsw::ins_no_small>();  // A/B and tests: the general path for every batch size
     const bool small = n > 0 && n <= INS_SMALL && !no_small;
     int gen = 0;
     int64_t* sid = ix->wi_sid.as<int64_t>();

@@ -1753,7 +1753,7 @@ __global__ __launch_bounds__(128) void k_pca_small(const TX* __restrict__ X, con
 int cis_dev_apply_pca(cis_model* m, const void* dX, int x_dtype, int64_t n, float* d_out, hipStream_t st, DevBuf* ws_y) {
     CIS_REQUIRE(m->has_pca, "model has no PCA parameters");
     if (n == 0) return CIS_OK;
-    static const bool no_small = getenv("CIS_PCA_NO_SMALL") != nullptr;   // A/B runs and tests: the batched form for every n
+    const bool no_small = envsw::once<envsw::pca_no_small>();   // A/B runs and tests: the batched form for every n
     if (!no_small && n <= 8 && m->renorm && m->D >= 8 && m->D <= 128 && m->D % 8 == 0 && m->D_in <= 512) {
         if (x_dtype == CIS_F32 && m->pca_mu_f32)
             hipLaunchKernelGGL((k_pca_small<float, true>), dim3((unsigned)n), dim3(128), 0, st, (const float*)dX, m->d_pmu, m->d_P, d_out, m->D_in, m->D);
@@ -1771,20 +1771,20 @@ int cis_dev_apply_pca(cis_model* m, const void* dX, int x_dtype, int64_t n, floa
     const bool small = ceil_div(n, 64) * ceil_div(m->D, 64) < 512;
     dim3 g((unsigned)ceil_div(n, small ? 32 : 64), (unsigned)ceil_div(m->D, 64));
     // wide inputs (the 4096-d DeepSentibank features): the float64 matrix cores; CIS_PCA_GEMM=valu keeps the register-tiled kernel
-    const char* pca_env = getenv("CIS_PCA_GEMM");
+    const char* pca_env = envsw::call<envsw::pca_gemm>();
     const bool pca_valu = pca_env && !strcmp(pca_env, "valu");
     const bool pca_force = pca_env && !strcmp(pca_env, "mfma");
     const bool use_mfma = !pca_valu && (m->D_in >= 128 || pca_force);
     dim3 gm((unsigned)ceil_div(n, 64), (unsigned)ceil_div(m->D, 64));
     // K 16 per stage = four workgroups per CU: pays once the grid is more than one round of the 32-per-stage form (measured on
     // the 4096 -> 256 product: 12500 rows 7.5 -> 8.3 M vectors/s of encode, 8192 rows 0.61 -> 0.64 ms)
-    const bool bk16 = getenv("CIS_PCA_BK") ? atoi(getenv("CIS_PCA_BK")) == 16 : (int64_t)gm.x * gm.y > 640;
+    const bool bk16 = envsw::call<envsw::pca_bk>((int64_t)gm.x * gm.y > 640 ? 16 : 32) == 16;
     // 128 x 128 tiles once they fill the chip twice over (CIS_PCA_TILE=64 keeps the 64 x 64 form)
     const dim3 gm128((unsigned)ceil_div(n, 128), (unsigned)ceil_div(m->D, 128));
-    const int tile_env = getenv("CIS_PCA_TILE") ? atoi(getenv("CIS_PCA_TILE")) : 0;
+    const int tile_env = envsw::call<envsw::pca_tile>();
     const bool big_tiles = use_mfma && m->D >= 128 && tile_env != 64 && ((int64_t)gm128.x * gm128.y >= 512 || tile_env == 128);
     // the loads-only fetch (k_pca_gemm_mfma_pf) where whole quads of k and pairs of columns exist; CIS_PCA_PF=0: the forms before it
-    const bool pf = m->D_in % 4 == 0 && m->D_in >= 4 && m->D % 2 == 0 && m->D >= 2 && !(getenv("CIS_PCA_PF") && atoi(getenv("CIS_PCA_PF")) == 0);
+    const bool pf = m->D_in % 4 == 0 && m->D_in >= 4 && m->D % 2 == 0 && m->D >= 2 && (int)envsw::call<envsw::pca_pf>() != 0;
 #define CIS_PCA_LAUNCH(TX, SUB, XP)                                                                                              \
     do {                                                                                                                          \
         if (big_tiles && pf) hipLaunchKernelGGL((k_pca_gemm_mfma_pf<TX, SUB, 128, 16>), gm128, dim3(256), 0, st, XP, m->d_pmu, m->d_P, Y, n, m->D_in, m->D); \
@@ -1892,7 +1892,7 @@ __global__ __launch_bounds__(256) void k_sqdist_rows2_reg(const T* __restrict__ 
 int cis_launch_sqdist_both(cis_model* m, const void* xc, int ct, int64_t n, void* out, hipStream_t st) {
     if (n == 0) return CIS_OK;
     // (the row must fit the register file next to eight accumulators: float32 up to h = 64, float64 up to h = 32)
-    if (m->V >= 64 && ((ct == CIS_F32 && (m->h == 32 || m->h == 64)) || (ct != CIS_F32 && m->h == 32)) && !getenv("CIS_SQDIST_PLAIN")) {
+    if (m->V >= 64 && ((ct == CIS_F32 && (m->h == 32 || m->h == 64)) || (ct != CIS_F32 && m->h == 32)) && !envsw::call<envsw::sqdist_plain>()) {
         const dim3 gr((unsigned)ceil_div(n, 256), (unsigned)ceil_div(m->V, 64), 2);
 #define CIS_SQ_REG(T, H, CP) hipLaunchKernelGGL((k_sqdist_rows2_reg<T, H>), gr, dim3(256), 0, st, (const T*)xc, (int64_t)m->D, CP, n, m->V, (T*)out)
         if (ct == CIS_F32) {
@@ -2025,10 +2025,10 @@ static int dev_predict_coarse(cis_model* m, const void* xc, int ct, int64_t n, u
     CIS_TRY(m->ws_dist.reserve((size_t)n * (m->V > m->K ? m->V : m->K) * sizeof(double)));
     // many clusters: matrix-core prefilter + exact re-check of the few listed pairs; the exact kernels below then only run
     // (device-side predicate) when a candidate list overflowed
-    const int coarse_mode = getenv("CIS_COARSE") ? atoi(getenv("CIS_COARSE")) : -1;  // 0 exact kernels, 1 prefilter
+    const int coarse_mode = envsw::call<envsw::coarse>();  // 0 exact kernels, 1 prefilter
     const bool pre = (coarse_mode >= 1 || (coarse_mode != 0 && m->V >= 256)) && m->h <= 128 && m->V <= 65535;  // 2: float64 cores for float32 too
     const int* only_if = nullptr;
-    if (!pre && m->V <= 1024 && ((ct == CIS_F32 && (m->h == 32 || m->h == 64)) || (ct != CIS_F32 && m->h == 32)) && !getenv("CIS_SQDIST_PLAIN")) {
+    if (!pre && m->V <= 1024 && ((ct == CIS_F32 && (m->h == 32 || m->h == 64)) || (ct != CIS_F32 && m->h == 32)) && !envsw::call<envsw::sqdist_plain>()) {
         const dim3 gr((unsigned)ceil_div(n, 256), 2);
         if (ct == CIS_F32) {
             if (m->h == 32) hipLaunchKernelGGL((k_coarse_assign_reg<float, 32>), gr, dim3(256), 0, st, (const float*)xc, (int64_t)m->D, m->d_Cs32, n, m->V, d_coarse);
@@ -2119,7 +2119,7 @@ static int dev_project(cis_model* m, const void* xc, int ct, int64_t n, const ui
     hipLaunchKernelGGL(k_group_scatter, dim3(grid1(n, 256)), dim3(256), bins_lds, st, d_coarse, n, V, offsets, cursor, perm);
     dim3 g((unsigned)max_tiles, (unsigned)ceil_div(m->h, 64));
     // the tile product on the float64 matrix cores where h is a multiple of 16 (CIS_PROJECT_VALU=1: the vector form)
-    const bool pm = m->h % 16 == 0 && !getenv("CIS_PROJECT_VALU");
+    const bool pm = m->h % 16 == 0 && !envsw::call<envsw::project_valu>();
     const bool pm64 = pm && m->h % 64 == 0;
 #define CIS_PROJ(KERN, TT, XP, CP) hipLaunchKernelGGL(KERN, g, dim3(256), 0, st, (const TT*)XP, CP, m->d_Rt, m->d_mus, tiles, n_tiles, perm, n, V, m->h, m->D, d_proj)
     if (ct == CIS_F32) {
@@ -2140,8 +2140,8 @@ static int dev_fine_from_proj(cis_model* m, const double* d_proj, int64_t n, uin
     if (n == 0) return CIS_OK;
     // CIS_FINE=0: every (vector, sub-centroid) pair exactly on the VALU (k_fine_codes, rounds 1-2); default: matrix-core
     // prefilter + exact re-check of the listed pairs
-    const bool fine_mfma = !(getenv("CIS_FINE") && atoi(getenv("CIS_FINE")) == 0);
-    if (fine_mfma && m->K <= 256 && (m->w == 4 || m->w == 8 || m->w == 16 || m->w == 32) && !getenv("CIS_ENCODE_TWO_KERNEL")) {
+    const bool fine_mfma = (int)envsw::call<envsw::fine>() != 0;
+    if (fine_mfma && m->K <= 256 && (m->w == 4 || m->w == 8 || m->w == 16 || m->w == 32) && !envsw::call<envsw::encode_two_kernel>()) {
         // groups of 128 vectors per workgroup: as many as keep >= ~4 workgroups per CU in the launch
         int reps = (int)(ceil_div(n, 128) * m->M / 1024);
         reps = reps < 1 ? 1 : (reps > 8 ? 8 : reps);
@@ -2157,7 +2157,7 @@ static int dev_fine_from_proj(cis_model* m, const double* d_proj, int64_t n, uin
         CIS_CHECK_HIP(hipGetLastError());
         return CIS_OK;
     }
-    if (m->K <= 256 && (m->w == 4 || m->w == 8 || m->w == 16 || m->w == 32) && !getenv("CIS_ENCODE_TWO_KERNEL")) {
+    if (m->K <= 256 && (m->w == 4 || m->w == 8 || m->w == 16 || m->w == 32) && !envsw::call<envsw::encode_two_kernel>()) {
         const dim3 gf((unsigned)ceil_div(n, 256), (unsigned)m->M);
         const size_t lds = (size_t)m->K * m->w * sizeof(double);
         switch (m->w) {

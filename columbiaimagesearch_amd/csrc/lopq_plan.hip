@@ -1390,7 +1390,7 @@ static void launch_rank(cis_index* ix, int nq, bool reg_sorts, int* grp_cnt, hip
     uint16_t* order = ix->w_order.as<uint16_t>();
     CT* sorted = ix->w_sorted.as<CT>();
     if constexpr (sizeof(CT) == 4) {
-        const bool sort_lds = getenv("CIS_RANK_SORT_LDS") != nullptr;  // the LDS form of the sort (A/B runs)
+        const bool sort_lds = envsw::call<envsw::rank_sort_lds>();  // the LDS form of the sort (A/B runs)
         if (reg_sorts && V > 256 && !sort_lds && (Vp2 == 1024 || Vp2 == 2048 || Vp2 == 4096)) {
             if (Vp2 == 1024) hipLaunchKernelGGL(k_rank_sort_reg<4>, dim3(nq, 2), dim3(256), 0, st, cd, nq, V, order, sorted, grp_cnt);
             else if (Vp2 == 2048) hipLaunchKernelGGL(k_rank_sort_reg<8>, dim3(nq, 2), dim3(256), 0, st, cd, nq, V, order, sorted, grp_cnt);
@@ -1430,7 +1430,7 @@ int dump_plan_fallbacks(const Batch& b) {
 
 // CIS_HOST_TIMING=1: where the host spends a batch (stderr, every 400 batches): entry -> plan totals requested, the wait for them
 static void host_timing(const Batch& b, std::chrono::steady_clock::time_point t0) {
-    static const bool ht = getenv("CIS_HOST_TIMING") != nullptr;
+    const bool ht = envsw::once<envsw::host_timing>();
     if (!ht) return;
     static std::atomic<long long> n_{0}, wait_ns{0}, front_ns{0};
     const auto t1 = std::chrono::steady_clock::now();
@@ -1539,7 +1539,7 @@ int plan_totals(Batch& b, const Route& r) {
     b.d_tot = nullptr;
     b.n_items = b.n_tabs = b.n_cand_all = 0;
     {
-        static const bool no_bounds = getenv("CIS_NO_BOUNDS") != nullptr;
+        const bool no_bounds = envsw::once<envsw::no_bounds>();
         // quota <= 0 still visits one cell (search.py:131-132: the test follows the first append)
         const int64_t q_eff = b.quota < 0 ? 0 : b.quota;
         const int64_t per_q = (q_eff < ix->n_total ? q_eff : ix->n_total) + ix->max_cell;
@@ -1550,7 +1550,7 @@ int plan_totals(Batch& b, const Route& r) {
         // candidates (search.py:128-133 stops at the quota or at the end of the index), and that alone is past the route's threshold
         // (an exhaustive quota): the same bounds size the workspaces, the kernels read the real totals from device memory, and the
         // host does not stop in the middle of the batch (round 6: the read-back was a 35 us hole in a 0.5 ms exhaustive query).
-        static const bool no_stream_bounds = getenv("CIS_STREAM_WAIT") != nullptr;   // A/B runs: the read-back as before
+        const bool no_stream_bounds = envsw::once<envsw::stream_wait>();   // A/B runs: the read-back as before
         const bool sure_stream = !no_bounds && !no_stream_bounds && r.stream_hint && r.split_tables && items_q <= 65536 &&
                                  (double)nq * (double)items_q < 4.0e6 &&
                                  (ix->force_stream || (q_eff < ix->n_total ? q_eff : ix->n_total) >= r.stream_min) && ix->n_total > 0 && nq <= 64;
@@ -1566,7 +1566,7 @@ int plan_totals(Batch& b, const Route& r) {
         // the plan totals size the rest of the batch: poll the pinned sequence word (a blocking stream synchronisation
         // wakes up tens of microseconds late); past 2 ms -- a stream busy with the caller's earlier work, or an error --
         // fall back to the blocking wait
-        static const bool no_poll = getenv("CIS_NO_POLL") != nullptr;
+        const bool no_poll = envsw::once<envsw::no_poll>();
         const auto t0 = std::chrono::steady_clock::now();
         bool got = false;
         while (!no_poll) {

@@ -465,8 +465,7 @@ inline unsigned grid_for(int64_t n, int t) { return (unsigned)(n > 0 ? ceil_div(
 
 // the LDS form of the set up to this many ids (CIS_REMOVE_LDS_MAX lowers it for the A/B of tools/bench_remove.py; read per call)
 int lds_switch() {
-    const char* e = getenv("CIS_REMOVE_LDS_MAX");
-    const int v = e ? atoi(e) : RM_LDS_MAX;
+    const int v = envsw::call<envsw::remove_lds_max>((int)RM_LDS_MAX);
     return v < 0 ? 0 : (v > RM_LDS_MAX ? RM_LDS_MAX : v);
 }
 

@@ -1906,9 +1906,9 @@ Scan3Geom scan3_geom(int M, int K, int L, int64_t avg_chunk, int force_two_pass)
     // the sampled form at M = 16: with the tables' largest entries as the scale the + M + 1 slack was ~17 % of the cut and 84 % of the
     // lists overflowed (8.99 against 0.60 ms for k_adc_scan2); with the SATURATING scale of k_adc_scan4 (Scan3Geom::sat) no slot of C3
     // falls back and the scan takes 0.474 ms (profiles/r04v_m16.txt).  CIS_S4_M16=0 keeps M = 16 on k_adc_scan2.
-    static const int s4_m16 = getenv("CIS_S4_M16") ? atoi(getenv("CIS_S4_M16")) : 1;
+    const int s4_m16 = envsw::once<envsw::s4_m16>();
     if (g.two_pass == 0 && g.long_chunks && (M <= 8 || s4_m16) && L <= 128) g.two_pass = 2;
-    if (const char* e = getenv("CIS_SCAN3_TWOPASS")) g.two_pass = atoi(e);
+    g.two_pass = envsw::call<envsw::scan3_twopass>(g.two_pass);
     if (force_two_pass >= 0) g.two_pass = force_two_pass;  // scan modes 3 / 4 / 5 (tests)
     if (g.two_pass == 2 && M > 8 && !s4_m16 && force_two_pass != 2) g.two_pass = g.long_chunks ? 0 : 1;
     if (g.two_pass == 1 && g.long_chunks && force_two_pass < 0) g.two_pass = 0;  // the histogram atomics of the two-pass form contend on long chunks
@@ -1924,7 +1924,7 @@ static void launch_scan4(const Scan3Geom& g, const ScanArgs& a, float z, int fra
     const size_t lds = scan4_lds(M, a.K, LCAP, NW);
     const int by_lds = (int)(163840 / lds), by_waves = (WPE * 4) / NW;
     int per_cu = by_lds < by_waves ? by_lds : by_waves;
-    if (const char* e = getenv("CIS_S4_PER_CU")) per_cu = atoi(e) > 0 && atoi(e) < per_cu ? atoi(e) : per_cu;  // A/B: room for other batches' kernels
+    per_cu = std::min(per_cu, envsw::call<envsw::s4_per_cu>(per_cu));  // A/B: room for other batches' kernels
     hipLaunchKernelGGL((k_adc_scan4<M, U, NW, WPE, LCAP>), dim3(persistent_grid(a, g.G, per_cu)), dim3(NW * 64), lds, a.st, a.items, a.tabs, a.slots, a.n_slots, a.T32, a.T,
                        a.codes, a.K, a.L, g.S, a.qctr + 9, a.fhdr, a.fslots, a.hits, a.hitn, a.slack, a.qbound, z, frac, sample_rows, dyn, g.sat);
 }
@@ -1937,14 +1937,14 @@ static void launch_scan3_t(const Scan3Geom& g, const ScanArgs& a) {
     }
     // k_adc_scan4, then the slots it could not settle (normally none) through k_adc_scan3.  Its switches are
     // read per call (A/B runs and the fall-back tests set them between calls)
-    const float z_short = getenv("CIS_S4_ZS") ? (float)atof(getenv("CIS_S4_ZS")) : CIS_S4_Z;
+    const float z_short = envsw::call<envsw::s4_zs>(CIS_S4_Z);
     // long chunks, measured on C4 (profiles/r03m_scan_long.txt): z 4 / 4.5 / 5 -> 0.326 / 0.332 / 0.335 ms, no verification
     // failure in 100 k lists at z = 4; static schedule 0.301 against 0.326 ms with slots from a counter; one row in 8 / 10 /
     // 16 as the sample -> 0.321 / 0.326 / 0.45 ms; at most 128 sample rows (64: the 65536-candidate chunks overflow their lists)
-    const float z_long = getenv("CIS_S4_ZL") ? (float)atof(getenv("CIS_S4_ZL")) : 4.5f;
-    const int frac_long = getenv("CIS_S4_FRAC") ? atoi(getenv("CIS_S4_FRAC")) : 8;
-    const int nsx_long = getenv("CIS_S4_NSX") ? atoi(getenv("CIS_S4_NSX")) : 128;
-    const int dyn_long = getenv("CIS_S4_DYN") ? atoi(getenv("CIS_S4_DYN")) : 0;
+    const float z_long = (float)envsw::call<envsw::s4_zl>();
+    const int frac_long = envsw::call<envsw::s4_frac>();
+    const int nsx_long = envsw::call<envsw::s4_nsx>();
+    const int dyn_long = envsw::call<envsw::s4_dyn>();
     // four waves per slot, compiled for 6 (short chunks) / 4 (long chunks) waves per SIMD
     if (!g.long_chunks) {
         constexpr int WPE4 = (M == 16) ? 4 : CIS_S4_WPE;  // (M = 16: 41 KB of LDS hold three workgroups per CU anyway)
@@ -1953,7 +1953,7 @@ static void launch_scan3_t(const Scan3Geom& g, const ScanArgs& a) {
         constexpr int WPE4 = (M == 16) ? 3 : 4;  // (M = 16: 49 KB of LDS = three workgroups per CU, 168 registers)
         launch_scan4<M, CIS_S4_UL, 4, WPE4, S4_LCAP_LONG>(g, a, z_long, frac_long, nsx_long, dyn_long);
     }
-    if (getenv("CIS_SCAN4_DEBUG")) {  // diagnosis: how many slots the sample misjudged (blocks)
+    if (envsw::call<envsw::scan4_debug>()) {  // diagnosis: how many slots the sample misjudged (blocks)
         int h[6] = {0, 0, 0, 0, 0, 0};
         if (hipMemcpyAsync(h, a.qctr + 9, sizeof(h), hipMemcpyDeviceToHost, a.st) == hipSuccess && hipStreamSynchronize(a.st) == hipSuccess)
             fprintf(stderr, "[cis] k_adc_scan4: %d slots, %d to the fall-back list (lists: %d overflowed, %d failed the verification, %d crowds at the cut; %d slots with items of different chunks)\n",

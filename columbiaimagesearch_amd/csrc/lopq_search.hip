@@ -274,7 +274,7 @@ static void launch_tables(int64_t n_tabs, size_t tab_lds, hipStream_t st, const 
                           int nf, int K, int D, double* T, PwProg prog_w, double* px_out, const int64_t* d_totals = nullptr,
                           float* px32_out = nullptr) {
     constexpr int TB = 8;
-    if (px_out && h <= 256 && h % 16 == 0 && !getenv("CIS_TABLES_UNGROUPED") && !getenv("CIS_TABLES_VALU")) {
+    if (px_out && h <= 256 && h % 16 == 0 && !envsw::call<envsw::tables_ungrouped>() && !envsw::call<envsw::tables_valu>()) {
         // the grouped projection on the float64 matrix cores (16 tables per block); CIS_TABLES_VALU=1: the vector form below
         const size_t lds = (size_t)16 * (h + 4 + h + 2) * sizeof(double);
         if (h % 64 == 0)
@@ -283,7 +283,7 @@ static void launch_tables(int64_t n_tabs, size_t tab_lds, hipStream_t st, const 
         else
             hipLaunchKernelGGL((k_tables_group_mfma<CT, 4>), dim3((unsigned)ceil_div(n_tabs, 16)), dim3(256), lds, st, X, Cs, Rt, mus, tabs,
                                tab_order, (int)n_tabs, V, h, D, px_out, d_totals, px32_out);
-    } else if (px_out && h <= 256 && 256 / h >= 1 && !getenv("CIS_TABLES_UNGROUPED")) {
+    } else if (px_out && h <= 256 && 256 / h >= 1 && !envsw::call<envsw::tables_ungrouped>()) {
         const size_t lds = (size_t)(TB * h + TB * h) * sizeof(double);
         hipLaunchKernelGGL((k_tables_group<CT, TB>), dim3((unsigned)ceil_div(n_tabs, TB)), dim3(256), lds, st, X, Cs, Rt, mus, tabs,
                            tab_order, (int)n_tabs, V, h, D, px_out, d_totals, px32_out);
@@ -1802,7 +1802,7 @@ static Scan2Geom scan2_geom(int M, int K, int L, int nq) {
     g.G = (nq >= 64 && NR < 16) ? 2 : 1;  // pairs of queries per workgroup when the batch is large enough to find pairs
     g.NW = 4;
     g.U = (g.G == 2) ? 4 : 2;
-    if (const char* e = getenv("CIS_SCAN_GEOM")) {  // experiments: "G,NW,U" out of the instantiated set
+    if (const char* e = envsw::call<envsw::scan_geom>()) {  // experiments: "G,NW,U" out of the instantiated set
         int a = 0, b = 0, c = 0;
         if (NR < 16 && sscanf(e, "%d,%d,%d", &a, &b, &c) == 3 && ((a == 1 && b == 4) || (a == 2 && b == 4) || (a == 2 && b == 8 && c == 2) || (a == 2 && (b == 1 || b == 2) && c == 4) || (a == 4 && b == 4 && c == 4 && NR == 4)) && (c == 2 || c == 4)) {
             g.G = a; g.NW = b; g.U = c;
@@ -2527,7 +2527,7 @@ static SelectPlan select_plan(int L, int nq, int64_t n_cand) {
     sp.stride = (int64_t)L < n_cand ? (int64_t)L : (n_cand > 0 ? n_cand : 1);
     sp.sort_lds = L <= MAX_LDS_LIMIT;
     sp.select = sp.sort_lds || (double)nq * (double)sp.stride <= 0.5 * (double)n_cand;
-    if (getenv("CIS_NO_SELECT")) sp.select = sp.sort_lds = false;  // experiments: the full segmented sort
+    if (envsw::call<envsw::no_select>()) sp.select = sp.sort_lds = false;  // experiments: the full segmented sort
     if (!sp.select) sp.sort_lds = false;
     sp.p2 = 64;
     while (sp.p2 < L && sp.sort_lds) sp.p2 <<= 1;
@@ -2542,7 +2542,7 @@ static SelectPlan select_plan(int L, int nq, int64_t n_cand) {
 // to fill the persistent scan kernel, and its per-wave regions grow with limit, while scoring every candidate with one
 // workgroup per 2048 of them and selecting per query costs the same 0.18-0.4 ms whatever the limit.
 static int small_batch_nq(int L) {
-    static const int forced = getenv("CIS_SMALL_NQ") ? atoi(getenv("CIS_SMALL_NQ")) : -1;  // experiments
+    const int forced = envsw::once<envsw::small_nq>();  // experiments
     if (forced >= 0) return forced;
     if (L <= 184) return 63;
     if (L <= 300) return 256;
@@ -3171,18 +3171,18 @@ static void route_hints(cis_index* ix, int nq, int64_t quota, int L, Route* r) {
     r->geom = scan2_geom(M, K, L, nq);
     // scan v3 (16-bit fixed-point tables, four queries per workgroup) for large batches; its region entries hold 16-bit
     // positions, so a chunk is at most 65536 candidates.  scan_mode 3 forces it for any batch size (tests).
-    static const int env_scan = getenv("CIS_FORCE_SCAN") ? atoi(getenv("CIS_FORCE_SCAN")) : 0;  // A/B runs: 2 or 3
+    const int env_scan = envsw::once<envsw::force_scan>();  // A/B runs: 2 or 3
     // Automatic routing picks it where it measured faster than k_adc_scan2 (profiles/r02*): short cells (a batch that
     // visits about quota / (n_total / cells) + 1 cells per query, each shorter than 8192 codes) at M <= 8.
     const bool short_cells = ix->nonempty_cells > 0 && ix->n_total / ix->nonempty_cells < 8192 && M <= 8;
     // ... and long cells at M <= 8, limit <= 128 through its sampled single-pass form (k_adc_scan4 with a tenth of the rows as
     // the sample: profiles/r03m_*); CIS_SCAN_LONG=0 keeps them on k_adc_scan2
-    static const int env_long = getenv("CIS_SCAN_LONG") ? atoi(getenv("CIS_SCAN_LONG")) : 1;
+    const int env_long = envsw::once<envsw::scan_long>();
     // ... and at M = 16 with the saturating scale (round 4).  Its failure mode is expensive -- a slot whose scale missed runs again in
     // the streaming form, ~14x the time when most of them do -- so the index watches the fall-back count of its last such scan
     // (a pinned word the scan's stream writes; no wait, the value may be one batch old) and, when more than an eighth of the slots
     // fell back, serves the next 64 batches from k_adc_scan2 before it tries again.  CIS_S4_M16=0: always k_adc_scan2.
-    static const int env_m16 = getenv("CIS_S4_M16") ? atoi(getenv("CIS_S4_M16")) : 1;
+    const int env_m16 = envsw::once<envsw::s4_m16>();
     if (M == 16 && env_m16 && ix->h_totals) {
         const int32_t* fb = reinterpret_cast<const int32_t*>(&ix->h_totals[4]);
         const int32_t n_s = __atomic_load_n(&fb[0], __ATOMIC_RELAXED), n_f = __atomic_load_n(&fb[1], __ATOMIC_RELAXED);
@@ -3203,8 +3203,8 @@ static void route_hints(cis_index* ix, int nq, int64_t quota, int L, Route* r) {
     // of hundreds of thousands of codes.  Decided here from the bound of the candidates per query (the chunk size is part of the
     // plan); the exact count confirms it in route_decide.  Chunks of 65536 candidates, longer when the largest cell would need more
     // than the slot builder's 16 chunk keys (the items of a slot must be the SAME chunk of a cell).
-    static const int64_t stream_min = getenv("CIS_STREAM_MIN") ? atoll(getenv("CIS_STREAM_MIN")) : 262144;  // candidates per query from which it pays
-    static const int stream_nq = getenv("CIS_STREAM_NQ") ? atoi(getenv("CIS_STREAM_NQ")) : 16;               // 0: never
+    const int64_t stream_min = envsw::once<envsw::stream_min>();  // candidates per query from which it pays
+    const int stream_nq = envsw::once<envsw::stream_nq>();         // 0: never
     r->stream_min = stream_min;
     const bool stream_auto = !ix->stream_off && !ix->force_exact_scan && !ix->force_prefilter_scan && !ix->force_scan2 && !ix->force_scan3 &&
                              nq <= stream_nq && L <= 440 && ix->world == 1 &&
@@ -3218,24 +3218,24 @@ static void route_hints(cis_index* ix, int nq, int64_t quota, int L, Route* r) {
         const int64_t cap_len = (((int64_t)1 << 31) - 65536) / M;
         int64_t want = ix->max_cell > 65536 ? ix->max_cell : 65536;
         want = want < cap_len ? want : cap_len;
-        if (const char* e = getenv("CIS_STREAM_CHUNK")) want = atoi(e) > 0 ? atoi(e) : want;  // A/B runs
+        want = envsw::call<envsw::stream_chunk>((int)want);  // A/B runs
         seg_max = (int)(ceil_div(want, (int64_t)1024) * 1024);
         const int64_t need = ceil_div(ix->max_cell > 0 ? ix->max_cell : 1, (int64_t)16);   // (at most 16 chunk keys per cell)
         if (need > seg_max) seg_max = (int)ceil_div(need, (int64_t)1024) * 1024;
-        if (ix->force_stream && getenv("CIS_STREAM_SEG")) seg_max = atoi(getenv("CIS_STREAM_SEG")) > 0 ? atoi(getenv("CIS_STREAM_SEG")) : seg_max;  // tests: short chunks on small fixtures
+        if (ix->force_stream) seg_max = envsw::call<envsw::stream_seg>(seg_max);  // tests: short chunks on small fixtures
     }
-    if (const char* e = getenv("CIS_SEG_MAX")) seg_max = atoi(e) > 0 ? atoi(e) : seg_max;  // A/B runs (tools/emulate_shard.py)
+    seg_max = envsw::call<envsw::seg_max>(seg_max);  // A/B runs (tools/emulate_shard.py)
     r->seg_max = seg_max;
     // thousands of coarse clusters (the release configurations' V = 2048 / 4096): the plan is a per-query selection + sort
     // (k_plan_par) instead of one frontier step per visited cell; queries it cannot resolve fall back to the frontier walk
-    const bool no_par_plan = getenv("CIS_NO_PAR_PLAN") != nullptr;
+    const bool no_par_plan = envsw::call<envsw::no_par_plan>();
     // ... and few queries that visit MANY cells of a small vocabulary (the streaming route's exhaustive quota: all 256 cells of V = 16):
     // the frontier walk costs ~1.3 us per visited cell and runs twice (count, emit) -- 0.67 of the 1.25 ms of a single exhaustive
     // query over 200 M codes; the sort-based plan does the same cells in one band
     const bool stream_par = r->stream_hint && V >= 8 && ix->n_total > 0 &&
                             (double)(quota < 0 ? 0 : quota) * (double)ix->nonempty_cells >= 32.0 * (double)ix->n_total;
     r->par_plan = ((V >= 128 || stream_par) && V <= PLAN_PAR_STAGE) && !no_par_plan;
-    static const bool no_fused_front = getenv("CIS_NO_FUSED_FRONT") != nullptr;
+    const bool no_fused_front = envsw::once<envsw::no_fused_front>();
     r->fused_front = V <= 64 && !r->par_plan && !no_fused_front;
 }
 
@@ -3257,7 +3257,7 @@ static int route_decide(Batch& b, Route* r) {
     cis_model* m = ix->m;
     const int K = m->K, M = m->M, h = m->h, nf = m->nf, nq = b.nq, L = b.L;
     r->direct = !b.d_tot && r->big && r->tiny_cells && h <= 256 && direct_jp(M, K, m->w) > 0 &&
-                !getenv("CIS_TABLES_UNGROUPED") && !getenv("CIS_NO_DIRECT");
+                !envsw::call<envsw::tables_ungrouped>() && !envsw::call<envsw::no_direct>();
     r->stream = r->stream_hint && b.n_items > 0 && (r->w_pow2 || r->fast) &&
                 (ix->force_stream || b.d_tot != nullptr || b.n_cand_all / (nq > 0 ? nq : 1) >= r->stream_min);   // (d_tot: certain, see plan_totals)
     if (!r->stream) {
@@ -3271,7 +3271,7 @@ static int route_decide(Batch& b, Route* r) {
                    (r->direct ? (double)b.n_tabs * h * sizeof(double) : (double)b.n_tabs * nf * K * sizeof(double));
         }
         // default 24 GB of the 288 GB: thousands of coarse clusters need ~1.6 MB of tables per query (V = 2048, quota 10000)
-        const double budget = (getenv("CIS_WORKSPACE_GB") ? atof(getenv("CIS_WORKSPACE_GB")) : 24.0) * 1.0e9;
+        const double budget = envsw::call<envsw::workspace_gb>() * 1.0e9;
         if (need > budget && nq > 1) {
             ix->retry_fraction = 0.9 * budget / need;  // the caller plans again with this share of the batch
             return CIS_RETRY_SMALLER;
@@ -3287,7 +3287,7 @@ static int route_decide(Batch& b, Route* r) {
     // The float32 copy of the tables is a third of what the tables kernel writes (8 + 4 bytes per entry: 402 MB per C2 batch, and that
     // kernel is bound by its writes); CIS_NO_T32=1 drops it -- the scans then convert the float64 entries while they stage them
     // (tab_f4: the same bits).  The tiny-cell path keeps its float32 px copy in this buffer.
-    static const bool no_t32 = getenv("CIS_NO_T32") != nullptr && atoi(getenv("CIS_NO_T32")) != 0;
+    const bool no_t32 = envsw::once<envsw::no_t32>();
     r->drop_t32 = no_t32 && !r->direct && r->split_tables;
     return CIS_OK;
 }
@@ -3419,12 +3419,13 @@ static int run_stream(Batch& b, const Route& r) {
     const int64_t per_q = n_cand_all / nq;
     const int row = 64 * (16 / M);
     int64_t target = 4096 > 16 * L ? 4096 : 16 * L;
-    if (const char* e = getenv("CIS_STREAM_TARGET")) target = atoll(e) > 0 ? atoll(e) : target;
+    target = envsw::call<envsw::stream_target>(target);
     int64_t ss = per_q / row / 4096;            // ~4096 sampled rows per query
     ss = ss < 8 ? 8 : (ss > 4096 ? 4096 : ss);
     int64_t kth = target / ss;
     kth = kth < 8 ? 8 : (kth > B / 4 ? B / 4 : kth);
-    if (ix->force_stream && getenv("CIS_STREAM_SS")) { ss = atoll(getenv("CIS_STREAM_SS")); kth = getenv("CIS_STREAM_K") ? atoll(getenv("CIS_STREAM_K")) : kth; }  // tests
+    const int64_t ss_env = ix->force_stream ? envsw::call<envsw::stream_ss>(INT64_MIN) : INT64_MIN;  // (INT64_MIN: unset)
+    if (ss_env != INT64_MIN) { ss = ss_env; kth = envsw::call<envsw::stream_k>(kth); }  // tests
     // a lane folds `flush` of its sampled rows into one bucket: ~4 B bucket writes per query (a query's sampled rows x 64 lanes / flush)
     int64_t flush = ceil_div(ceil_div(per_q, (int64_t)row * ss) * 64, (int64_t)4 * B);
     flush = flush < 1 ? 1 : flush;
@@ -3462,7 +3463,7 @@ static int run_stream(Batch& b, const Route& r) {
     if (ix->h_totals[6] == 0 && ix->h_totals[7] == 0) return CIS_OK;
     // a failed proof (an unlucky sample) or an overflowed list (a crowd of equal codes): the generic path answers the batch
     ++ix->stream_fallbacks;
-    if (getenv("CIS_STREAM_DEBUG"))
+    if (envsw::call<envsw::stream_debug>())
         fprintf(stderr, "[cis] streaming route: %lld failed proofs, %lld overflowed lists of %d queries -> generic path\n", (long long)ix->h_totals[6], (long long)ix->h_totals[7], nq);
     ix->stream_off = true;
     for (int i = 0; i < 3; ++i) ix->stats[i] = 0;  // (the generic pass counts the batch again)
@@ -3560,13 +3561,13 @@ static int run_all_candidates(Batch& b, const Route& r) {
         int* fbflag = nullptr;
         // (measured at V = 2048, 8192 queries, limit 100: quota 10000 5.16 against 6.35 ms for the exact kernels, quota 1000 2.19 against
         // 1.36 -- the sample, the row copies and the sort are fixed costs per query: from 8192 candidates on)
-        const int64_t tiny_min_quota = getenv("CIS_TINY_MIN_QUOTA") ? atoll(getenv("CIS_TINY_MIN_QUOTA")) : 8192;
-        if (direct && sp.sort_lds && n_items > 0 && (int64_t)L * 8 <= (int64_t)quota && (int64_t)quota >= tiny_min_quota && !getenv("CIS_NO_TINY")) {
+        const int64_t tiny_min_quota = envsw::call<envsw::tiny_min_quota>();
+        if (direct && sp.sort_lds && n_items > 0 && (int64_t)L * 8 <= (int64_t)quota && (int64_t)quota >= tiny_min_quota && !envsw::call<envsw::no_tiny>()) {
             int ncmax = 0;
             const int tch = tiny_pool(M, K, m->w, h, L, (int64_t)quota + ix->max_cell, &ncmax);  // bytes of the per-query pool
             if (tch > 0) {
                 fbflag = nsel + (nq + 2);
-                static const bool tiny_dbg = getenv("CIS_TINY_DEBUG") != nullptr;
+                const bool tiny_dbg = envsw::once<envsw::tiny_debug>();
                 unsigned int* dbg = nullptr;
                 if (tiny_dbg) {
                     CIS_TRY(ix->w_slack.reserve(128));
@@ -3642,7 +3643,7 @@ static int run_fast_scan(Batch& b, const Route& r) {
     if (use3) {
         Scan3Geom g3 = geom3;
         // M = 16 on the sampled form: the saturating scale of k_adc_scan4 (sums of the near candidates at this fraction of the entry cap)
-        const float sat16 = getenv("CIS_S4_SAT") ? (float)atof(getenv("CIS_S4_SAT")) : 0.75f;
+        const float sat16 = (float)envsw::call<envsw::s4_sat>();
         if (M == 16 && g3.two_pass == 2) g3.sat = sat16;
         launch_scan3(M, g3, a);
         if (g3.sat > 0.f && ix->h_totals)  // (slots, fall-back slots) for the back-off in route_hints
@@ -3746,7 +3747,7 @@ static int search_batch(cis_index* ix, const void* dQ, int q_dtype, int nq, int6
     b.grp_base = b.f.grp_cnt + 4 * V * GRP_SUB;
     Route r{};
     route_hints(ix, nq, quota, L, &r);
-    b.plan_hint = (r.par_plan && !getenv("CIS_NO_PLAN_HINT")) ? ix->plan_hint_ptr() : nullptr;
+    b.plan_hint = (r.par_plan && !envsw::call<envsw::no_plan_hint>()) ? ix->plan_hint_ptr() : nullptr;
     b.hint_slot = (int)((ix->plan_seq + 1) & 1);  // this batch's launches add into this parity and read the other
     // cells WITH candidates per query the fast plan lists (16 bytes each; the empty cells it walks -- most of them at thousands of coarse
     // clusters, tens of thousands for an outlier query -- are not listed): 2 GB of lists per batch at most; past the cap the query goes
@@ -3769,7 +3770,7 @@ static int search_batch(cis_index* ix, const void* dQ, int q_dtype, int nq, int6
     }
     const bool f32 = b.f.ct == CIS_F32;
     CIS_TRY(f32 ? front_count<float>(b, r) : front_count<double>(b, r));
-    if ((r.par_plan || r.fused_front) && getenv("CIS_DEBUG_PLAN")) CIS_TRY(dump_plan_fallbacks(b));
+    if ((r.par_plan || r.fused_front) && envsw::call<envsw::debug_plan>()) CIS_TRY(dump_plan_fallbacks(b));
     CIS_TRY(plan_totals(b, r));
     CIS_TRY(route_decide(b, &r));
     // 3. emit items + table list

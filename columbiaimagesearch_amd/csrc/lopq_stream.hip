@@ -631,7 +631,7 @@ size_t stream_slot_bytes() { return sizeof(StreamSlot); }
 int stream_grid(int M, int G, int K, int64_t max_rows) {
     (void)M; (void)G; (void)K;
     int64_t g = (int64_t)256 * CIS_STREAM_PER_CU;
-    if (const char* e = getenv("CIS_STREAM_GRID")) g = atoll(e) > 0 ? atoll(e) : g;  // experiments
+    g = envsw::call<envsw::stream_grid>(g);  // experiments
     const int64_t by_rows = ceil_div(max_rows < 1 ? 1 : max_rows, (int64_t)CIS_STREAM_NW);
     g = g < by_rows ? g : by_rows;
     return (int)(g < 1 ? 1 : g);
