@@ -131,8 +131,13 @@ _PROTOS = {
                                            c_int, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cis_rerank_packed_half_dev": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int64,
                                            c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "cis_rerank_select_int8_dev": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p,
+                                           c_int, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cis_rerank_packed_int8_dev": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int64,
+                                           c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "cis_featstore_create":(c_int, [POINTER(c_void_p), c_int, c_int, c_int64]),
     "cis_featstore_create_half": (c_int, [POINTER(c_void_p), c_int, c_int64]),
+    "cis_featstore_create_int8": (c_int, [POINTER(c_void_p), c_int, c_int64]),
     "cis_featstore_destroy": (None, [c_void_p]),
     "cis_featstore_size": (c_int64, [c_void_p]),
     "cis_featstore_reserve": (c_int, [c_void_p, c_int64, c_void_p]),

@@ -3,7 +3,8 @@
 //
 // A cis_featstore owns a feature matrix [cap_rows][D] (float32 or float64; or float16 behind a float32 interface,
 // cis_featstore_create_half: put converts on the way in, get and rows on the way out, with the kernels of feat_half.hip, and remove
-// moves the 2 D-byte rows with k_fs_copy as they are), the row -> id column row_ids [cap_rows], the id -> row
+// moves the 2 D-byte rows with k_fs_copy as they are; or int8 codes behind an in-row float32 scale, cis_featstore_create_int8 and
+// feat_int8.hip, 16 + D bytes a row: row_bytes() is the one place that knows), the row -> id column row_ids [cap_rows], the id -> row
 // table keys / rows [cap] (layout, hash, linear probing and -1 = empty of lopq_rerank.hip: row_of_id reads it unchanged) and the live
 // row count n.  Rows [0, n) are always dense, so cis_exact_knn_dev and cis_rerank_select_dev read the matrix directly
 // (cis_featstore_view).
@@ -54,10 +55,16 @@ int cis_seg_sort_u64(void* temp, size_t* temp_bytes, const uint64_t* keys_in, ui
 // feat_half.hip: k_fs_copy's jobs with a conversion, float32 -> float16 rows (put) and float16 -> float32 rows (get; src == NULL: row j)
 int cis_fs_half_scatter(const void* from_f32, void* to_f16, int D, const int64_t* src, const int64_t* dst, int64_t njobs, hipStream_t st);
 int cis_fs_half_gather(const void* from_f16, void* to_f32, int D, const int64_t* src, int64_t njobs, hipStream_t st);
+// feat_int8.hip: the same two on int8 rows (16 + D bytes: a float32 scale in the first 16-byte word, then the codes)
+int cis_fs_int8_scatter(const void* from_f32, void* to_i8, int D, const int64_t* src, const int64_t* dst, int64_t njobs, hipStream_t st);
+int cis_fs_int8_gather(const void* from_i8, void* to_f32, int D, const int64_t* src, int64_t njobs, hipStream_t st);
+
+constexpr int FS_F16 = 2;  // f_dtype of a store made by cis_featstore_create_half
+constexpr int FS_I8 = 1;   // f_dtype of a store made by cis_featstore_create_int8
 
 struct cis_featstore {
     int device = 0;
-    int D = 0, f_dtype = 0;       // f_dtype: bytes per stored element (FS_F16 = 2: float16 rows, float32 at the interface)
+    int D = 0, f_dtype = 0;       // f_dtype: bytes per stored element (FS_F16 = 2, FS_I8 = 1: float32 at the interface)
     void* feats = nullptr;        // [cap_rows][D]
     int64_t* row_ids = nullptr;   // [cap_rows]
     int64_t cap_rows = 0, n = 0;
@@ -68,12 +75,13 @@ struct cis_featstore {
     DevBuf ws;                    // per-call scratch, per batch element
     DevBuf cnt;                   // FS_WORDS counters
     int64_t* h_cnt = nullptr;     // pinned: their read-back
+    // bytes from one stored row to the next: an int8 row carries its scale in a 16-byte word in front of the codes
+    size_t row_bytes() const { return f_dtype == FS_I8 ? (size_t)D + 16 : (size_t)D * (size_t)f_dtype; }
 };
 
 namespace {
 
 constexpr int64_t FS_EMPTY = -1, FS_TOMB = -2;
-constexpr int FS_F16 = 2;                          // f_dtype of a store made by cis_featstore_create_half
 constexpr int64_t FS_MAX_CAP = (int64_t)1 << 36;   // lopq_rerank.hip's IDMAP_MAX_CAP
 constexpr int64_t FS_MAX_BATCH = (int64_t)1 << 30;
 constexpr int FS_CNT_A = 0, FS_CNT_NEW = 1, FS_CNT_ERR = 2, FS_WORDS = 4;  // A: skipped (put) or removed (remove)
@@ -349,7 +357,7 @@ int counted_malloc(void** p, size_t bytes) {
 int fs_grow_rows(cis_featstore* fs, int64_t need, hipStream_t st) {
     if (need <= fs->cap_rows) return CIS_OK;
     const int64_t cap = std::max<int64_t>(need, 2 * fs->cap_rows);
-    const size_t row_bytes = (size_t)fs->D * (size_t)fs->f_dtype;
+    const size_t row_bytes = fs->row_bytes();
     void* nf = nullptr;
     void* ni = nullptr;
     CIS_TRY(counted_malloc(&nf, (size_t)cap * row_bytes + 16));
@@ -488,6 +496,14 @@ extern "C" int cis_featstore_create_half(cis_featstore** out, int D, int64_t res
     return fs_create(out, D, FS_F16, reserve_rows);
 }
 
+extern "C" int cis_featstore_create_int8(cis_featstore** out, int D, int64_t reserve_rows) {
+    CIS_REQUIRE(out != nullptr, "out is NULL");
+    *out = nullptr;
+    CIS_REQUIRE(D > 0 && D <= (1 << 24) && D % 16 == 0, "the width of int8 rows must be a multiple of 16 in [16, 2^24] (D = %d)", D);
+    CIS_REQUIRE(reserve_rows >= 0 && reserve_rows <= FS_MAX_CAP / 8, "bad reserve_rows");
+    return fs_create(out, D, FS_I8, reserve_rows);
+}
+
 extern "C" void cis_featstore_destroy(cis_featstore* fs) {
     if (!fs) return;
     (void)hipSetDevice(fs->device);
@@ -544,8 +560,10 @@ extern "C" int cis_featstore_put_dev(cis_featstore* fs, const int64_t* d_ids, co
                        (const uint32_t*)s.rank, nb, fs->n, fs->cap_rows, rows, fs->row_ids, s.job_src, s.job_dst, cnt);
     if (fs->f_dtype == FS_F16)
         CIS_TRY(cis_fs_half_scatter(d_feats, fs->feats, fs->D, s.job_src, s.job_dst, n, st));
+    else if (fs->f_dtype == FS_I8)
+        CIS_TRY(cis_fs_int8_scatter(d_feats, fs->feats, fs->D, s.job_src, s.job_dst, n, st));
     else
-        launch_copy<false>(d_feats, fs->feats, (int64_t)fs->D * fs->f_dtype, s.job_src, s.job_dst, n, st);
+        launch_copy<false>(d_feats, fs->feats, (int64_t)fs->row_bytes(), s.job_src, s.job_dst, n, st);
     CIS_CHECK_HIP(hipGetLastError());
     CIS_TRY(fs_read_counters(fs, st));
     const int64_t added = fs->h_cnt[FS_CNT_NEW];
@@ -578,7 +596,7 @@ extern "C" int cis_featstore_remove_dev(cis_featstore* fs, const int64_t* d_ids,
     CIS_TRY(cis_seg_sort_u64(s.sort_tmp, &sort_bytes, s.skey, s.sorted, s.skey, s.svals, n, 1, s.seg, s.seg + 1, st));
     hipLaunchKernelGGL(k_fs_rm_plan, g, b, 0, st, (const uint64_t*)s.sorted, nb, fs->n, (const int64_t*)keys, rows, fs->cap, fs->row_ids, s.job_src,
                        s.job_dst, cnt);
-    launch_copy<false>(fs->feats, fs->feats, (int64_t)fs->D * fs->f_dtype, s.job_src, s.job_dst, n, st);
+    launch_copy<false>(fs->feats, fs->feats, (int64_t)fs->row_bytes(), s.job_src, s.job_dst, n, st);
     CIS_CHECK_HIP(hipGetLastError());
     CIS_TRY(fs_read_counters(fs, st));
     const int64_t k = fs->h_cnt[FS_CNT_A];
@@ -605,8 +623,10 @@ extern "C" int cis_featstore_get_dev(cis_featstore* fs, const int64_t* d_ids, in
     CIS_TRY(cis_idmap_lookup_dev(fs->keys.as<int64_t>(), fs->rows.as<int64_t>(), fs->cap, fs->n, d_ids, m, out_rows, st));
     if (fs->f_dtype == FS_F16)
         CIS_TRY(cis_fs_half_gather(fs->feats, d_out_feats, fs->D, out_rows, m, st));
+    else if (fs->f_dtype == FS_I8)
+        CIS_TRY(cis_fs_int8_gather(fs->feats, d_out_feats, fs->D, out_rows, m, st));
     else
-        launch_copy<true>(fs->feats, d_out_feats, (int64_t)fs->D * fs->f_dtype, out_rows, nullptr, m, st);
+        launch_copy<true>(fs->feats, d_out_feats, (int64_t)fs->row_bytes(), out_rows, nullptr, m, st);
     CIS_CHECK_HIP(hipGetLastError());
     return CIS_OK;
 }
@@ -617,9 +637,12 @@ extern "C" int cis_featstore_rows_dev(cis_featstore* fs, int64_t first, int64_t 
                 (long long)first, (long long)first, (long long)count, (long long)fs->n);
     if (count == 0) return CIS_OK;
     CIS_TRY(fs_ready(fs));
-    const size_t row_bytes = (size_t)fs->D * (size_t)fs->f_dtype;
+    const size_t row_bytes = fs->row_bytes();
     if (d_out_feats && fs->f_dtype == FS_F16) {
         CIS_TRY(cis_fs_half_gather((const unsigned char*)fs->feats + (size_t)first * row_bytes, d_out_feats, fs->D, nullptr, count, (hipStream_t)stream));
+        CIS_CHECK_HIP(hipGetLastError());
+    } else if (d_out_feats && fs->f_dtype == FS_I8) {
+        CIS_TRY(cis_fs_int8_gather((const unsigned char*)fs->feats + (size_t)first * row_bytes, d_out_feats, fs->D, nullptr, count, (hipStream_t)stream));
         CIS_CHECK_HIP(hipGetLastError());
     } else if (d_out_feats)
         CIS_CHECK_HIP(hipMemcpyAsync(d_out_feats, (const unsigned char*)fs->feats + (size_t)first * row_bytes, (size_t)count * row_bytes,

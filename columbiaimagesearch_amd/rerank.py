@@ -213,24 +213,33 @@ class FeatureStore(object):
     `dtype` is the type at the interface: what put_dev takes, what get_dev / rows_dev return, and the type of the queries.
     `storage` is what a row occupies in HBM: None (the same as dtype) or torch.float16 with dtype float32 and D % 8 == 0
     (cis_featstore_create_half; csrc/feat_half.hip).  A float16 store rounds every row to nearest even on the way in, so get_dev
-    hands back the ROUNDED row, widened; 1M x 4096 features are 8 GB instead of 16, and the re-rank reads half the bytes."""
+    hands back the ROUNDED row, widened; 1M x 4096 features are 8 GB instead of 16, and the re-rank reads half the bytes.
+    Or torch.int8 with dtype float32 and D % 16 == 0 (cis_featstore_create_int8; csrc/feat_int8.hip): a row is 16 + D bytes, a
+    float32 scale s = max|x| / 127 and the codes clip(rint(x / s), -127, 127), so get_dev hands back the QUANTISED row c * s (about
+    7 bits of every component relative to the row's largest; a row with a non-finite component reads back as NaN and keeps its
+    ADC distance in a re-rank).  `search_exact` does not read int8 rows."""
 
     def __init__(self, D, dtype, reserve=0, device=None, storage=None):
         import torch
         if dtype not in (torch.float32, torch.float64):
             raise ValueError("dtype must be torch.float32 or torch.float64")
         if storage is not None and storage != dtype:
-            if storage != torch.float16 or dtype != torch.float32 or int(D) % 8 != 0:
-                raise ValueError("storage must be None, the dtype itself, or torch.float16 with dtype torch.float32 and D % 8 == 0")
+            width = {torch.float16: 8, torch.int8: 16}.get(storage)
+            if width is None or dtype != torch.float32 or int(D) % width != 0:
+                raise ValueError("storage must be None, the dtype itself, or with dtype torch.float32 torch.float16 (D % 8 == 0) "
+                                 "or torch.int8 (D % 16 == 0)")
         self.D, self.dtype = int(D), dtype
         self.storage = dtype if storage is None else storage
         self._half = self.storage == torch.float16
+        self._int8 = self.storage == torch.int8
         self._code = _lib.CIS_F32 if dtype == torch.float32 else _lib.CIS_F64
         self._fs = None
         h = _lib.ctypes.c_void_p()
         # (the library comes first: without a GPU this is its loud failure, not torch's)
         if self._half:
             _lib.check(_lib.lib().cis_featstore_create_half(_lib.ctypes.byref(h), self.D, int(reserve)))
+        elif self._int8:
+            _lib.check(_lib.lib().cis_featstore_create_int8(_lib.ctypes.byref(h), self.D, int(reserve)))
         else:
             _lib.check(_lib.lib().cis_featstore_create(_lib.ctypes.byref(h), self.D, self._code, int(reserve)))
         self._fs = h
@@ -359,6 +368,13 @@ class FeatureStore(object):
                                                    torch.cuda.current_stream(ids.device).cuda_stream))
         return out
 
+    def _rerank_entry(self, L_, which):
+        """cis_rerank_<which>_dev for the rows as they are stored, called as fn(feats, n, D, ...)."""
+        if self._half or self._int8:
+            return getattr(L_, "cis_rerank_%s_%s_dev" % (which, "half" if self._half else "int8"))
+        plain = getattr(L_, "cis_rerank_%s_dev" % which)
+        return lambda f, *a: plain(f, self._code, *a)
+
     def rerank_dev(self, q, ids, adc, rerank_nb=None, max_returned=None, near_dup_th=None, out=None):
         """ResidentFeatures.rerank_dev on the store's rows and table as they are now (cis_featstore_view, fetched anew on every
         call): the same kernel, the same results.  A result whose id is not stored keeps its ADC distance."""
@@ -386,7 +402,7 @@ class FeatureStore(object):
                 raise ValueError("out[%r] must be a contiguous %s tensor of shape %r on the GPU" % (k, str(dt).split(".")[-1], shp))
         feats, _, keys, rows, cap, n = self._view()
         L_ = _lib.lib()
-        select = (lambda f, *a: L_.cis_rerank_select_half_dev(f, *a)) if self._half else (lambda f, *a: L_.cis_rerank_select_dev(f, self._code, *a))
+        select = self._rerank_entry(L_, "select")
         _lib.check(select(
             feats, n, self.D, keys, rows, cap, q.data_ptr(), nq, ids.data_ptr(), adc.data_ptr(), L, nb,
             int(max_returned or 0), 0 if near_dup_th is None else 1, 0.0 if near_dup_th is None else float(near_dup_th),
@@ -417,7 +433,7 @@ class FeatureStore(object):
         true_d = torch.empty(n_rec, dtype=torch.float64, device=q.device)
         feats, _, keys, rows, cap, n = self._view()
         L_ = _lib.lib()
-        packed = (lambda f, *a: L_.cis_rerank_packed_half_dev(f, *a)) if self._half else (lambda f, *a: L_.cis_rerank_packed_dev(f, self._code, *a))
+        packed = self._rerank_entry(L_, "packed")
         _lib.check(packed(feats, n, self.D, keys, rows, cap, q.data_ptr(), nq, recs.data_ptr(), n_rec, off.data_ptr(), cnt.data_ptr(),
                           nb, true_d.data_ptr(), torch.cuda.current_stream(q.device).cuda_stream))
         return true_d
@@ -429,6 +445,9 @@ class FeatureStore(object):
         import torch
         if not (q.is_cuda and q.is_contiguous() and q.dim() == 2 and q.dtype in (torch.float32, torch.float64) and q.shape[1] == self.D):
             raise ValueError("q must be a contiguous float32/float64 [nq, D] tensor on the GPU with the features' width")
+        if self._int8:
+            raise ValueError("search_exact does not read storage=torch.int8 rows (the prefilter's error bound is not proven for scaled "
+                             "codes): search the rows of get_dev / rows_dev, or keep a storage=torch.float16 store")
         nq, k = int(q.shape[0]), int(k)
         rows = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=q.device)
         dists = torch.empty((nq, max(k, 0)), dtype=torch.float64, device=q.device)

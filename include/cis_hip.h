@@ -366,6 +366,24 @@ int cis_rerank_packed_half_dev(const void* d_feats, int64_t n_feats, int D, cons
                                int64_t map_cap, const void* d_q, int nq, const cis_hit* d_recs, int64_t n_rec,
                                const int64_t* d_off /* [nq] */, const int32_t* d_cnt /* [nq] */, int nb, double* d_true, void* stream);
 
+/* The same two calls on int8 feature rows (csrc/feat_int8.hip; searcher_lopqhbase.py:864-912, :975-1017): d_feats is the view of a
+ * store made by cis_featstore_create_int8, n_feats rows of 16 + D bytes each -- the row's float32 scale s at byte 0, zeros in bytes
+ * 4 .. 15, then the D codes -- and d_q stays float32 [nq][D]; D % 16 == 0 and both 16-byte aligned (anything else: CIS_EINVAL).  Every
+ * other argument, every check (nb > 1024 is CIS_EINVAL), the outputs and the padding are the float16 sibling's.
+ * The distance: df = fma(-(float)c, s, q), one rounding of q - c s, and acc = fma(df, df, acc) in float32 (a row is given to a group
+ * of G lanes, G the power of two in [4, 64] that covers its D / 16 sixteen-byte words; lane l owns the codes 16 (l + G t) .. + 15,
+ * t = 0, 1, ..., with one accumulator for its even and one for its odd elements, added at the end), the lanes of the group fold with
+ * the __shfl_xor butterfly G / 2 ... 1, and the result is (double) of the correctly rounded float32 square root:
+ * |d - d_exact| <= (D / 2 + 8) 2^-24 d_exact against the dequantised row.  A NaN result (a row whose scale is NaN) and a result
+ * without a stored row keep the ADC distance (select) / are NaN (packed). */
+int cis_rerank_select_int8_dev(const void* d_feats, int64_t n_feats, int D, const int64_t* d_map_keys, const int64_t* d_map_rows,
+                               int64_t map_cap, const void* d_q, int nq, const int64_t* d_ids, const double* d_adc, int L, int nb,
+                               int max_returned, int use_th, double near_dup_th, int64_t* d_out_ids, double* d_out_dists,
+                               int32_t* d_out_src, int32_t* d_n_kept, void* stream);
+int cis_rerank_packed_int8_dev(const void* d_feats, int64_t n_feats, int D, const int64_t* d_map_keys, const int64_t* d_map_rows,
+                               int64_t map_cap, const void* d_q, int nq, const cis_hit* d_recs, int64_t n_rec,
+                               const int64_t* d_off /* [nq] */, const int32_t* d_cnt /* [nq] */, int nb, double* d_true, void* stream);
+
 /* A feature store that lives in HBM and changes by kernels (csrc/feat_store.hip): the `put` and the fetch of the reference's
  * HBase feature table (hbase_indexer_minimal.py:779-831) for the exact re-rank above, addressed by the index's device ids.  The
  * store owns a feature matrix [rows][D] in f_dtype (4 = float32, 8 = float64), the row -> id column, and an id -> row table with
@@ -405,10 +423,20 @@ int cis_rerank_packed_half_dev(const void* d_feats, int64_t n_feats, int D, cons
  * above works on such a handle: put reads float32 rows and rounds them to nearest even on the way in (subnormals kept, overflow to
  * +-inf, NaN to NaN: numpy's astype(float16) bit for bit), get and rows write float32, the stored halves widened (so a row read back
  * is the ROUNDED row), remove moves the float16 rows, and the view hands out the float16 matrix: for cis_rerank_select_half_dev,
- * cis_rerank_packed_half_dev and cis_exact_knn_half_dev. */
+ * cis_rerank_packed_half_dev and cis_exact_knn_half_dev.
+ *
+ * cis_featstore_create_int8 (hbase_indexer_minimal.py:779-831 as well): a store whose rows are int8 codes with a per-row scale in
+ * HBM, 16 + D bytes each (the float32 scale s at byte 0, zeros in bytes 4 .. 15, then the codes; rows 16-byte aligned), behind a
+ * float32 interface; D % 16 == 0 (anything else: CIS_EINVAL).  Every call above works on such a handle.  put reads float32 rows and
+ * quantises them: m = max |x_i|, s = m / 127 (float32, IEEE division), c_i = clip(rint(x_i / s), -127, 127) (float32 division, round
+ * half to even; -128 is never stored); a row with s == 0 (a zero row) stores zero codes, a row with a non-finite component stores
+ * s = NaN and zero codes.  get and rows write float32, (float)c_i * s (so a row read back is the QUANTISED row, and NaN throughout
+ * for a NaN scale), remove moves the rows with their scales, and the view hands out the rows as they lie: for
+ * cis_rerank_select_int8_dev and cis_rerank_packed_int8_dev.  cis_exact_knn_dev does not read such rows. */
 typedef struct cis_featstore cis_featstore;
 int cis_featstore_create(cis_featstore** out, int D, int f_dtype, int64_t reserve_rows);
 int cis_featstore_create_half(cis_featstore** out, int D, int64_t reserve_rows);
+int cis_featstore_create_int8(cis_featstore** out, int D, int64_t reserve_rows);
 void cis_featstore_destroy(cis_featstore* fs);
 int64_t cis_featstore_size(cis_featstore* fs);
 int cis_featstore_reserve(cis_featstore* fs, int64_t rows, void* stream);

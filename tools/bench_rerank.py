@@ -23,6 +23,12 @@ kernels alternate in one process, and five such runs are reported, each figure t
 Exit status 1 unless every float16 run at D = 4096 lies below every float32 run.
 
     python tools/bench_rerank.py --storage f16 [--out profiles/rerank_half.txt]
+
+--storage i8: the same protocol with a third store, FeatureStore(storage=torch.int8) (csrc/feat_int8.hip, k_rerank_select_int8): the
+rows are quantised once, and all three stores are fed the dequantised rows (the float16 store rounds them once more), so the three
+kernels, alternating in one process, rank the same items.  A report: the exit status is 0 whatever comes out.
+
+    python tools/bench_rerank.py --storage i8 [--out profiles/rerank_int8.txt]
 """
 import argparse
 import json
@@ -100,10 +106,16 @@ def storage_leg(args, dev, commit):
         s, feats, q = build(fixture, gen, n, chunk_n, dev)
         D = int(feats.shape[1])
         stores = (FeatureStore(D, torch.float32, reserve=n), FeatureStore(D, torch.float32, reserve=n, storage=torch.float16))
+        if args.storage == "i8":
+            stores += (FeatureStore(D, torch.float32, reserve=n, storage=torch.int8),)
         for a in range(0, n, chunk_n):
             ids = torch.arange(a, a + chunk_n, dtype=torch.int64, device=dev)
-            rounded = feats[a:a + chunk_n].half().float()
-            for st in stores:
+            if args.storage == "i8":
+                stores[2].put_dev(ids, feats[a:a + chunk_n].contiguous())
+                rounded = stores[2].get_dev(ids)[0]
+            else:
+                rounded = feats[a:a + chunk_n].half().float()
+            for st in stores[:2]:
                 st.put_dev(ids, rounded)
         del feats
         r = s.search_batch_dev(q, quota=QUOTA, limit=LIMIT)
@@ -120,9 +132,20 @@ def storage_leg(args, dev, commit):
                 "float32_gathered_over_peak_8TBs": gathered * 4 / sorted(t32)[2] / HBM_PEAK,
                 "float16_gathered_over_peak_8TBs": gathered * 2 / sorted(t16)[2] / HBM_PEAK, "reps_per_run": [runs[0][0][1], runs[0][1][1]],
                 "same_order": same_ids, "largest_relative_distance_difference": worst, "commit": commit, "device": torch.cuda.get_device_name(0)}
+        if args.storage == "i8":
+            t8 = [run[2][0] for run in runs]
+            row8 = float(NQ) * LIMIT * (D + 16)
+            line.update({"int8_kernel_s": t8, "float16_over_int8_medians": sorted(t16)[2] / sorted(t8)[2],
+                         "float32_over_int8_medians": sorted(t32)[2] / sorted(t8)[2],
+                         "every_int8_run_below_every_float16_run": max(t8) < min(t16), "no_int8_run_above_a_float32_run": max(t8) <= min(t32),
+                         "int8_gathered_bytes_per_s": row8 / sorted(t8)[2], "int8_gathered_over_peak_8TBs": row8 / sorted(t8)[2] / HBM_PEAK,
+                         "int8_same_order_as_float32": bool((outs[0]["ids"] == outs[2]["ids"]).all().item()),
+                         "int8_largest_relative_distance_difference": float(((outs[0]["dists"] - outs[2]["dists"]).abs()
+                                                                             / outs[0]["dists"].clamp_min(1e-30)).nan_to_num(0.0).max().item())})
+            line["reps_per_run"].append(runs[0][2][1])
         print(json.dumps(line), flush=True)
         lines.append(line)
-        ok = ok and (D != 4096 or line["every_float16_run_below_every_float32_run"])
+        ok = ok and (args.storage == "i8" or D != 4096 or line["every_float16_run_below_every_float32_run"])
         for st in stores:
             st.close()
         s.close()
@@ -130,6 +153,9 @@ def storage_leg(args, dev, commit):
         torch.cuda.empty_cache()
     if args.out:
         with open(args.out, "w") as f:
+            if args.storage == "i8":
+                f.write("# tools/bench_rerank.py --storage i8: as --storage f16 below with a third store of int8 rows (k_rerank_select_int8; 16 + D\n"
+                        "# bytes a row, which is what its gathered bytes count), all three stores fed the dequantised rows.\n")
             f.write("# tools/bench_rerank.py --storage f16: the fused re-rank kernel alone on one search result of %d queries, rerank_nb = %d, on\n"
                     "# float32 rows (k_rerank_select) and on the same rows as float16 (k_rerank_select_half), alternating in one process; five\n"
                     "# runs, each figure the median of repetitions adding up to >= 0.5 s, HIP events; gathered = nq x nb x D x 4 or 2 bytes.\n"
@@ -146,7 +172,8 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--commit", default=None)
     ap.add_argument("--small", action="store_true", help="1/8 of the rows (a quick look)")
-    ap.add_argument("--storage", default=None, choices=["f16"], help="time the re-rank kernel on float16 rows beside the float32 kernel")
+    ap.add_argument("--storage", default=None, choices=["f16", "i8"],
+                    help="time the re-rank kernel on float16 rows (f16), or on float16 and int8 rows (i8), beside the float32 kernel")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     commit = args.commit
