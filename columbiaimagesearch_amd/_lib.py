@@ -150,6 +150,7 @@ _PROTOS = {
     "cis_exact_knn_dev": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_int, c_int64, c_int, c_void_p, c_void_p,
                                   c_void_p]),
     "cis_exact_knn_half_dev": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "cis_exact_knn_int8_dev": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "cis_exact_knn": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_int, c_int64, c_int, c_void_p, c_void_p]),
     "cis_exact_knn_set_mode": (c_int, [c_int]),
     "cis_exact_knn_stats": (c_int, [c_void_p]),

@@ -2,6 +2,7 @@
 // re-rank of lopq_rerank.hip on such rows (searcher_lopqhbase.py:849-912 and :964-1017), and the conversions into and out of the store
 // (the `put` and the fetch of hbase_indexer_minimal.py:779-831).  Stored features are L2-normalised, so a scale per row and 8-bit codes
 // keep about 7 bits of every component relative to the row's largest; a 4096-wide row is 4112 bytes instead of 16 KB.
+// The exact k-NN reads the same rows in place: knn_int8.hip (prefilter on the int8 matrix cores) and the Int8Rows view of lopq_eval.hip.
 //
 // The row: 16 + D bytes, D % 16 == 0, 16-byte aligned.  Word 0 (16 bytes) holds the float32 scale s at byte 0 and zeros behind it,
 // words 1 .. D / 16 the codes, element 16 w + k in byte k of word 1 + w.  The scale travels with the row, so k_fs_copy, the removal and

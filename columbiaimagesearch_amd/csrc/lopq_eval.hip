@@ -35,10 +35,17 @@
 // float16 data (cis_exact_knn_half_dev: the rows of a half feature store) runs through the same kernels with TD = _Float16: float16 ->
 // float32 and -> float64 are exact, so the data is widened while it is staged into sA and while the chain reads it, the matrix-core
 // product stays the float32 one and the bound E holds unchanged ("inputs rounded to float32" costs nothing for such data).
+//
+// int8 data (cis_exact_knn_int8_dev: the rows of an int8 feature store, codes with an in-row scale) is read through the Int8Rows view:
+// the chain, k_finalize and k_exact run on the dequantised row as they run on any other, so the exact-only path serves such rows as it
+// stands.  Their prefilter is a different one, on the int8 matrix cores with a bound of its own: knn_int8.hip.  It fills the same
+// candidate lists, and everything from k_finalize on is shared.
 #include <algorithm>
 #include <mutex>
+#include <type_traits>
 
 #include "common.h"
+#include "knn_int8.h"
 
 namespace {
 
@@ -58,13 +65,47 @@ __device__ __forceinline__ bool lex_less(double da, int64_t ia, double db, int64
     return da < db || (da == db && ia < ib);
 }
 
+// Row views: what the kernels below read the data (and the norms kernel the queries) through.  rows.row(j) is row j, whose [i] is
+// element i widened to float64 and f32(i) the same as float32; rows.from(r) is the view that starts at row r.
+// DenseRows: [n][d] of float, double or _Float16, a row every d elements.
+template <typename T>
+struct DenseRow {
+    const T* __restrict__ p;
+    __device__ __forceinline__ double operator[](int i) const { return (double)p[i]; }
+    __device__ __forceinline__ float f32(int i) const { return (float)p[i]; }
+};
+template <typename T>
+struct DenseRows {
+    const T* base;
+    int d;
+    __device__ __forceinline__ DenseRow<T> row(int64_t j) const { return DenseRow<T>{base + j * d}; }
+    DenseRows from(int64_t r) const { return DenseRows{base + r * d, d}; }
+};
+// Int8Rows: the rows of an int8 feature store as they lie (feat_int8.hip), a row every `stride` = 16 + d bytes: the float32 scale s,
+// 12 zero bytes, the codes.  Element i is the DEQUANTISED value (float)c_i * s, one float32 product -- what cis_featstore_get_dev hands
+// back -- widened; s is read once per row.  Only the chain reads such rows here: their prefilter is knn_int8.hip's.
+struct Int8Row {
+    const signed char* __restrict__ c;
+    float s;
+    __device__ __forceinline__ double operator[](int i) const { return (double)((float)c[i] * s); }
+};
+struct Int8Rows {
+    const unsigned char* base;
+    int64_t stride;
+    __device__ __forceinline__ Int8Row row(int64_t j) const {
+        const unsigned char* p = base + j * stride;
+        return Int8Row{(const signed char*)(p + 16), *(const float*)p};
+    }
+    Int8Rows from(int64_t r) const { return Int8Rows{base + r * stride, stride}; }
+};
+
 // scipy's cdist value: sequential float64 chain, no fused multiply-add (the file is compiled with -ffp-contract=off), then sqrt.
-template <typename TD, typename TQ>
-__device__ __forceinline__ double exact_dist(const TQ* __restrict__ x, const TD* __restrict__ y, int d) {
+template <typename Row, typename TQ>
+__device__ __forceinline__ double exact_dist(const TQ* __restrict__ x, const Row y, int d) {
 #pragma clang fp contract(off)
     double s = 0.0;
     for (int i = 0; i < d; ++i) {
-        const double t = (double)x[i] - (double)y[i];
+        const double t = (double)x[i] - y[i];
         const double p = t * t;
         s = s + p;
     }
@@ -80,16 +121,16 @@ __global__ __launch_bounds__(256) void k_knn_pad(int64_t* __restrict__ idx, doub
 }
 
 // |row|^2 in float64, one wave per row: out64 (queries) or out32 + the maximum over rows as ordered bits (data)
-template <typename T>
-__global__ __launch_bounds__(256) void k_knn_norms(const T* __restrict__ X, int64_t n, int d, double* __restrict__ out64,
+template <typename Rows>
+__global__ __launch_bounds__(256) void k_knn_norms(const Rows X, int64_t n, int d, double* __restrict__ out64,
                                                    float* __restrict__ out32, unsigned long long* __restrict__ max_bits) {
     const int lane = threadIdx.x & 63;
     unsigned long long best = 0;
     for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < n; r += (int64_t)gridDim.x * 4) {
-        const T* x = X + r * d;
+        const auto x = X.row(r);
         double acc = 0.0;
         for (int i = lane; i < d; i += 64) {
-            const double v = (double)x[i];
+            const double v = x[i];
             acc = acc + v * v;
         }
 #pragma unroll
@@ -108,8 +149,8 @@ __global__ __launch_bounds__(256) void k_knn_norms(const T* __restrict__ X, int6
 // query l & 31); result register r of lane l is row (r & 3) + 8 (r >> 2) + 4 (l >> 5) of query l & 31.  The four waves of a
 // workgroup own 32 rows each and share the 64 queries.  The next stage's operands are fetched into registers while the matrix
 // cores work on the current one.
-template <typename TD, typename TQ, int EMIT>
-__global__ __launch_bounds__(256) void k_knn_surface(const TD* __restrict__ data, int m2, int d, const TQ* __restrict__ Q, int m1,
+template <typename Rows, typename TQ, int EMIT>
+__global__ __launch_bounds__(256) void k_knn_surface(const Rows data, int m2, int d, const TQ* __restrict__ Q, int m1,
                                                      const float* __restrict__ ny32, int S, float* __restrict__ gmin,
                                                      const float* __restrict__ thr, int* __restrict__ cnt,
                                                      int64_t* __restrict__ cand, int W, int cap, int64_t base) {
@@ -128,7 +169,7 @@ __global__ __launch_bounds__(256) void k_knn_surface(const TD* __restrict__ data
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             const int row = tile * BM + lr + 8 * i;
-            ra[i] = (row < m2 && k < d) ? (float)data[(int64_t)row * d + k] : 0.f;
+            ra[i] = (row < m2 && k < d) ? data.row(row).f32(k) : 0.f;
         }
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
@@ -266,8 +307,8 @@ __device__ __forceinline__ int take_current(const int64_t* oi, const double* od,
     return *s_n;
 }
 
-template <typename TD, typename TQ>
-__global__ __launch_bounds__(256) void k_knn_finalize(const TD* __restrict__ data, int d, const TQ* __restrict__ Q, int k, int64_t base,
+template <typename Rows, typename TQ>
+__global__ __launch_bounds__(256) void k_knn_finalize(const Rows data, int d, const TQ* __restrict__ Q, int k, int64_t base,
                                                       const int* __restrict__ cnt, int cap, int W, int64_t* __restrict__ cand,
                                                       double* __restrict__ cdist, int* __restrict__ flag, int64_t* __restrict__ out_idx,
                                                       double* __restrict__ out_dist) {
@@ -280,7 +321,7 @@ __global__ __launch_bounds__(256) void k_knn_finalize(const TD* __restrict__ dat
     }
     int64_t* bi = cand + (int64_t)q * W;
     double* bd = cdist + (int64_t)q * W;
-    for (int i = threadIdx.x; i < n; i += 256) bd[i] = exact_dist(Q + (int64_t)q * d, data + (bi[i] - base) * d, d);
+    for (int i = threadIdx.x; i < n; i += 256) bd[i] = exact_dist(Q + (int64_t)q * d, data.row(bi[i] - base), d);
     const int total = take_current(out_idx + (int64_t)q * k, out_dist + (int64_t)q * k, k, bd, bi, n, &s_n);
     rank_and_write(bd, bi, total, k, out_idx + (int64_t)q * k, out_dist + (int64_t)q * k);
 }
@@ -288,8 +329,8 @@ __global__ __launch_bounds__(256) void k_knn_finalize(const TD* __restrict__ dat
 // The exact-only path: one workgroup per flagged query, one row per lane and step.  Rows below the running threshold (the k-th
 // entry of the last compaction) are collected in buf [W]; when fewer than 256 free places are left the list is ranked, its first
 // k entries kept (through the output row, which is free: the caller's entries were moved into buf first).
-template <typename TD, typename TQ>
-__global__ __launch_bounds__(256) void k_knn_exact(const TD* __restrict__ data, int m2, int d, const TQ* __restrict__ Q, int k, int64_t base,
+template <typename Rows, typename TQ>
+__global__ __launch_bounds__(256) void k_knn_exact(const Rows data, int m2, int d, const TQ* __restrict__ Q, int k, int64_t base,
                                                    const int* __restrict__ flag, int W, int64_t* __restrict__ cand, double* __restrict__ cdist,
                                                    int64_t* __restrict__ out_idx, double* __restrict__ out_dist) {
     __shared__ int s_n;
@@ -307,7 +348,7 @@ __global__ __launch_bounds__(256) void k_knn_exact(const TD* __restrict__ data, 
     for (int row0 = 0; row0 < m2; row0 += 256) {
         const int row = row0 + threadIdx.x;
         if (row < m2) {
-            const double dist = exact_dist(x, data + (int64_t)row * d, d);
+            const double dist = exact_dist(x, data.row(row), d);
             const int64_t gi = base + row;
             if (!has_thr || lex_less(dist, gi, thr_d, thr_i)) {
                 const int pos = atomicAdd(&s_n, 1);
@@ -342,14 +383,15 @@ __global__ __launch_bounds__(256) void k_knn_exact(const TD* __restrict__ data, 
 struct KnnWs {
     std::mutex mu;
     DevBuf cand, cdist, cnt, flag, thr, xn2, ny32, ymax, gmin;
+    DevBuf digits, qe;  // int8 rows: the queries' digits and exponents (knn_int8.hip); ny32 then holds (ny32, scale) pairs, ymax both maxima
 };
 KnnWs g_ws;
 int g_mode = 0;  // 0: prefilter + exact re-check, 1: the exact-only path for every query
 int g_last_m1 = 0;        // the last internal pass: its queries, and whether the prefilter ran (cis_exact_knn_stats)
 bool g_last_fast = false;
 
-template <typename TD, typename TQ>
-int knn_chunk(const TD* data, int m2, int d, const TQ* Q, int m1, int k, int64_t base, int64_t* d_idx, double* d_dist, hipStream_t st) {
+template <typename Rows, typename TQ>
+int knn_chunk(const Rows data, int m2, int d, const TQ* Q, int m1, int k, int64_t base, int64_t* d_idx, double* d_dist, hipStream_t st) {
     KnnWs& w = g_ws;
     const int W = 4 * k + 512, cap = W - k;
     CIS_TRY(w.cand.reserve((size_t)m1 * W * 8));
@@ -366,41 +408,52 @@ int knn_chunk(const TD* data, int m2, int d, const TQ* Q, int m1, int k, int64_t
         CIS_TRY(w.cnt.reserve((size_t)m1 * 4));
         CIS_TRY(w.thr.reserve((size_t)m1 * 4));
         CIS_TRY(w.xn2.reserve((size_t)m1 * 8));
-        CIS_TRY(w.ny32.reserve((size_t)m2 * 4));
-        CIS_TRY(w.ymax.reserve(8));
+        CIS_TRY(w.ny32.reserve((size_t)m2 * 8));
+        CIS_TRY(w.ymax.reserve(16));
         CIS_TRY(w.gmin.reserve((size_t)m1 * G * 4));
         CIS_CHECK_HIP(hipMemsetAsync(w.cnt.p, 0, (size_t)m1 * 4, st));
         CIS_CHECK_HIP(hipMemsetAsync(w.flag.p, 0, (size_t)m1 * 4, st));
-        CIS_CHECK_HIP(hipMemsetAsync(w.ymax.p, 0, 8, st));
-        hipLaunchKernelGGL(k_knn_norms<TD>, dim3((unsigned)std::min<int64_t>(ceil_div(m2, 4), 4096)), dim3(256), 0, st, data, (int64_t)m2, d,
-                           (double*)nullptr, w.ny32.as<float>(), w.ymax.as<unsigned long long>());
-        hipLaunchKernelGGL(k_knn_norms<TQ>, dim3((unsigned)std::min<int64_t>(ceil_div(m1, 4), 4096)), dim3(256), 0, st, Q, (int64_t)m1, d,
-                           w.xn2.as<double>(), (float*)nullptr, (unsigned long long*)nullptr);
-        const dim3 grid((unsigned)nqt, (unsigned)S);
-        hipLaunchKernelGGL((k_knn_surface<TD, TQ, 0>), grid, dim3(256), 0, st, data, m2, d, Q, m1, w.ny32.as<float>(), S, w.gmin.as<float>(),
-                           (const float*)nullptr, (int*)nullptr, (int64_t*)nullptr, W, cap, base);
-        hipLaunchKernelGGL(k_knn_select, dim3((unsigned)m1), dim3(256), (size_t)G * 4, st, w.gmin.as<float>(), G, k, d, w.xn2.as<double>(),
-                           w.ymax.as<unsigned long long>(), w.thr.as<float>());
-        hipLaunchKernelGGL((k_knn_surface<TD, TQ, 1>), grid, dim3(256), 0, st, data, m2, d, Q, m1, w.ny32.as<float>(), S, (float*)nullptr,
-                           w.thr.as<float>(), w.cnt.as<int>(), w.cand.as<int64_t>(), W, cap, base);
-        hipLaunchKernelGGL((k_knn_finalize<TD, TQ>), dim3((unsigned)m1), dim3(256), 0, st, data, d, Q, k, base, w.cnt.as<int>(), cap, W,
+        CIS_CHECK_HIP(hipMemsetAsync(w.ymax.p, 0, 16, st));
+        hipLaunchKernelGGL(k_knn_norms<DenseRows<TQ>>, dim3((unsigned)std::min<int64_t>(ceil_div(m1, 4), 4096)), dim3(256), 0, st,
+                           DenseRows<TQ>{Q, d}, (int64_t)m1, d, w.xn2.as<double>(), (float*)nullptr, (unsigned long long*)nullptr);
+        if constexpr (std::is_same<Rows, Int8Rows>::value) {  // the prefilter on the int8 matrix cores
+            CIS_TRY(w.digits.reserve(knn_i8_digit_bytes(m1, d)));
+            CIS_TRY(w.qe.reserve((size_t)nqt * BN * 4));
+            KnnI8Args a;
+            a.rows = data.base; a.m2 = m2; a.d = d; a.Q = Q; a.q_f64 = sizeof(TQ) == 8; a.m1 = m1; a.k = k; a.S = S; a.W = W; a.cap = cap;
+            a.base = base; a.digits = w.digits.p; a.qe = w.qe.as<int>(); a.xn2 = w.xn2.as<double>(); a.stat = w.ny32.as<float>();
+            a.maxima = w.ymax.as<unsigned long long>(); a.gmin = w.gmin.as<float>(); a.thr = w.thr.as<float>(); a.cnt = w.cnt.as<int>();
+            a.cand = w.cand.as<int64_t>();
+            CIS_TRY(cis_knn_i8_prefilter(a, st));
+        } else {
+            hipLaunchKernelGGL(k_knn_norms<Rows>, dim3((unsigned)std::min<int64_t>(ceil_div(m2, 4), 4096)), dim3(256), 0, st, data, (int64_t)m2, d,
+                               (double*)nullptr, w.ny32.as<float>(), w.ymax.as<unsigned long long>());
+            const dim3 grid((unsigned)nqt, (unsigned)S);
+            hipLaunchKernelGGL((k_knn_surface<Rows, TQ, 0>), grid, dim3(256), 0, st, data, m2, d, Q, m1, w.ny32.as<float>(), S, w.gmin.as<float>(),
+                               (const float*)nullptr, (int*)nullptr, (int64_t*)nullptr, W, cap, base);
+            hipLaunchKernelGGL(k_knn_select, dim3((unsigned)m1), dim3(256), (size_t)G * 4, st, w.gmin.as<float>(), G, k, d, w.xn2.as<double>(),
+                               w.ymax.as<unsigned long long>(), w.thr.as<float>());
+            hipLaunchKernelGGL((k_knn_surface<Rows, TQ, 1>), grid, dim3(256), 0, st, data, m2, d, Q, m1, w.ny32.as<float>(), S, (float*)nullptr,
+                               w.thr.as<float>(), w.cnt.as<int>(), w.cand.as<int64_t>(), W, cap, base);
+        }
+        hipLaunchKernelGGL((k_knn_finalize<Rows, TQ>), dim3((unsigned)m1), dim3(256), 0, st, data, d, Q, k, base, w.cnt.as<int>(), cap, W,
                            w.cand.as<int64_t>(), w.cdist.as<double>(), w.flag.as<int>(), d_idx, d_dist);
     } else {
         CIS_CHECK_HIP(hipMemsetAsync(w.flag.p, 0xff, (size_t)m1 * 4, st));
     }
-    hipLaunchKernelGGL((k_knn_exact<TD, TQ>), dim3((unsigned)m1), dim3(256), 0, st, data, m2, d, Q, k, base, w.flag.as<int>(), W,
+    hipLaunchKernelGGL((k_knn_exact<Rows, TQ>), dim3((unsigned)m1), dim3(256), 0, st, data, m2, d, Q, k, base, w.flag.as<int>(), W,
                        w.cand.as<int64_t>(), w.cdist.as<double>(), d_idx, d_dist);
     CIS_CHECK_HIP(hipGetLastError());
     return CIS_OK;
 }
 
-template <typename TD, typename TQ>
-int knn_all(const TD* data, int64_t m2, int d, const TQ* Q, int m1, int k, int64_t base, int64_t* d_idx, double* d_dist, hipStream_t st) {
+template <typename Rows, typename TQ>
+int knn_all(const Rows data, int64_t m2, int d, const TQ* Q, int m1, int k, int64_t base, int64_t* d_idx, double* d_dist, hipStream_t st) {
     for (int q0 = 0; q0 < m1; q0 += Q_CHUNK) {
         const int mq = std::min(Q_CHUNK, m1 - q0);
         for (int64_t r0 = 0; r0 < m2; r0 += ROW_CHUNK) {
             const int mr = (int)std::min<int64_t>(ROW_CHUNK, m2 - r0);
-            CIS_TRY(knn_chunk(data + r0 * d, mr, d, Q + (int64_t)q0 * d, mq, k, base + r0, d_idx + (int64_t)q0 * k, d_dist + (int64_t)q0 * k, st));
+            CIS_TRY(knn_chunk(data.from(r0), mr, d, Q + (int64_t)q0 * d, mq, k, base + r0, d_idx + (int64_t)q0 * k, d_dist + (int64_t)q0 * k, st));
         }
     }
     return CIS_OK;
@@ -444,8 +497,14 @@ extern "C" int cis_exact_knn_stats(int64_t stats[3]) {
     return CIS_OK;
 }
 
-// The driver of both device entry points, their dtypes checked.  data_dtype: bytes per element, KNN_F16 = 2 for float16.
-constexpr int KNN_F16 = 2;
+// The driver of the device entry points, their dtypes checked.  data_dtype: bytes per element, KNN_F16 = 2 for float16, KNN_I8 = 1 for
+// the rows of an int8 feature store.
+constexpr int KNN_F16 = 2, KNN_I8 = 1;
+template <typename T, typename TQ>
+static int knn_dense(const void* d_data, int64_t m2, int d, const void* d_q, int m1, int k, int64_t base, int64_t* d_idx, double* d_dist,
+                     hipStream_t st) {
+    return knn_all(DenseRows<T>{(const T*)d_data, d}, m2, d, (const TQ*)d_q, m1, k, base, d_idx, d_dist, st);
+}
 static int knn_run(const void* d_data, int data_dtype, int64_t m2, int d, const void* d_q, int q_dtype, int m1, int k, int64_t base,
                    int accumulate, int64_t* d_idx, double* d_dist, void* stream) {
     CIS_REQUIRE(m1 == 0 || (d_q && d_idx && d_dist), "NULL query or result buffer");
@@ -460,12 +519,17 @@ static int knn_run(const void* d_data, int data_dtype, int64_t m2, int d, const 
         CIS_CHECK_HIP(hipGetLastError());
     }
     if (m2 == 0) return CIS_OK;
-    if (data_dtype == KNN_F16 && q_dtype == CIS_F32) return knn_all((const _Float16*)d_data, m2, d, (const float*)d_q, m1, k, base, d_idx, d_dist, st);
-    if (data_dtype == KNN_F16) return knn_all((const _Float16*)d_data, m2, d, (const double*)d_q, m1, k, base, d_idx, d_dist, st);
-    if (data_dtype == CIS_F32 && q_dtype == CIS_F32) return knn_all((const float*)d_data, m2, d, (const float*)d_q, m1, k, base, d_idx, d_dist, st);
-    if (data_dtype == CIS_F32) return knn_all((const float*)d_data, m2, d, (const double*)d_q, m1, k, base, d_idx, d_dist, st);
-    if (q_dtype == CIS_F32) return knn_all((const double*)d_data, m2, d, (const float*)d_q, m1, k, base, d_idx, d_dist, st);
-    return knn_all((const double*)d_data, m2, d, (const double*)d_q, m1, k, base, d_idx, d_dist, st);
+    if (data_dtype == KNN_I8) {
+        const Int8Rows rows{(const unsigned char*)d_data, 16 + (int64_t)d};
+        if (q_dtype == CIS_F32) return knn_all(rows, m2, d, (const float*)d_q, m1, k, base, d_idx, d_dist, st);
+        return knn_all(rows, m2, d, (const double*)d_q, m1, k, base, d_idx, d_dist, st);
+    }
+    if (data_dtype == KNN_F16 && q_dtype == CIS_F32) return knn_dense<_Float16, float>(d_data, m2, d, d_q, m1, k, base, d_idx, d_dist, st);
+    if (data_dtype == KNN_F16) return knn_dense<_Float16, double>(d_data, m2, d, d_q, m1, k, base, d_idx, d_dist, st);
+    if (data_dtype == CIS_F32 && q_dtype == CIS_F32) return knn_dense<float, float>(d_data, m2, d, d_q, m1, k, base, d_idx, d_dist, st);
+    if (data_dtype == CIS_F32) return knn_dense<float, double>(d_data, m2, d, d_q, m1, k, base, d_idx, d_dist, st);
+    if (q_dtype == CIS_F32) return knn_dense<double, float>(d_data, m2, d, d_q, m1, k, base, d_idx, d_dist, st);
+    return knn_dense<double, double>(d_data, m2, d, d_q, m1, k, base, d_idx, d_dist, st);
 }
 
 extern "C" int cis_exact_knn_dev(const void* d_data, int data_dtype, int64_t m2, int d, const void* d_q, int q_dtype, int m1, int k,
@@ -480,6 +544,16 @@ extern "C" int cis_exact_knn_half_dev(const void* d_data, int64_t m2, int d, con
     CIS_REQUIRE(m2 == 0 || d_data, "NULL data buffer");
     if (m1 == 0) return CIS_OK;  // nothing to do: the device is not touched
     return knn_run(d_data, KNN_F16, m2, d, d_q, q_dtype, m1, k, base, accumulate, d_idx, d_dist, stream);
+}
+
+extern "C" int cis_exact_knn_int8_dev(const void* d_rows, int64_t m2, int d, const void* d_q, int q_dtype, int m1, int k, int64_t base,
+                                      int accumulate, int64_t* d_idx, double* d_dist, void* stream) {
+    CIS_TRY(knn_validate(CIS_F32, m2, d, q_dtype, m1, k));  // (the data's type is this entry point's)
+    CIS_REQUIRE(d % 16 == 0 && d <= KNN_I8_MAX_D, "int8 feature rows need d %% 16 == 0 and d <= %d (d = %d)", KNN_I8_MAX_D, d);
+    CIS_REQUIRE(((uintptr_t)d_rows & 15) == 0, "int8 feature rows must be 16-byte aligned");
+    CIS_REQUIRE(m2 == 0 || d_rows, "NULL data buffer");
+    if (m1 == 0) return CIS_OK;  // nothing to do: the device is not touched
+    return knn_run(d_rows, KNN_I8, m2, d, d_q, q_dtype, m1, k, base, accumulate, d_idx, d_dist, stream);
 }
 
 extern "C" int cis_exact_knn(const void* data, int data_dtype, int64_t m2, int d, const void* q, int q_dtype, int m1, int k, int64_t base,

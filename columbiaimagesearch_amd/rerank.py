@@ -217,7 +217,9 @@ class FeatureStore(object):
     Or torch.int8 with dtype float32 and D % 16 == 0 (cis_featstore_create_int8; csrc/feat_int8.hip): a row is 16 + D bytes, a
     float32 scale s = max|x| / 127 and the codes clip(rint(x / s), -127, 127), so get_dev hands back the QUANTISED row c * s (about
     7 bits of every component relative to the row's largest; a row with a non-finite component reads back as NaN and keeps its
-    ADC distance in a re-rank).  `search_exact` does not read int8 rows."""
+    ADC distance in a re-rank).  `search_exact` reads such rows in place (cis_exact_knn_int8_dev; csrc/knn_int8.hip: the prefilter on the
+    int8 matrix cores, the query split into three int8 digits): its distances are scipy's float64 chain on the QUANTISED rows, so the
+    answer is ResidentFeatures(rows_dev()[0]).search_exact's bit for bit, and a NaN row ranks behind every number."""
 
     def __init__(self, D, dtype, reserve=0, device=None, storage=None):
         import torch
@@ -441,19 +443,20 @@ class FeatureStore(object):
     def search_exact(self, q, k):
         """ResidentFeatures.search_exact over the rows [0, len): (ids, dists) [nq, k] numpy arrays ranked by (distance, row), ids
         mapped through the store's id column (-1 / NaN padded).  After a removal the rows are not in insertion order: that is
-        the order exact distance ties are broken in."""
+        the order exact distance ties are broken in.  A float16 or int8 store is searched on its rows as they lie in HBM; the distances
+        are those to the rounded / quantised rows that get_dev hands back."""
         import torch
         if not (q.is_cuda and q.is_contiguous() and q.dim() == 2 and q.dtype in (torch.float32, torch.float64) and q.shape[1] == self.D):
             raise ValueError("q must be a contiguous float32/float64 [nq, D] tensor on the GPU with the features' width")
-        if self._int8:
-            raise ValueError("search_exact does not read storage=torch.int8 rows (the prefilter's error bound is not proven for scaled "
-                             "codes): search the rows of get_dev / rows_dev, or keep a storage=torch.float16 store")
         nq, k = int(q.shape[0]), int(k)
         rows = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=q.device)
         dists = torch.empty((nq, max(k, 0)), dtype=torch.float64, device=q.device)
         feats, _, _, _, _, n = self._view()
         L_ = _lib.lib()
-        knn = (lambda f, *a: L_.cis_exact_knn_half_dev(f, *a)) if self._half else (lambda f, *a: L_.cis_exact_knn_dev(f, self._code, *a))
+        if self._half or self._int8:
+            knn = L_.cis_exact_knn_half_dev if self._half else L_.cis_exact_knn_int8_dev
+        else:
+            knn = lambda f, *a: L_.cis_exact_knn_dev(f, self._code, *a)
         _lib.check(knn(feats, n, self.D, q.data_ptr(), _lib.CIS_F32 if q.dtype == torch.float32 else _lib.CIS_F64, nq, k, 0, 0,
                        rows.data_ptr(), dists.data_ptr(), torch.cuda.current_stream(q.device).cuda_stream))
         table = self.row_ids().cpu().numpy()

@@ -432,7 +432,7 @@ int cis_rerank_packed_int8_dev(const void* d_feats, int64_t n_feats, int D, cons
  * half to even; -128 is never stored); a row with s == 0 (a zero row) stores zero codes, a row with a non-finite component stores
  * s = NaN and zero codes.  get and rows write float32, (float)c_i * s (so a row read back is the QUANTISED row, and NaN throughout
  * for a NaN scale), remove moves the rows with their scales, and the view hands out the rows as they lie: for
- * cis_rerank_select_int8_dev and cis_rerank_packed_int8_dev.  cis_exact_knn_dev does not read such rows. */
+ * cis_rerank_select_int8_dev, cis_rerank_packed_int8_dev and cis_exact_knn_int8_dev. */
 typedef struct cis_featstore cis_featstore;
 int cis_featstore_create(cis_featstore** out, int D, int f_dtype, int64_t reserve_rows);
 int cis_featstore_create_half(cis_featstore** out, int D, int64_t reserve_rows);
@@ -461,11 +461,18 @@ int cis_featstore_view(cis_featstore* fs, const void** d_feats, const int64_t** 
  * cis_exact_knn_set_mode: 0 = float32 matrix-core prefilter with exact re-check (default), 1 = the exact-only path for every query
  * (tests; both give the same answer).
  * cis_exact_knn_half_dev (lopq/lopq/eval.py:7-38 as well): cis_exact_knn_dev on float16 data [m2][d] (the view of a half feature
- * store); the chain runs on the data widened to float64, i.e. scipy's value for data.astype(float64).  Same kernels, same bound. */
+ * store); the chain runs on the data widened to float64, i.e. scipy's value for data.astype(float64).  Same kernels, same bound.
+ * cis_exact_knn_int8_dev (lopq/lopq/eval.py:7-38 as well): the same on the rows of an int8 feature store as they lie in HBM (16 + d
+ * bytes each: the float32 scale s, 12 zero bytes, the codes).  The chain runs on the dequantised row y_i = (float)c_i * s widened to
+ * float64, the value cis_featstore_get_dev hands back: a row with a NaN scale has distance NaN, a zero-scale row is a row of zeros.
+ * The prefilter runs on the int8 matrix cores with the query split into three int8 digits (csrc/knn_int8.hip, which derives its
+ * bound).  d % 16 == 0, d <= 65536 and 16-byte aligned rows (anything else: CIS_EINVAL); m1 == 0 does not touch the device. */
 int cis_exact_knn_dev(const void* d_data, int data_dtype, int64_t m2, int d, const void* d_q, int q_dtype, int m1, int k,
                       int64_t base, int accumulate, int64_t* d_idx, double* d_dist, void* stream);
 int cis_exact_knn_half_dev(const void* d_data /* f16 [m2][d] */, int64_t m2, int d, const void* d_q, int q_dtype, int m1, int k,
                            int64_t base, int accumulate, int64_t* idx, double* dist, void* stream);
+int cis_exact_knn_int8_dev(const void* d_rows /* int8 store rows [m2][16 + d] */, int64_t m2, int d, const void* d_q, int q_dtype, int m1,
+                           int k, int64_t base, int accumulate, int64_t* d_idx, double* d_dist, void* stream);
 int cis_exact_knn(const void* data, int data_dtype, int64_t m2, int d, const void* q, int q_dtype, int m1, int k, int64_t base,
                   int accumulate, int64_t* idx, double* dist);
 int cis_exact_knn_set_mode(int mode);

@@ -7,9 +7,16 @@ after one untimed call (workspace growth).  The torch formulation -- max dot pro
 library breaks them -- streams the data in 256k-row chunks so that its score matrix stays at 8 GB.
 
     python tools/bench_exact_nn.py [--out profiles/exact_nn.json] [--small]
+    python tools/bench_exact_nn.py --stores [--small] > profiles/exact_nn_int8.txt
 
 Prints one JSON line per shape: seconds, the fraction of the 155 TFLOP/s float32 matrix rate that 2 m1 m2 d flop in that time
 amount to, and the share of queries on which the two answers agree.
+
+--stores: FeatureStore.search_exact on an int8 store (csrc/knn_int8.hip: the prefilter on the int8 matrix cores), beside a float16
+store and a float32 ResidentFeatures, all three filled from the SAME rows -- unit vectors as the int8 store dequantises them -- in one
+run: 1M x 128 and 131072 x 4096, 1024 queries, k = 100.  The time is search_exact's as a caller sees it (HIP events around the call,
+which ends with the copy of the answer, and for a store of its id column, to the host).  One JSON line per shape and store: seconds,
+repetitions, the candidates per query the prefilter left (cis_exact_knn_stats) and the bytes of the rows searched.
 """
 import argparse
 import json
@@ -50,14 +57,49 @@ def torch_nn(q, x, chunk=262144):
     return arg
 
 
+def stores_leg(dev, small):
+    import torch
+    from columbiaimagesearch_amd.lopq import eval as ev
+    from columbiaimagesearch_amd.rerank import FeatureStore, ResidentFeatures
+    m1, k = 1024, 100
+    for m2, d in ((1 << 20, 128), (1 << 17, 4096)):
+        m2 >>= 4 if small else 0
+        g = torch.Generator(device=dev).manual_seed(m2 + d)
+        x = torch.randn((m2, d), device=dev, dtype=torch.float32, generator=g)
+        x /= x.norm(dim=1, keepdim=True)
+        q = torch.randn((m1, d), device=dev, dtype=torch.float32, generator=g)
+        q /= q.norm(dim=1, keepdim=True)
+        ids = torch.arange(m2, device=dev, dtype=torch.int64)
+        i8 = FeatureStore(d, torch.float32, reserve=m2, storage=torch.int8)
+        i8.put_dev(ids, x)
+        x = i8.rows_dev()[0]  # the dequantised rows: what all three search
+        f16 = FeatureStore(d, torch.float32, reserve=m2, storage=torch.float16)
+        f16.put_dev(ids, x)
+        want = None
+        for name, obj, row_bytes in (("int8 store", i8, 16 + d), ("float16 store", f16, 2 * d), ("float32 resident", ResidentFeatures(x), 4 * d)):
+            t, n, (got, _) = timed(lambda: obj.search_exact(q, k))
+            stats = ev.exact_stats()
+            want = got if want is None else want
+            print(json.dumps({"shape": [m1, m2, d], "k": k, "rows": name, "search_exact_s": t, "reps": n, "row_bytes": row_bytes * m2,
+                              "candidates_per_query_last_pass": stats[2] / max(stats[0] - stats[1], 1), "exact_only_queries_last_pass": stats[1],
+                              "top_k_equal_to_int8_stores": float((got == want).all(axis=1).mean()),  # (float16 rounds the rows again)
+                              "device": torch.cuda.get_device_name(0)}), flush=True)
+        i8.close()
+        f16.close()
+        del x, q
+
+
 def main():
     import torch
     from columbiaimagesearch_amd.lopq import eval as ev
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
+    ap.add_argument("--stores", action="store_true", help="search_exact on an int8 store, a float16 store and float32 resident rows")
     ap.add_argument("--small", action="store_true", help="1/16 of the rows (a quick look)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
+    if args.stores:
+        return stores_leg(dev, args.small)
     rows = 1 << 20 >> (4 if args.small else 0)
     results = []
     for m1, m2, d in ((8192, rows, 128), (1024, rows, 4096)):
